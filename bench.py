@@ -20,7 +20,10 @@ Workloads (BASELINE.md numbering; the scene is synthetic, InteriorGS is not avai
 Step i renders pose (i * 77) mod n_poses — 77 is coprime to 256 and 360, so ANY K steps sample the whole sweep evenly and
 `--steps 20` measures the same workload as `--steps 100`.
 
-Prints ONE JSON line on rank 0 with the contract's fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the contract's fields (value,
+ms_per_step, ...).  `--dump-outputs DIR` writes the frame of the last timed step to DIR/frame.npy (float32 [H, W, 3]; a
+fixed, seeded sample of its pixels, DIR/frame_sample.npy, when the frame exceeds 64 MB).  `--full` adds everything else
+the line can carry (the checks and side measurements below, value_100, also_measured, verify, N > 1's second sharding mode):
   roofline      the dominant kernel (the fused sort + composite) against the HBM roofline, from its duration ALONE (one
                 frame at a time, HIP events on the launch stream — the figure `rocprofv3 --kernel-trace --stats` of
                 `--no-pipeline` reproduces, profiles/), with SURVEY.md §8(d)'s bytes; never from the overlapped span;
@@ -119,6 +122,13 @@ def parse():
     ap.add_argument("--no-pipeline", action="store_true",
                     help="issue the frames of the sweep strictly one after another (default: SGS_FLAG_PIPELINED, a few "
                          "independent frames in flight on the library's internal streams)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: verify, value_100, the roofline / latency post-pass, the upload probes, the compressed "
+                         "and trained scenes, the reference's resolutions, cpu_baseline and N>1's second sharding mode (the --no-* "
+                         "options above switch single ones off again); default: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame of the last timed step as DIR/frame.npy (float32 [H, W, 3]; a fixed, "
+                         "seeded sample of its pixels as DIR/frame_sample.npy [n, 3] when the frame exceeds 64 MB)")
     return ap.parse_args()
 
 
@@ -205,6 +215,25 @@ def pct(xs):
     import numpy as np
     return {"p10": float(np.percentile(xs, 10)), "p50": float(np.percentile(xs, 50)), "p90": float(np.percentile(xs, 90)),
             "mean": float(np.mean(xs)), "n": len(xs)}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21
+
+
+def dump_frame(out_dir, frame):
+    """--dump-outputs: the frame a caller of the timed path receives for its last step, as float32 (a uint8 RGBA frame
+    keeps its 0..255 values).  A frame over DUMP_MAX_BYTES is written as a fixed sample of its pixels (seed 0, in raster
+    order), so that two builds compare the same pixels."""
+    import numpy as np
+    a = frame.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), a)
+        return
+    px = a.reshape(-1, a.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=min(px.shape[0], DUMP_SAMPLE_PIXELS), replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), np.ascontiguousarray(px[idx]))
 
 
 def self_launch_argv(n_gpus, argv, port=None):
@@ -314,7 +343,8 @@ def main():
                  "what": "scene load, once per scene and outside every timed region: Z-order (device radix sort of 63-bit Morton keys), layout into "
                          "wave-chunked rows, per-chunk bounds.  arrays_on_device = the fp32 tensors already in HBM (236 B per Gaussian at degree 3); "
                          "compressed_* = the PlayCanvas compressed.ply payload (16 B + 45 SH bytes per Gaussian), dequantised by the layout kernel"}
-    if rank == 0 and world == 1 and not args.no_upload_probe and not args.scene:
+    full = args.full
+    if full and rank == 0 and world == 1 and not args.no_upload_probe and not args.scene:
         from sage_gs import ply as ply_mod
         t0 = time.perf_counter()
         g_host = scenes.to_gaussians(scene, "cpu")
@@ -401,9 +431,13 @@ def main():
     def short_sweep(count):
         return batch_frames is not None and 0 < count <= batch_frames.shape[0] and K <= SHORT
 
+    last_frame = [None]      # what the caller of the path holds for the last frame a runner issued (--dump-outputs)
+
     def run_cameras(first, count, timed):
         """Camera shards: step i is one pose PER RANK (rank rk renders pose (i * world + rk) of the strided sweep); no
         data-path collective.  Returns this rank's per-frame average statistics; every frame is checked for overflow."""
+        if count > 0:
+            last_frame[0] = batch_frames[count - 1] if short_sweep(count) else frames[(count - 1) % len(frames)]
         if short_sweep(count):
             # a short sweep is ONE call of the batch entry (the generate_images.py loop, SURVEY A4): frame groups (eight frames) per
             # set of launches fill and drain the pipeline faster than frames issued one by one (round 3: 0.235 vs 0.256 ms/frame at
@@ -423,6 +457,7 @@ def main():
         frames are rendered through the pipelined lanes and travel in one asynchronous exchange, double-buffered."""
         sharded = sharded or sharded_head
         acc, n_acc, i = None, 0, 0
+        last_batch = None
         if warming[0] and pipelined and count > 0:
             # the library's batch path rotates over group x group_lanes sets of intermediates (buffers allocated on first use): touch
             # them all before the clock starts, whatever W is
@@ -439,10 +474,10 @@ def main():
             if pipelined:
                 # (no per-stage events inside the timed region: they would force one call per frame instead of one call per
                 #  batch; the stage times of rank 0's band come from the one-at-a-time post-pass)
-                sharded.render_batch(batch_cams, gs)
+                last_batch = (sharded.render_batch(batch_cams, gs), nb - 1)
                 st = None
             else:
-                sharded.render(batch_cams[0], gs)
+                last_frame[0] = sharded.render(batch_cams[0], gs)
                 st = r.last_stats
             if st is not None and timed:
                 if acc is None:
@@ -453,6 +488,8 @@ def main():
                 n_acc += nb
             i += nb
         sharded.finish()
+        if last_batch is not None:
+            last_frame[0] = last_batch[0].frame(last_batch[1])      # (rank 0: the gathered frame; None elsewhere)
         if acc is not None:
             for n in STAGE_NAMES:
                 acc["ms"][n] /= n_acc
@@ -497,7 +534,7 @@ def main():
     # timed FIRST, and a watchdog prints a line with it as the headline should the exchange of the tile-row mode never
     # come back on this node — the driver gets one JSON line either way
     pre_second, guard = None, None
-    if rows_primary and not args.no_secondary:
+    if full and rows_primary and not args.no_secondary:
         import threading
         dt2, _ = measure(run_cameras, min(W, 8), K, False)
         pre_second = {"shard": "cameras", "value": K * world / dt2, "unit": "frames/s", "steps": K, "ms_per_step": 1e3 * dt2 / K,
@@ -580,17 +617,19 @@ def main():
 
     verify = None
     try:
-        if not args.no_verify and (world > 1 or not (args.scene or args.scene_kind == "trained")):
+        if full and not args.no_verify and (world > 1 or not (args.scene or args.scene_kind == "trained")):
             verify = verify_rows()
         elapsed, avg = measure(run_rows if rows_primary else run_cameras, W, K, timing)
     except Exception as e:             # noqa: BLE001
         if guard is None:
             raise
         bail_rows(f"the tile-row-sharded sweep failed: {type(e).__name__}: {e}"[:300])
+    if args.dump_outputs and rank == 0 and last_frame[0] is not None:       # (camera shards: rank 0's own last frame)
+        dump_frame(args.dump_outputs, last_frame[0])
     frames_total = K if (rows_primary or world == 1) else K * world       # camera shards: one frame per rank per step
     # N > 1, tile rows: the exchange alone — the gatherv of already rendered bands, no rendering — per frame (all ranks take part)
     gather_us, gather_ops = None, None
-    if rows_primary and pipelined and getattr(sharded_head, "_ring", None):
+    if full and rows_primary and pipelined and getattr(sharded_head, "_ring", None):
         from sage_gs.dist import FrameGather
         gather_us, gather_ops = {}, {}
         gq = sharded_head._ring[0]
@@ -621,7 +660,7 @@ def main():
     # of the scene) —, W warm-up steps already done; and, beside it, the 100 frames issued one by one on the library's three lanes
     # (SGS_FLAG_PIPELINED: what a caller that cannot batch gets; rounds 4-5 quoted this one as value_100)
     value_100 = None
-    if world == 1 and K < 64 and pipelined:
+    if full and world == 1 and K < 64 and pipelined:
         K0, bf0 = K, batch_frames
         lanes_100 = None
         try:
@@ -645,7 +684,7 @@ def main():
     # payload and uploaded with sgs_scene_upload_compressed — the 8-bit SH coefficients stay bytes in HBM, k_preprocess streams 64 B of SH per
     # visible Gaussian instead of 192 B.  Not the headline: quantisation makes it a (slightly) different scene than the fp32 arrays.
     compressed_scene = None
-    if world == 1 and pipelined and not args.scene and not args.no_upload_probe:
+    if full and world == 1 and pipelined and not args.scene and not args.no_upload_probe:
         gs_fp32, gs_packed = gs, None
         try:
             dvq = quantise_on_gpu(scenes.to_gaussians(scene, device))
@@ -682,7 +721,7 @@ def main():
     frame_ms, latency = [], []
     counts = {"n_visible": 0, "d_total": 0, "d_super": 0, "d_fetched": 0, "max_tile_len": 0, "n_spill_tiles": 0}
     pixels = 0
-    if rank == 0:
+    if full and rank == 0:
         own = sharded.g.render_target(0) if rows_primary else {"out": frame}      # (rows: rank 0's band of the even split)
         sel = [pose(W + i) for i in range(K)] if (rows_primary or world == 1) else [pose((W + i) * world) for i in range(K)]
         r.render(cams[sel[0]], gs, timing=timing, **own)          # (untimed: the event sets are created on first use)
@@ -742,7 +781,8 @@ def main():
                                        + (", bands packed to uint8 RGBA on every rank (4-byte pixels travel)" if head_rgba8 else " (fp32 bands)")
                                        + (f" (bands of {sharded.batch} frames per exchange)" if pipelined else "")
                                        if rows_primary else cameras_desc),
-                       "per_frame": {k: (v / nfr if k != "max_tile_len" else v) for k, v in counts.items()}},
+                       # (the counts of the one-at-a-time post-pass: --full)
+                       "per_frame": {k: (v / nfr if k != "max_tile_len" else v) for k, v in counts.items()} if full else None},
         }
         if timing and frame_ms:
             stages = {}
@@ -846,10 +886,11 @@ def main():
         if value_100 is not None:
             out["value_100"] = value_100
         # which of the two is the headline: `value` — the driver's K timed steps after the pre-heat; value_100 is the same sweep over 100 steps
-        out["headline"] = f"value = {K} timed steps (BASELINE.md asks for >= 100: value_100 beside it when K < 64)"
+        out["headline"] = f"value = {K} timed steps (BASELINE.md asks for >= 100: " + \
+            ("value_100 beside it when K < 64)" if full else "--full adds value_100 beside it when K < 64)")
         if compressed_scene is not None:
             out["also_measured"] = dict(out.get("also_measured") or {}, compressed_scene=compressed_scene)
-        if world == 1 and not args.no_lowres:
+        if full and world == 1 and not args.no_lowres:
             # the reference's own resolutions (simple_env.py:52 get_rgb at 640x480; generate_images.py:43 at 1024x768): what a
             # synchronous get_rgb()-style caller sees per frame on the same scene and poses, one frame at a time
             low = {}
@@ -943,7 +984,7 @@ def main():
             out["also_measured"] = dict(out.get("also_measured") or {}, reference_resolutions=dict(
                 low, what="one frame at a time at the resolutions the reference renders (run_benchmark.py:1409-1419 --low-res 320x240, simple_env.py:52 "
                           "640x480, generate_images.py:43 1024x768), same scene and poses; get_rgba = the same through the GsCamera adapter to host uint8"))
-        if world == 1 and pipelined and not args.no_lowres and config != 5:
+        if full and world == 1 and pipelined and not args.no_lowres and config != 5:
             # What the reference's data generator renders is a PATH (generate_images.py:408-436: consecutive waypoints), not the headline's
             # stride-77 pose order: the same scene at the same resolution over consecutive headings from one position (5.6 degrees apart; the
             # lens is 105 degrees wide).  The frames of such a batch's groups see nearly the same part of the scene, and the library projects
@@ -965,7 +1006,7 @@ def main():
                             "best of three) — a trajectory's frames, whose groups share their reads of the scene"})
             except Exception as e:
                 out["also_measured"] = dict(out.get("also_measured") or {}, trajectory_sweep={"error": f"{type(e).__name__}: {e}"[:300]})
-        if world == 1 and not args.no_trained and not args.scene and args.scene_kind == "room" and config != 5:
+        if full and world == 1 and not args.no_trained and not args.scene and args.scene_kind == "room" and config != 5:
             # Real InteriorGS scenes are TRAINED 3DGS, not make_room: log-normal scales with a heavy tail, strong anisotropy, 40 % of the splats
             # nearly transparent, floaters, no spatial order (scenes.make_trained_like; no checkpoint is available offline).  The same sweep and
             # the same one-at-a-time pass on such a scene of the same size, with every stage's algorithmic bytes and GB/s: here the binning, not
@@ -1008,7 +1049,7 @@ def main():
                 del tb, sc_t, cams_t
             except Exception as e:             # noqa: BLE001 - a neighbour of the headline, never fatal for it
                 out["also_measured"] = dict(out.get("also_measured") or {}, trained_scene={"error": f"{type(e).__name__}: {e}"[:300]})
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(scene, [cams[pose(W + i)] for i in range(min(K, 32))], args.cpu_seconds)
     else:
         out = None
@@ -1047,7 +1088,7 @@ def main():
             t8.cancel()
             if rank == 0:
                 out["also_measured"][third_key] = third
-    elif world > 1 and not args.no_secondary:
+    elif full and world > 1 and not args.no_secondary:
         import threading
         finished = threading.Event()
 

@@ -70,3 +70,59 @@ def test_scene_instances_are_stable_and_cover_every_scene_once(tmp_path):
     assert sweep.find_scene_file(str(root), "0001") == (str(root / "0001.ply"), False)
     assert sweep.find_scene_file(str(root), "0002") == (str(root / "0002" / "3dgs_compressed.ply"), True)
     assert sweep.find_scene_file(str(root), "0003") == (None, False)
+
+
+def test_dump_frame_writes_float32_and_a_fixed_sample_of_a_large_frame(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's frame as float32 .npy (uint8 RGBA frames keep their 0..255 values); a frame over the size limit
+    becomes a seeded sample of its pixels, the same pixels in every run."""
+    import numpy as np
+    import torch
+    b = _bench()
+    f32 = torch.rand((6, 5, 3), generator=torch.Generator().manual_seed(1))
+    b.dump_frame(str(tmp_path / "a"), f32)
+    a = np.load(tmp_path / "a" / "frame.npy")
+    assert a.dtype == np.float32 and a.shape == (6, 5, 3) and (a == f32.numpy()).all()
+    u8 = torch.arange(6 * 5 * 4, dtype=torch.int64).remainder(256).to(torch.uint8).reshape(6, 5, 4)
+    b.dump_frame(str(tmp_path / "b"), u8)
+    a = np.load(tmp_path / "b" / "frame.npy")
+    assert a.dtype == np.float32 and (a == u8.numpy().astype(np.float32)).all()
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 100)
+    monkeypatch.setattr(b, "DUMP_SAMPLE_PIXELS", 7)
+    for d in ("c", "d"):
+        b.dump_frame(str(tmp_path / d), f32)
+        assert not (tmp_path / d / "frame.npy").exists()
+    s, s2 = np.load(tmp_path / "c" / "frame_sample.npy"), np.load(tmp_path / "d" / "frame_sample.npy")
+    assert s.dtype == np.float32 and s.shape == (7, 3) and (s == s2).all()
+    px = f32.numpy().reshape(-1, 3)
+    assert all(any((row == p).all() for p in px) for row in s)          # pixels of the frame, not made-up values
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_and_dumps_the_last_steps_frame(tmp_path):
+    """A plain run: exactly --steps timed steps, the contract's fields and none of --full's side measurements; --dump-outputs holds the
+    frame of the last timed step — the frame the renderer draws for that pose on its own."""
+    import json
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "sage-3d_official_amd"))
+    from sage_gs import Renderer, scenes
+    K, W, n = 5, 2, 300_000
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                        "--gaussians", str(n), "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == K and d["warmup"] == W and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["ms_per_step"] * K - d["timed_region_ms"]) < 1e-6 * d["timed_region_ms"]
+    assert abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    for side in ("roofline", "latency_ms", "value_100", "also_measured", "cpu_baseline"):
+        assert side not in d, side
+    assert d["verify"] is None
+    got = np.load(tmp_path / "out" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 3) and np.isfinite(got).all()
+    sc = scenes.make_room(n, seed=2)
+    cams = scenes.room_cameras(sc, 1920, 1080, n_positions=4, n_yaw=64, seed=2)
+    r = Renderer("cuda:0")
+    gs = r.upload(scenes.to_gaussians(sc, "cuda:0"))
+    ref = r.render(cams[((W + K - 1) * 77) % len(cams)], gs).cpu().numpy()
+    r.close()
+    assert float(np.abs(got - ref).max()) < 1e-5 and float(ref.max()) > 0

@@ -220,7 +220,7 @@ def test_bench_multi_rank_line_verifies_itself_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SGS_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--gaussians", "300000",
-                        "--no-secondary", "--no-cpu-baseline", "--no-lowres", "--preheat-ms", "0"],
+                        "--full", "--no-secondary", "--no-cpu-baseline", "--no-lowres", "--preheat-ms", "0"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
