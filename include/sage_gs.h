@@ -167,7 +167,10 @@ int sgs_set_record_capacity(sgs_ctx* ctx, int64_t max_records);
  * sgs_tuning_default() fills what the bench runs; sgs_set_tuning() takes effect for the scenes uploaded and the frames issued AFTER it
  * (it completes the frames in flight first).  Frames do not depend on any of these, bit for bit (tests/test_gpu_parity.py).  No
  * counterpart in the reference (one synchronous SimulationApp per process, simple_env.py:163).  Version 112 (113: fine_tile_pixels, 114: fine_tile_growth — the two
- * fields frames DO depend on, to fp32 rounding). */
+ * fields frames DO depend on, to fp32 rounding).  The tiling a frame gets is decided from a probe of the scene drawn by the Gaussians'
+ * indices in the caller's order, so neither morton nor the upload path (sgs_scene_upload or sgs_scene_upload_compressed of the same
+ * values) changes it; reordering the input still can, to fp32 rounding — as it can reorder the blend of splats whose depths tie (equal
+ * depths blend in the order of the caller's indices). */
 typedef struct sgs_tuning {
     int32_t lanes;            /* 3  frames in flight for SGS_FLAG_PIPELINED single frames: each lane has its own stream and intermediates (1..16) */
     int32_t group;            /* 8  frames per set of launches in sgs_render_batch* (blockIdx.y selects the frame; 1..8).  The full frames of a

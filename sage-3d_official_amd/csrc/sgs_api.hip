@@ -92,6 +92,7 @@ struct Lane {
 };
 
 constexpr int kMaxLanes = 16;
+constexpr int64_t kMaxRecords = 0xfffffff0ll;   // record capacity: tile offsets are 32-bit
 
 struct sgs_ctx {
     int device = 0;
@@ -203,7 +204,7 @@ int ensure_tiles(sgs_ctx* ctx, Lane& L, int tiles) {
 int ensure_records(sgs_ctx* ctx, Lane& L) {
     if (L.rec_cap >= ctx->rec_cap_wanted && L.rec) return SGS_OK;
     const int64_t cap = std::max<int64_t>(ctx->rec_cap_wanted, 1024);
-    if (cap > 0xfffffff0ll) SGS_FAIL(ctx, SGS_ERR_INVALID, "record capacity %lld exceeds 2^32", (long long)cap);
+    if (cap > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "record capacity %lld exceeds 2^32", (long long)cap);
     int rc;
     if ((rc = grow(ctx, L.rec, (size_t)cap)) != SGS_OK) return rc;
     if ((rc = grow(ctx, L.alt, (size_t)cap)) != SGS_OK) return rc;
@@ -761,19 +762,26 @@ int sgs_set_tuning(sgs_ctx* ctx, const sgs_tuning* t) {
     if (t->record_capacity <= 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_tuning.record_capacity must be positive");
     if (t->fine_tile_pixels < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_tuning.fine_tile_pixels must not be negative (0 = never)");
     if (!(t->fine_tile_growth >= 1.0)) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_tuning.fine_tile_growth must be at least 1 (>= 16: whenever the pixel rule allows)");
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();                          // frames in flight were issued under the old values (their verdicts stay for sgs_frame_sync)
+    // the capacity first: it is the one field that can still be refused (its own limit, an allocation); a refused tuning changes nothing
+    if (t->record_capacity != ctx->rec_cap_wanted) {
+        const int rc = sgs_set_record_capacity(ctx, t->record_capacity);
+        if (rc != SGS_OK) return rc;
+    } else {
+        SGS_HIP(ctx, hipSetDevice(ctx->device));
+        SGS_HIP(ctx, hipDeviceSynchronize());              // frames in flight were issued under the old values (their verdicts stay for sgs_frame_sync)
+    }
     ctx->n_lanes = t->lanes; ctx->next_lane = 0; ctx->group = t->group; ctx->group_lanes = t->group_lanes; ctx->morton = t->morton != 0;
     ctx->fine_tile_pixels = t->fine_tile_pixels; ctx->fine_tile_growth = t->fine_tile_growth;
-    if (t->record_capacity != ctx->rec_cap_wanted) return sgs_set_record_capacity(ctx, t->record_capacity);
     return SGS_OK;
 }
 
 int sgs_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
     if (!ctx) return SGS_ERR_INVALID;
     if (max_records <= 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "max_records must be positive");
-    (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
+    if (max_records > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "record capacity %lld exceeds 2^32", (long long)max_records);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    SGS_HIP(ctx, hipDeviceSynchronize());
+    const int64_t prev = ctx->rec_cap_wanted;
     ctx->rec_cap_wanted = max_records;
     for (Lane& L : ctx->lanes) {      // force reallocation at the requested size (lanes other than 0: on next use)
         L.rec_cap = 0;
@@ -781,7 +789,11 @@ int sgs_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
             for (unsigned long long** q : {&L.rec, &L.alt, &L.part}) if (*q) { (void)hipFree(*q); *q = nullptr; }
         }
     }
-    return ensure_records(ctx, ctx->lanes[0]);
+    // the new capacity holds only once lane 0's buffers exist; a failed allocation leaves the previous one wanted (every lane
+    // reallocates at it on its next frame)
+    const int rc = ensure_records(ctx, ctx->lanes[0]);
+    if (rc != SGS_OK) ctx->rec_cap_wanted = prev;
+    return rc;
 }
 
 namespace {
@@ -853,14 +865,20 @@ int layout_scene(sgs_ctx* ctx, sgs_scene* sc, const float* const* src, const sgs
         if ((e = hipDeviceSynchronize()) != hipSuccess) fail("k_scene_layout / k_chunk_bounds", e);
     }
     if (rc == SGS_OK && n > 0) {
-        // the probe (fine_shift_of): a pre-sample of up to 64 Ki Gaussians at even strides through the layout comes to the host; 512 of them
-        // are drawn from it — systematically, with probability 1/2 (1 / M0 + trace_i / sum of traces) each — and their covariances formed once
+        // the probe (fine_shift_of): a pre-sample of up to 64 Ki Gaussians at even strides through the caller's order comes to the host (through
+        // the inverse of the Z-order permutation, in the sort's spare index buffer); 512 of them are drawn from it — systematically, with
+        // probability 1/2 (1 / M0 + trace_i / sum of traces) each — and their covariances formed once
         const int M0 = (int)std::min<int64_t>(n, 65536), M = std::min(M0, 512);
         float4* d_probe = nullptr;
+        unsigned* d_inv = nullptr;
+        if (d_perm) {
+            d_inv = idx[d_perm == idx[0] ? 1 : 0];
+            hipLaunchKernelGGL(sgs::k_invert_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (long long)n, d_perm, d_inv);
+        }
         std::vector<float4> rows((size_t)M0 * SGS_GEOM_ROWS);
         if ((e = hipMalloc(reinterpret_cast<void**>(&d_probe), rows.size() * sizeof(float4))) != hipSuccess) fail("hipMalloc", e);
         else {
-            hipLaunchKernelGGL(sgs::k_probe_gather, dim3((unsigned)((M0 + 255) / 256)), dim3(256), 0, 0, (long long)n, M0, sc->geom, d_probe);
+            hipLaunchKernelGGL(sgs::k_probe_gather, dim3((unsigned)((M0 + 255) / 256)), dim3(256), 0, 0, (long long)n, M0, d_inv, sc->geom, d_probe);
             if ((e = hipMemcpy(rows.data(), d_probe, rows.size() * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) fail("reading the probe", e);
             (void)hipFree(d_probe);
         }

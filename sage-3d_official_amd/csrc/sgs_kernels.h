@@ -401,12 +401,22 @@ __global__ __launch_bounds__(256) void k_chunk_bounds(long long n, long long n_c
     }
 }
 
-// The scene's PROBE (sgs_api.hip fine_shift_of): the geometry rows of M Gaussians at even strides through the layout, for the host.
-__global__ __launch_bounds__(256) void k_probe_gather(long long n, int M, const float4* __restrict__ geom, float4* __restrict__ out) {
+// The inverse of the Z-order permutation: inv[perm[p]] = p (original index -> layout position), for k_probe_gather.
+__global__ __launch_bounds__(256) void k_invert_perm(long long n, const unsigned* __restrict__ perm, unsigned* __restrict__ inv) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) inv[perm[p]] = (unsigned)p;
+}
+
+// The scene's PROBE (sgs_api.hip fine_shift_of): the geometry rows of M Gaussians at even strides through the ORIGINAL order (the caller's),
+// looked up in the layout through inv (nullptr: the layout is the original order), for the host — so the probe, and the tiling it decides,
+// depend on the scene and its order alone, not on sgs_tuning.morton or the upload path.
+__global__ __launch_bounds__(256) void k_probe_gather(long long n, int M, const unsigned* __restrict__ inv, const float4* __restrict__ geom,
+                                                      float4* __restrict__ out) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= M) return;
-    long long p = (long long)(((double)k + 0.5) * (double)n / (double)M);
-    p = p < n ? p : n - 1;
+    long long q = (long long)(((double)k + 0.5) * (double)n / (double)M);
+    q = q < n ? q : n - 1;
+    const long long p = inv ? (long long)inv[q] : q;
     const long long chunk = p >> 6, lane = p & 63;
 #pragma unroll
     for (int r = 0; r < SGS_GEOM_ROWS; ++r) out[(size_t)k * SGS_GEOM_ROWS + r] = geom[(chunk * SGS_GEOM_ROWS + r) * SGS_WAVE + lane];

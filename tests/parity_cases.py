@@ -662,3 +662,97 @@ def case_fine_tile_decision(drv, n=500):
             assert (band[16:16 * (gy - 1)] == got[16:16 * (gy - 1)]).all(), f"seed {seed} {w}x{h}: a band chose another tiling than its frame"
             drv.set_tuning(fine_tile_pixels=keep["fine_tile_pixels"], fine_tile_growth=keep["fine_tile_growth"])
     assert seen == {16, 8, 4}, seen          # (the five scenes span the three outcomes)
+
+
+# Scenes whose splats straddle sgs_tuning.fine_tile_growth at small resolutions: random_scene(n, 700 + i, 0, scale=(s / 2, 2 s),
+# opac_mu=1.0) for s = LAYOUT_SCALES[i], seen by an identity camera with f = 0.9 w.  While the probe was drawn at even strides through the
+# LAYOUT, four of them (i = 12, 15, 17, 19) got another tiling — and another frame — with morton = 0 than with morton = 1 (4000 Gaussians:
+# 1900 against 475 tiles at 200x152, 192 against 768 / 48 against 192 / 130 against 475 at 128x96 and 200x152).
+LAYOUT_SCALES = np.geomspace(0.004, 0.3, 28)
+LAYOUT_FLIPS = (12, 15, 17, 19)
+
+
+def layout_scene(i, n=4000):
+    s = float(LAYOUT_SCALES[i])
+    return random_scene(n, 700 + i, 0, scale=(s / 2, 2 * s), opac_mu=1.0)
+
+
+def layout_cameras(res=((128, 96), (200, 152))):
+    return [onp.Camera(w, h, 0.9 * w, 0.9 * w, w / 2.0, h / 2.0, np.eye(4, dtype=np.float32)) for w, h in res]
+
+
+def frames_of(drv, cams):
+    """The frames of `cams` on the driver's scene as the library renders them by itself (its own tiling), with (n_tiles, n_visible, d_total)."""
+    out = []
+    for cam in cams:
+        img, st = drv.render(cam, stats=False)
+        out.append((img, (st["n_tiles"], st["n_visible"], st["d_total"])))
+    return out
+
+
+def case_tiling_does_not_depend_on_the_layout(drv, picks=range(28), n=4000, cams=None):
+    """The tiling a small frame gets (fine_shift_of) is estimated from the scene's probe of 512 Gaussians; the probe is drawn by the Gaussians'
+    indices in the caller's order, so the layout of the scene on the device — Z-order (sgs_tuning.morton = 1) or the caller's order
+    (morton = 0) — must not change the tiling, nor, therefore, a pixel: same n_tiles / N_v / D, frames bit for bit.  The scales sweep across
+    the growth threshold (every tiling is chosen somewhere) and take in the scenes that flipped with the layout (LAYOUT_FLIPS).
+    Returns the frames (morton = 1) by scene for further comparisons (the GPU's compressed upload)."""
+    cams = layout_cameras() if cams is None else cams
+    keep = drv.tuning()["morton"]
+    tilings, frames = set(), {}
+    try:
+        for i in picks:
+            scene = layout_scene(i, n)
+            got = {}
+            for morton in (1, 0):
+                drv.set_tuning(morton=morton)
+                drv.upload(*scene)
+                got[morton] = frames_of(drv, cams)
+            for cam, (a, sa), (b, sb) in zip(cams, got[1], got[0]):
+                what = f"scene {i} (seed {700 + i}, s {LAYOUT_SCALES[i]:.4f}, n {n}) at {cam.width}x{cam.height}"
+                assert sa == sb, f"{what}: (n_tiles, N_v, D) {sa} with the scene in Z-order, {sb} in the caller's order"
+                assert (a == b).all(), f"{what}: the frame depends on the scene's layout"
+                tilings.add((cam.width, sa[0]))
+            frames[i] = got[1]
+    finally:
+        drv.set_tuning(morton=keep)
+    return frames, tilings
+
+
+def case_refused_capacity_changes_nothing(drv):
+    """A record capacity the library refuses (2^33: more than its 32-bit tile offsets can address; validation refuses it, nothing is allocated)
+    must leave the context as it was: the tuning reads back unchanged and the next frame renders, the same frame as before.  The same for
+    sgs_set_tuning carrying that capacity: SGS_ERR_INVALID, and none of its other fields applied either."""
+    from sage_gs import _capi
+    scene = random_scene(900, 43, 1, scale=(0.05, 0.3))
+    cam = onp.Camera(96, 64, 70.0, 70.0, 48.0, 32.0, np.eye(4, dtype=np.float32))
+    drv.upload(*scene)
+    want, st0 = drv.render(cam, stats=False)
+    keep = drv.tuning()
+    assert keep["lanes"] != 5 and keep["morton"] == 1
+    for what, attempt in (("sgs_set_record_capacity", lambda: drv.set_record_capacity(1 << 33)),
+                          ("sgs_set_tuning", lambda: drv.set_tuning(lanes=5, group=2, group_lanes=3, morton=0, record_capacity=1 << 33))):
+        try:
+            attempt()
+        except _capi.SgsError as e:
+            assert e.code == -1 and "2^32" in str(e), (what, e.code, str(e))        # SGS_ERR_INVALID
+        else:
+            raise AssertionError(f"{what}: a record capacity of 2^33 was accepted")
+        assert drv.tuning() == keep, (what, drv.tuning(), keep)
+        got, st = drv.render(cam, stats=False)
+        assert (got == want).all() and (st["n_visible"], st["d_total"]) == (st0["n_visible"], st0["d_total"]), f"{what}: the next frame differs"
+    # ... and once more: still refused (a refused value that had been stored would now compare as "unchanged")
+    try:
+        drv.set_tuning(lanes=5, group=2, group_lanes=3, morton=0, record_capacity=1 << 33)
+    except _capi.SgsError as e:
+        assert e.code == -1                                  # SGS_ERR_INVALID
+    else:
+        raise AssertionError("sgs_set_tuning: a record capacity of 2^33 was accepted the second time")
+    assert drv.tuning() == keep
+    # the capacity the context already holds (unchanged, no reallocation) with the other fields: applied
+    drv.set_tuning(lanes=5, group=2, group_lanes=3, morton=0)
+    t = drv.tuning()
+    assert (t["lanes"], t["group"], t["group_lanes"], t["morton"], t["record_capacity"]) == (5, 2, 3, 0, keep["record_capacity"]), t
+    got, st = drv.render(cam, stats=False)
+    assert (got == want).all()
+    drv.set_tuning(**{k: keep[k] for k in ("lanes", "group", "group_lanes", "morton")})
+    assert drv.tuning() == keep

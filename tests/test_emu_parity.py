@@ -446,3 +446,14 @@ def test_tuning_surface(drv):
             assert (img == want).all() and st["d_total"] == st0["d_total"]
     u = _capi.SgsTuning(*keep)
     lib.check(lib.sgs_set_tuning(ctx, C.byref(u)), ctx)
+
+
+def test_tiling_does_not_depend_on_the_scene_layout(drv):
+    """sgs_tuning.morton must not change a frame (include/sage_gs.h): the probe that decides a small frame's tiling is drawn by original
+    index.  The scenes that flipped while it was drawn through the layout (parity_cases.LAYOUT_FLIPS), and others across the threshold."""
+    _, tilings = pc.case_tiling_does_not_depend_on_the_layout(drv, picks=(2, 8) + pc.LAYOUT_FLIPS + (22, 27))
+    assert {t for w, t in tilings if w == 128} == {48, 192, 768}, tilings          # (16x16, 8x8 and 4x4 tiles all chosen somewhere)
+
+
+def test_refused_record_capacity_changes_nothing(drv):
+    pc.case_refused_capacity_changes_nothing(drv)
