@@ -166,10 +166,11 @@ def render(means, scales, quats, opacities, sh, sh_degree, cam, cfg=None, tile_r
             conic=_np(f.conic, (N, 3), np.float32), opacity=_np(f.opacity, (N,), np.float32),
             rgb=_np(f.rgb, (N, 3), np.float32), offsets=_np(f.offsets, (T + 1,), np.int64),
             ids=_np(f.ids, (int(f.D),), np.int32), consumed=_np(f.consumed, (T,), np.int64),
-            final_T=_np(f.final_T, (H, W), np.float32), n_contrib=_np(f.n_contrib, (H, W), np.int32))
+            final_T=_np(f.final_T, (H, W), np.float32))
     aux["margin"] = _np(f.margin, (H, W), np.float32)
     aux["depth_image"] = _np(f.depth_img, (H, W), np.float32)
     aux["final_T"] = _np(f.final_T, (H, W), np.float32)
+    aux["n_contrib"] = _np(f.n_contrib, (H, W), np.int32)     # (the tight parity budget of tests/tight_parity.py: with want="image" too)
     if real == "f64":
         aux["recheck"] = Recheck(lib, fp, cfg, REL_MARGIN)      # owns the frame from here on
     else:

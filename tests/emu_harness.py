@@ -26,14 +26,24 @@ if PKG not in sys.path:
 from sage_gs import _capi  # noqa: E402
 
 
-def build_emu(force=False):
-    os.makedirs(os.path.dirname(EMU_LIB), exist_ok=True)
-    stale = force or not os.path.exists(EMU_LIB) or any(
-        os.path.getmtime(s) > os.path.getmtime(EMU_LIB) for s in SRCS)
-    if stale:
-        subprocess.check_call(["g++", "-x", "c++", "-std=c++17", "-O2", "-g", "-fopenmp", "-fPIC", "-shared",
-                               "-I", EMU_DIR, SRCS[0], "-o", EMU_LIB])
-    return EMU_LIB
+def build_emu(force=False, src_dir=None, out=None, wait=True):
+    """The emulator library of csrc/ at EMU_LIB — or, given src_dir (a copy of csrc/, e.g. a mutant of it) and out, of that copy at
+    `out` (sgs_api.hip includes ../../include/sage_gs.h: the copy needs one there too).  wait=False: start the compiler and return
+    its Popen (None when the library is up to date); the caller waits."""
+    csrc = os.path.join(PKG, "csrc") if src_dir is None else str(src_dir)
+    lib_out = EMU_LIB if out is None else str(out)
+    srcs = [os.path.join(csrc, n) for n in ("sgs_api.hip", "sgs_kernels.h", "sgs_common.h")] + SRCS[3:]
+    os.makedirs(os.path.dirname(lib_out), exist_ok=True)
+    stale = force or not os.path.exists(lib_out) or any(
+        os.path.getmtime(s) > os.path.getmtime(lib_out) for s in srcs)
+    if not stale:
+        return lib_out if wait else None
+    cmd = ["g++", "-x", "c++", "-std=c++17", "-O2", "-g", "-fopenmp", "-fPIC", "-shared",
+           "-I", EMU_DIR, srcs[0], "-o", lib_out]
+    if not wait:
+        return subprocess.Popen(cmd)
+    subprocess.check_call(cmd)
+    return lib_out
 
 
 _lib = None
@@ -49,8 +59,8 @@ def lib():
 class EmuRenderer:
     """Minimal numpy-facing driver of the C ABI (host pointers: the emulator's 'device' is the host)."""
 
-    def __init__(self, record_capacity=1 << 20):
-        self.lib = lib()
+    def __init__(self, record_capacity=1 << 20, lib_path=None):
+        self.lib = lib() if lib_path is None else _capi.Lib(lib_path)     # lib_path: another emulator build (build_emu(src_dir=...))
         self.ctx = C.c_void_p()
         self.lib.check(self.lib.sgs_create(0, _capi.BACKEND_HIP, C.byref(self.ctx)))
         self.lib.check(self.lib.sgs_set_record_capacity(self.ctx, record_capacity), self.ctx)

@@ -12,6 +12,7 @@ import numpy as np
 import oracle_c
 import oracle_np as onp
 from conftest import assert_frame_close
+from tight_parity import assert_depth_coverage_tight, assert_frame_tight
 
 
 def random_scene(n, seed, deg=0, box=((-2, 2), (-2, 2), (2, 8)), scale=(0.02, 0.2), opac_mu=0.0):
@@ -137,6 +138,7 @@ def check_against_oracle(drv, scene, cam, cfg=None, rows=(0, -1), what="", queue
     gy = (cam.height + 15) // 16
     ya, yb = 16 * rows[0], min(cam.height, 16 * (gy if rows[1] < 0 else rows[1]))
     worst = assert_frame_close(img[ya:yb], ref[ya:yb], aux["margin"][ya:yb], aux["recheck"], what=what, y0=ya)
+    assert_frame_tight(img[ya:yb], ref[ya:yb], aux, y0=ya, what=what)
     if "d_fetched" in st_loose and st_loose["d_fetched"]:
         # D_f (reference binning) only differs from the oracle's where a pixel sat on the termination threshold
         assert abs(st_loose["d_fetched"] - aux["D_f"]) <= max(8, 2e-3 * aux["D_f"]), (what, st_loose["d_fetched"], aux["D_f"])
@@ -157,6 +159,7 @@ def check_against_oracle(drv, scene, cam, cfg=None, rows=(0, -1), what="", queue
                 img_fa, st_fa = drv.render(cam, cfg, rows, chunk_cull=False)
                 assert (img_fn == img_f).all() and (img_fa == img_f).all() and st_fa["d_total"] == st_f["d_total"], f"{what}: fine tiles: a switch changed the frame"
             worst = max(worst, assert_frame_close(img_f[ya:yb], ref[ya:yb], aux["margin"][ya:yb], aux["recheck"], what=what + " [fine tiles]", y0=ya))
+            assert_frame_tight(img_f[ya:yb], ref[ya:yb], aux, y0=ya, what=what + " [fine tiles]")
         else:
             assert (img_f == img).all(), f"{what}: SGS_FLAG_NO_FINE_TILES changed a frame that is not rendered through fine tiles"
     # ... and what the library does with this frame when nobody tells it: one of the tilings above (or the one between them), its own decision
@@ -170,6 +173,7 @@ def check_against_oracle(drv, scene, cam, cfg=None, rows=(0, -1), what="", queue
     else:
         assert st["n_tiles"] < st_d["n_tiles"] < st_f["n_tiles"] and st_d["n_visible"] == aux["n_visible"]
         worst = max(worst, assert_frame_close(img_d[ya:yb], ref[ya:yb], aux["margin"][ya:yb], aux["recheck"], what=what + " [8x8-pixel tiles]", y0=ya))
+        assert_frame_tight(img_d[ya:yb], ref[ya:yb], aux, y0=ya, what=what + " [8x8-pixel tiles]")
     return img, st, aux, worst
 
 
@@ -259,6 +263,7 @@ def case_fuzz(drv, seeds, max_n=700, max_res=(260, 160), wild=False, thorough_ev
             if safe.any():
                 assert np.abs(aux[..., 0] - o["depth_image"])[safe].max() < 1e-3 * zmax, f"fuzz seed {seed}: depth"
                 assert np.abs(aux[..., 1] - (1.0 - o["final_T"]))[safe].max() < 1e-3, f"fuzz seed {seed}: coverage"
+            assert_depth_coverage_tight(aux, o, what=f"fuzz seed {seed} aux")
 
 
 def case_non_finite_gaussians(drv, n=3000, res=(160, 120), seed=3):
@@ -407,6 +412,7 @@ def case_tile_rows(drv, n=2500, res=(208, 150)):
                 _, st_ref = drv.render(cam, None, (r0, r1), loose_cull=True)      # reference binning: the oracle's D
                 assert st_ref["d_total"] == aux["D"] and st["n_visible"] == aux["n_visible"] and (fine or st["d_total"] <= aux["D"])
                 assert_frame_close(img[y0:y1], ref[y0:y1], aux["margin"][y0:y1], aux["recheck"], what=f"tile rows [{r0}, {r1}) fine={fine}", y0=y0)
+                assert_frame_tight(img[y0:y1], ref[y0:y1], aux, y0=y0, what=f"tile rows [{r0}, {r1}) fine={fine}")
                 union[y0:y1] = img[y0:y1]
                 d_sum += st["d_total"]
             assert (union == full).all(), f"union of tile-row bands != full frame (fine {fine})"
@@ -575,6 +581,7 @@ def case_depth_aux(drv, n=1500, res=(96, 80)):
     assert np.abs(aux[..., 0] - o["depth_image"])[safe].max() < 1e-3 * zmax
     assert np.abs(aux[..., 1] - (1.0 - o["final_T"]))[safe].max() < 1e-3
     assert np.abs(aux[..., 0] - o["depth_image"]).max() < zmax / 255.0 + 1e-3 * zmax
+    assert_depth_coverage_tight(aux, o, what="depth aux")
 
 
 def case_determinism(drv, n=4000):

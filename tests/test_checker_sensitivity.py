@@ -1,0 +1,127 @@
+"""The parity checks must see a kernel that is slightly wrong (CPU, wave64 emulator).
+
+Each mutant is csrc/ with one small textual change — a kernel that is wrong by a few 1e-4 per pixel, or in a few pixels only — built as an
+emulator library of its own (never for gfx950).  Its cases run through parity_cases.check_against_oracle twice: with the flat 1e-3 checks
+alone, which must PASS (the gap tight_parity.py closes: otherwise the mutant proves nothing), and with tight_parity's budget, which must
+FAIL with a [tight] assertion — not with a crash, not with another check.  The anchor of every patch must be found exactly once, so that a
+refactor of the kernels cannot make a mutant vanish silently.
+"""
+import os
+import shutil
+
+import numpy as np
+import pytest
+
+import conftest
+import emu_harness
+import oracle_np as onp
+import parity_cases as pc
+
+R11 = "#define SGS_MUT_R11(x) ((x) * 8193.0f - ((x) * 8193.0f - (x)))   /* x rounded to an 11-bit significand: fp16 precision */\n"
+
+# mutant -> [(anchor in sgs_kernels.h, replacement)]
+MUTANTS = {
+    # SGS_STAGE: the splat's colour staged at fp16 precision
+    "stage_rgb_fp16": [("s_p3[J] = make_float2(B_.z, B_.w);", "s_p3[J] = make_float2(SGS_MUT_R11(B_.z), SGS_MUT_R11(B_.w));"),
+                       ("s_p4[J] = make_float2(C_.x, C_.y);", "s_p4[J] = make_float2(SGS_MUT_R11(C_.x), C_.y);")],
+    # SGS_APPLY: the depth added to the AUX output's expected depth at fp16 precision
+    "aux_depth_fp16": [("if (AUX) Dz = __builtin_fmaf(wgt, (N##4).y, Dz);", "if (AUX) Dz = __builtin_fmaf(wgt, SGS_MUT_R11((N##4).y), Dz);")],
+    # SGS_ALPHA_F: every alpha 2^-13 too large
+    "alpha_x(1+2^-13)": [("AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big));",
+                          "AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big)) * (1.0f + 0x1p-13f);")],
+    # fine tiles only: the splat's centre 2^-10 px off along x when the frame is rendered through 8x8 / 4x4-pixel tiles
+    "fine_centre_2^-10px": [("sp[0] = make_float4(sx * up, sy * up,", "sp[0] = make_float4((sx + (zf > 0 ? 0x1p-10f : 0.0f)) * up, sy * up,")],
+    # termination: the stop rule T (1 - alpha) < t_min at 1.05 t_min
+    "t_min_x1.05": [("nt_big = -(P.alpha_max * P.t_min) * SGS_BIG;", "nt_big = -(P.alpha_max * (P.t_min * 1.05f)) * SGS_BIG;")],
+    # background: the final transmittance rounded to fp16 precision before T * bg
+    "bg_T_fp16": [("o[0] = C0 + Tf * P.bg[0]; o[1] = C1 + Tf * P.bg[1]; o[2] = C2 + Tf * P.bg[2];",
+                   "o[0] = C0 + SGS_MUT_R11(Tf) * P.bg[0]; o[1] = C1 + SGS_MUT_R11(Tf) * P.bg[1]; o[2] = C2 + SGS_MUT_R11(Tf) * P.bg[2];")],
+}
+
+
+def _fuzz(seeds):
+    return lambda drv: pc.case_fuzz(drv, seeds, thorough_every=1 << 30)
+
+
+def _config1(drv, n=3000):
+    scene, cam = onp.config1_scene(n=n, seed=0)          # 128x128, dense enough that pixels stop (T (1 - alpha) < t_min)
+    pc.check_against_oracle(drv, scene, cam, what=f"config1 n={n}", thorough=False)
+
+
+# mutant -> its cases (small frames; thorough=False: the switches that only hold one render against another are left to the main suite)
+CASES = {
+    "stage_rgb_fp16": _fuzz([1]),
+    "aux_depth_fp16": lambda drv: pc.case_depth_aux(drv, n=600, res=(64, 48)),
+    "alpha_x(1+2^-13)": _config1,
+    "fine_centre_2^-10px": _fuzz([1]),
+    "t_min_x1.05": _config1,
+    "bg_T_fp16": _fuzz([1]),
+}
+
+
+def _patch(src_dir, edits):
+    path = os.path.join(src_dir, "sgs_kernels.h")
+    s = open(path).read()
+    anchor = '#include "sgs_common.h"\n'
+    assert s.count(anchor) == 1
+    s = s.replace(anchor, anchor + R11)
+    for old, new in edits:
+        assert s.count(old) == 1, f"mutant anchor found {s.count(old)} times (expected once): {old!r}"
+        s = s.replace(old, new)
+    open(path, "w").write(s)
+
+
+@pytest.fixture(scope="module")
+def mutant_libs(tmp_path_factory):
+    """Every mutant's emulator library, compiled side by side (one g++ each)."""
+    root = tmp_path_factory.mktemp("mutants")
+    procs, libs = {}, {}
+    for k, (name, edits) in enumerate(MUTANTS.items()):
+        base = root / f"m{k}"
+        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
+        os.makedirs(base / "include")
+        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
+        _patch(str(base / "pkg" / "csrc"), edits)
+        libs[name] = str(base / "libsage_gs_mutant.so")
+        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
+    for name, p in procs.items():
+        assert p.wait() == 0, f"{name}: the mutant does not compile"
+    return libs
+
+
+def _run(lib_path, case, tight, monkeypatch):
+    """Run `case` on the mutant; tight=False: the tight_parity checks are switched off (today's suite).  Returns the worst |d| the
+    flat checks saw (conftest.PARITY_LOG) and the worst depth / coverage |d| of the AUX renders."""
+    seen = {"aux": 0.0}
+    if not tight:
+        def no_tight(*a, **k):
+            return 0.0
+
+        def aux_seen(out_aux, o, what=""):
+            safe = o["margin"] >= conftest.MARGIN
+            d = np.abs(out_aux[..., 0] - o["depth_image"]) / max(1.0, float(o["depth_image"].max()))
+            c = np.abs(out_aux[..., 1] - (1.0 - o["final_T"]))
+            seen["aux"] = max(seen["aux"], float(d[safe].max(initial=0.0)), float(c[safe].max(initial=0.0)))
+            return 0.0
+        monkeypatch.setattr(pc, "assert_frame_tight", no_tight)
+        monkeypatch.setattr(pc, "assert_depth_coverage_tight", aux_seen)
+    n0 = len(conftest.PARITY_LOG)
+    drv = emu_harness.EmuRenderer(record_capacity=1 << 20, lib_path=lib_path)
+    try:
+        case(drv)
+    finally:
+        drv.close()
+        monkeypatch.undo()
+        rows = conftest.PARITY_LOG[n0:]
+        del conftest.PARITY_LOG[n0:]                  # (a mutant's frames stay out of the suite's parity ledger)
+    return max([r[3] for r in rows] + [r[4] for r in rows] + [0.0]), seen["aux"]
+
+
+@pytest.mark.parametrize("name", list(MUTANTS))
+def test_mutant_passes_the_flat_check_and_fails_the_budget(mutant_libs, name, monkeypatch):
+    worst, worst_aux = _run(mutant_libs[name], CASES[name], False, monkeypatch)
+    print(f"[mutant] {name}: passes the 1e-3 checks, worst |d| {worst:.2e} (depth / zmax, coverage {worst_aux:.2e})")
+    with pytest.raises(AssertionError) as e:
+        _run(mutant_libs[name], CASES[name], True, monkeypatch)
+    assert str(e.value).startswith("[tight]"), f"{name}: failed, but not on the tight budget: {e.value}"
+    print(f"[mutant] {name}: caught: {str(e.value)[:160]}")

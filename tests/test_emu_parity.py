@@ -131,6 +131,7 @@ def test_against_committed_golden_fixture(drv):
     """The kernels (under the emulator) against tests/golden/config1_golden.npz — no oracle run involved."""
     import os
     from conftest import assert_frame_close, stored_variants
+    from tight_parity import assert_frame_tight
     g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config1_golden.npz"))
     scene, _ = onp.config1_scene(n=int(g["n"]), seed=int(g["seed"]))
     cam = onp.Camera(int(g["width"]), int(g["height"]), float(g["f"]), float(g["f"]), 64.0, 64.0, np.eye(4, dtype=np.float32))
@@ -142,10 +143,13 @@ def test_against_committed_golden_fixture(drv):
     assert st["d_total"] == int(g["D"]) and st["n_visible"] == int(g["n_visible"]) and st["d_fetched"] == int(g["D_f"])
     assert (off == g["offsets"]).all() and (ids == g["ids"]).all()
     assert_frame_close(img, g["image"], g["margin"], stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]), what="golden config1")
+    gaux = dict(n_contrib=g["n_contrib"], margin=g["margin"], recheck=stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]))
+    assert_frame_tight(img, g["image"], gaux, what="golden config1")
     with pc.forced_fine(drv):
         fine, st_fine = drv.render(cam)                               # ... and through fine tiles
     assert st_fine["n_tiles"] > st_prod["n_tiles"] and st_fine["n_visible"] == int(g["n_visible"])
     assert_frame_close(fine, g["image"], g["margin"], stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]), what="golden config1 [fine tiles]")
+    assert_frame_tight(fine, g["image"], gaux, what="golden config1 [fine tiles]")
 
 
 def test_pipelined_frames_and_batch_rotate_over_lanes(drv):

@@ -11,6 +11,7 @@ import oracle_np as onp
 import parity_cases as pc
 import fuzz_cases
 from conftest import assert_frame_close
+from tight_parity import assert_frame_tight
 from test_gpu_parity import GpuDriver, BANDS_4K_8, _ocam
 
 
@@ -135,6 +136,7 @@ def test_4k_batch_of_consecutive_poses(room4k):
     ref, aux = oracle_c.render(*sc.as_tuple(), ocams[k], want="image")
     assert (img_ref == img).all() and st[k]["n_visible"] == aux["n_visible"] and st_ref["d_total"] == aux["D"] and st[k]["d_total"] <= aux["D"]
     assert_frame_close(img, ref, aux["margin"], aux["recheck"], what="3M @ 3840x2160 sweep pose 85 (image + counts)")
+    assert_frame_tight(img, ref, aux, what="3M @ 3840x2160 sweep pose 85 (image + counts)")
     aux["recheck"].close()
     print(f"[batch] 3M @4K poses 78-93: 16 frames bit-equal to the frames alone (D {min(s['d_total'] for s in st)}-{max(s['d_total'] for s in st)})")
 
@@ -299,4 +301,5 @@ def test_big_splat_list_overflow():
         ref, aux = oracle_c.render(*scene, ocam, None, r0, r1, want="image")
         sl = slice(16 * r0, 16 * r1)
         assert_frame_close(full[sl], ref[sl], aux["margin"][sl], aux["recheck"], what=f"big-splat list overflow, tile rows {r0}-{r1}", y0=sl.start)
+        assert_frame_tight(full[sl], ref[sl], aux, y0=sl.start, what=f"big-splat list overflow, tile rows {r0}-{r1}")
         aux["recheck"].close()

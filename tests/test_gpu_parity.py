@@ -12,6 +12,7 @@ import oracle_c
 import oracle_np as onp
 import parity_cases as pc
 from conftest import assert_frame_close, stored_variants
+from tight_parity import assert_frame_tight
 
 
 class GpuDriver:
@@ -413,6 +414,7 @@ def test_3m_scene_4k_config5_geometry(drv, big_scene):
     assert (img_ref == img).all() and st_bref["d_total"] == aux["D"] and st_b["n_visible"] == aux["n_visible"]
     sl = slice(r0 * 16, r1 * 16)
     assert_frame_close(img[sl], ref[sl], aux["margin"][sl], aux["recheck"], what="3M @ 4K band", y0=sl.start)
+    assert_frame_tight(img[sl], ref[sl], aux, y0=sl.start, what="3M @ 4K band")
 
 
 # ---- BASELINE.json full sizes: FULL frames against the oracle ----------------------------------------------------------
@@ -458,6 +460,7 @@ def test_3m_scene_more_bench_poses_images_and_counts_vs_oracle(drv, big_scene):
         ref, aux = oracle_c.render(*sc.as_tuple(), ocam, want="image")
         assert (img_ref == img).all() and st["n_visible"] == aux["n_visible"] and st_ref["d_total"] == aux["D"] and st["d_total"] <= aux["D"]
         assert_frame_close(img, ref, aux["margin"], aux["recheck"], what=f"3M @1080p bench pose {pid} (image + counts)")
+        assert_frame_tight(img, ref, aux, what=f"3M @1080p bench pose {pid} (image + counts)")
         aux["recheck"].close()
 
 
@@ -544,6 +547,7 @@ def test_4k_frame_multi_window_binning(drv):
     assert st_bref["d_total"] == aux["D"] and st_b["n_visible"] == aux["n_visible"]
     sl = slice(r0 * 16, r1 * 16)
     assert_frame_close(img[sl], ref[sl], aux["margin"][sl], aux["recheck"], what="4K band", y0=sl.start)
+    assert_frame_tight(img[sl], ref[sl], aux, y0=sl.start, what="4K band")
 
 
 def test_culling_never_changes_a_pixel_stress(drv):
@@ -608,6 +612,7 @@ def test_culling_never_changes_a_pixel_stress(drv):
         o_ref, aux = oracle_c.render(f32(means), f32(s), f32(quats), f32(opac), f32(sh), 3, ocam)
         assert st_f["n_visible"] == aux["n_visible"]
         assert_frame_close(fine, o_ref, aux["margin"], aux["recheck"], what=f"adversarial splats, yaw {yaw} [fine tiles]")
+        assert_frame_tight(fine, o_ref, aux, what=f"adversarial splats, yaw {yaw} [fine tiles]")
         aux["recheck"].close()
     scene.free()
 
@@ -634,10 +639,13 @@ def test_against_committed_golden_fixture(drv):
     assert st["d_total"] == int(g["D"]) and st["n_visible"] == int(g["n_visible"]) and st["d_fetched"] == int(g["D_f"])
     assert (off == g["offsets"]).all() and (ids == g["ids"]).all()
     assert_frame_close(img, g["image"], g["margin"], stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]), what="golden config1")
+    gaux = dict(n_contrib=g["n_contrib"], margin=g["margin"], recheck=stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]))
+    assert_frame_tight(img, g["image"], gaux, what="golden config1")
     with pc.forced_fine(drv):
         fine, st_fine = drv.render(cam)                               # ... and through fine tiles
     assert st_fine["n_tiles"] > st_prod["n_tiles"] and st_fine["n_visible"] == int(g["n_visible"])
     assert_frame_close(fine, g["image"], g["margin"], stored_variants(g["flag_yx"], g["flag_ptr"], g["flag_rgb"]), what="golden config1 [fine tiles]")
+    assert_frame_tight(fine, g["image"], gaux, what="golden config1 [fine tiles]")
 
 
 def test_batch_equals_single_frames(drv):
@@ -720,6 +728,7 @@ def test_render_function_surface():
     ocam = onp.Camera(256, 256, 128.0, 128.0, 128.0, 128.0, np.eye(4, dtype=np.float32))
     ref, aux = oracle_c.render(*sc.as_tuple(), ocam)
     assert_frame_close(img.cpu().numpy(), ref, aux["margin"], aux["recheck"], what="render()")
+    assert_frame_tight(img.cpu().numpy(), ref, aux, what="render()")
 
 
 # ---- "next" rows on the GPU ------------------------------------------------------------
@@ -761,6 +770,7 @@ def test_ply_scene_against_the_oracle(drv, tmp_path):
         img = drv.r.render(cam, g).cpu().numpy()
         ref, aux = oracle_c.render(*arrays, _oracle_view(sc, cam), want="image")
         assert_frame_close(img, ref, aux["margin"], aux["recheck"], what=f"3DGS .ply scene, camera {k}")
+        assert_frame_tight(img, ref, aux, what=f"3DGS .ply scene, camera {k}")
         aux["recheck"].close()
         assert img.max() > 0.2
 
@@ -799,6 +809,7 @@ def test_compressed_ply_scene_against_the_oracle(drv, tmp_path, deg):
         view = _oracle_view(sc, cam)
         ref, aux = oracle_c.render(*held, view, want="image")
         assert_frame_close(img, ref, aux["margin"], aux["recheck"], what=f"compressed .ply scene (degree {deg}), camera {k}")
+        assert_frame_tight(img, ref, aux, what=f"compressed .ply scene (degree {deg}), camera {k}")
         aux["recheck"].close()
         orig, _ = oracle_c.render(m, s_, q, o, sh, deg, view, want="image")
         d0 = np.abs(img.astype(np.float64) - orig)
