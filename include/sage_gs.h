@@ -305,6 +305,44 @@ enum {
 };
 int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes);
 
+/* ---- Collision-mesh depth — replaces SimpleVLNEnv.get_depth() (simple_env.py:1395-1589): the reference makes /World/scene_collision
+ * visible, renders Isaac Sim's `distance_to_image_plane` of the COLLISION MESH and clips it to [0.1, 6.5] m.  The mesh is the payload
+ * `{scene_id}_collision.usd` of the template's scene_collision prim (Data/template.usda:156-165).  Synchronous only; no new struct.
+ *
+ *   Rays     pixel (x, y) is sampled along r = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1) in camera space — the pixel centres the splat
+ *            path uses (it projects a point to fx x / z + cx - 0.5 and samples pixel i at coordinate i).
+ *   Output   out_depth[y * W + x] = the camera-space z of the NEAREST hit on any triangle among hits with near_z < z <= far_z (cfg, or
+ *            sgs_config_default's 0.2 / 1e30), both faces counting (collision meshes are not reliably wound); +inf where nothing is hit.
+ *            This is `distance_to_image_plane` (z along the optical axis), not the distance along the ray.  A DEVICE buffer of H*W floats.
+ *   Camera   sgs_camera.view maps MESH MODEL space to camera space and must be rigid (as for sgs_render; a model scale is baked into the
+ *            vertices by the caller — sage_gs.Renderer.upload_mesh does).  All cameras of one call share one resolution.
+ *   Refused  with SGS_ERR_INVALID: cfg->tile_row_stride > 1, SGS_FLAG_ASYNC / SGS_FLAG_PIPELINED, a non-rigid view; at upload, triangle
+ *            indices outside [0, n_vertices) and non-finite vertices — checked ON THE DEVICE through a status word (the arrays may be
+ *            device pointers, on_device != 0), so the upload synchronises once.
+ *   Records  the mesh path owns its record buffer: 4 bytes per (triangle, 16x16-pixel tile) record, 4 Mi records (16 MiB) to start
+ *            with (sgs_mesh_set_record_capacity); a frame that needs more grows it and is rendered again (sgs_stats.retries).  Besides it,
+ *            per (triangle, frame of a group of up to 8 frames) 72 bytes of setup records + 4 bytes, and 8 bytes per tile and frame.
+ *   stats    nullable (n_cams entries for the batch): n_visible (triangles that survive culling and reach a tile of the band), d_total
+ *            (records), n_tiles, max_tile_len, n_pixels, retries, and ms_total under SGS_FLAG_TIMING (a batch: its group's time / frames
+ *            in the group); every other field is 0.
+ *   Exact    the value of a pixel is a minimum over the triangles listed for its tile, so it does not depend on the order of the records:
+ *            every frame is bit-identical whether rendered alone or in a batch, as a band of tile rows or as the full frame, and under
+ *            any permutation of the triangles.  Watertight: two triangles that share an edge (the same two vertex indices) leave no pixel
+ *            between them (sage-3d_official_amd/csrc/sgs_mesh.h says how). */
+typedef struct sgs_mesh sgs_mesh;      /* opaque */
+/* vertices float[V][3], triangles int32[F][3] (host pointers, or device pointers on the context's device when on_device != 0): copied. */
+int sgs_mesh_upload(sgs_ctx* ctx, int64_t n_vertices, const float* vertices, int64_t n_triangles, const int32_t* triangles,
+                    int on_device, sgs_mesh** out);
+int sgs_mesh_free(sgs_ctx* ctx, sgs_mesh* mesh);
+/* Record buffer of the mesh path, in records (1 .. 2^32 - 16): takes effect at the next mesh frame. */
+int sgs_mesh_set_record_capacity(sgs_ctx* ctx, int64_t max_records);
+/* One frame: the tile rows [tile_row_begin, tile_row_end) (end < 0: all) of out_depth (H*W floats); other rows are left untouched. */
+int sgs_render_mesh_depth(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cam, const sgs_config* cfg,
+                          int tile_row_begin, int tile_row_end, float* out_depth, sgs_stats* stats, void* hip_stream);
+/* n_cams whole frames, out_depth[B][H][W]; issued in groups of up to 8 frames per set of launches. */
+int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams,
+                                const sgs_config* cfg, float* out_depth, sgs_stats* stats, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 
 #include "../../include/sage_gs.h"
 #include "sgs_kernels.h"
+#include "sgs_mesh.h"
 
 namespace {
 
@@ -94,8 +95,31 @@ struct Lane {
 constexpr int kMaxLanes = 16;
 constexpr int64_t kMaxRecords = 0xfffffff0ll;   // record capacity: tile offsets are 32-bit
 
+// The collision-mesh depth path's own scratch (sgs_render_mesh_depth*): nothing of it is shared with the splat path's lanes.
+struct MeshScratch {
+    int64_t slot_cap = 0;                    // (triangle, frame) slots of the setup records
+    float4* rec = nullptr;
+    uint2* rect = nullptr;
+    unsigned* big = nullptr;
+    int64_t tile_cap = 0;                    // per-tile counters / offsets of a group
+    unsigned *counts = nullptr, *offs = nullptr;
+    int64_t list_cap = 0;                    // the record buffer: triangle ids of the per-tile lists
+    unsigned* list = nullptr;
+    int64_t cap_wanted = 4ll << 20;          // sgs_mesh_set_record_capacity (4 Mi records, 16 MiB)
+    sgs::MeshStatus* d_st = nullptr;         // [SGS_MESH_MAX_GROUP] + the upload check's word
+    sgs::MeshStatus* h_st = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+struct sgs_mesh {
+    int64_t n_verts = 0, n_tris = 0;
+    float* verts = nullptr;
+    int* tris = nullptr;
+};
+
 struct sgs_ctx {
     int device = 0;
+    MeshScratch mesh;
     std::string err;
     Lane lanes[kMaxLanes];
     int n_lanes = 3, next_lane = 0;          // sgs_tuning.lanes: lanes that SGS_FLAG_PIPELINED single frames rotate over
@@ -726,6 +750,13 @@ int sgs_destroy(sgs_ctx* ctx) {
         if (L.stream) (void)hipStreamDestroy(L.stream);
         if (L.fork) (void)hipEventDestroy(L.fork);
         if (L.done) (void)hipEventDestroy(L.done);
+    }
+    {
+        MeshScratch& M = ctx->mesh;
+        void* bufs[] = {M.rec, M.rect, M.big, M.counts, M.offs, M.list, M.d_st};
+        for (void* b : bufs) if (b) (void)hipFree(b);
+        if (M.h_st) (void)hipHostFree(M.h_st);
+        for (hipEvent_t e : M.ev) if (e) (void)hipEventDestroy(e);
     }
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->row_acc) (void)hipFree(ctx->row_acc);
@@ -1400,6 +1431,237 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
         free(vm);
     }
     return have;
+}
+
+// ---- collision-mesh depth (include/sage_gs.h "Collision-mesh depth"; kernels in sgs_mesh.h) ------------------------------------------
+
+int sgs_mesh_upload(sgs_ctx* ctx, int64_t n_vertices, const float* vertices, int64_t n_triangles, const int32_t* triangles,
+                    int on_device, sgs_mesh** out) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n_vertices < 0 || n_vertices > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "n_vertices = %lld out of range", (long long)n_vertices);
+    if (n_triangles < 0 || n_triangles > (1ll << 28)) SGS_FAIL(ctx, SGS_ERR_INVALID, "n_triangles = %lld out of range [0, 2^28]", (long long)n_triangles);
+    if ((n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles)) SGS_FAIL(ctx, SGS_ERR_INVALID, "null input array");
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    MeshScratch& M = ctx->mesh;
+    if (!M.d_st) {
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1)));
+        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&M.h_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1), 0));
+    }
+    sgs_mesh* m = new (std::nothrow) sgs_mesh;
+    if (!m) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
+    m->n_verts = n_vertices; m->n_tris = n_triangles;
+    const size_t vb = (size_t)n_vertices * 12, tb = (size_t)n_triangles * 12;
+    hipError_t e = hipSuccess;
+    if ((e = hipMalloc(reinterpret_cast<void**>(&m->verts), vb ? vb : 16)) != hipSuccess ||
+        (e = hipMalloc(reinterpret_cast<void**>(&m->tris), tb ? tb : 16)) != hipSuccess ||
+        (vb && (e = hipMemcpy(m->verts, vertices, vb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess) ||
+        (tb && (e = hipMemcpy(m->tris, triangles, tb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess)) {
+        sgs_mesh_free(ctx, m);
+        SGS_FAIL(ctx, e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "mesh upload: %s", hipGetErrorString(e));
+    }
+    // the checks run on the device (the caller's arrays may live there): a status word, read back once
+    unsigned* bad = &M.d_st[SGS_MESH_MAX_GROUP].n_visible;
+    SGS_HIP(ctx, hipMemset(bad, 0, sizeof(unsigned)));
+    const long long work = 3 * std::max<long long>(n_vertices, n_triangles);
+    if (work > 0)
+        hipLaunchKernelGGL(sgs::k_mesh_validate, dim3((unsigned)std::min<long long>((work + 255) / 256, 4096)), dim3(256), 0, nullptr,
+                           (long long)n_vertices, (const float*)m->verts, (long long)n_triangles, (const int*)m->tris, bad);
+    unsigned flags = 0;
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost)) != hipSuccess) {
+        sgs_mesh_free(ctx, m);
+        SGS_FAIL(ctx, SGS_ERR_HIP, "mesh upload: %s", hipGetErrorString(e));
+    }
+    if (flags) {
+        sgs_mesh_free(ctx, m);
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh upload: %s%s", (flags & 1u) ? "non-finite vertex coordinates " : "",
+                 (flags & 2u) ? "triangle indices outside [0, n_vertices)" : "");
+    }
+    *out = m;
+    return SGS_OK;
+}
+
+int sgs_mesh_free(sgs_ctx* ctx, sgs_mesh* mesh) {
+    if (!mesh) return SGS_OK;
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipDeviceSynchronize(); }
+    if (mesh->verts) (void)hipFree(mesh->verts);
+    if (mesh->tris) (void)hipFree(mesh->tris);
+    delete mesh;
+    return SGS_OK;
+}
+
+int sgs_mesh_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (max_records < 1 || max_records > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh record capacity %lld outside [1, 2^32)", (long long)max_records);
+    MeshScratch& M = ctx->mesh;
+    M.cap_wanted = max_records;
+    if (M.list && M.list_cap != max_records) {               // reallocated at the requested size by the next mesh frame
+        SGS_HIP(ctx, hipSetDevice(ctx->device));
+        SGS_HIP(ctx, hipDeviceSynchronize());
+        (void)hipFree(M.list);
+        M.list = nullptr; M.list_cap = 0;
+    }
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+template <class T>
+int mesh_grow(sgs_ctx* ctx, T*& p, int64_t& cap, int64_t want, int64_t count_per) {
+    if (want <= cap && p) return SGS_OK;
+    const int64_t c = std::max<int64_t>(want, 1);
+    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), (size_t)c * (size_t)count_per * sizeof(T)));
+    cap = c;
+    return SGS_OK;
+}
+
+// Frames [0, n) of cams: groups of up to SGS_MESH_MAX_GROUP frames, each five launches and one synchronisation; frame i is written at
+// out + i * frame_stride.  stats: n entries (nullable).
+int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n, const sgs_config* cfg_in, int row_begin, int row_end,
+                float* out, int64_t frame_stride, sgs_stats* stats, void* hip_stream) {
+    if (!mesh || !cams || !out) SGS_FAIL(ctx, SGS_ERR_INVALID, "null mesh / camera / output");
+    if (n < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "n_cams = %d", n);
+    sgs_config cfg;
+    if (cfg_in) cfg = *cfg_in; else sgs_config_default(&cfg);
+    if (cfg.tile_row_stride > 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh depth: interleaved tile rows (tile_row_stride %d) are not supported", cfg.tile_row_stride);
+    if (cfg.flags & (SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED)) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh depth is synchronous only: SGS_FLAG_ASYNC / SGS_FLAG_PIPELINED are refused");
+    if (!(cfg.near_z > 0.f) || !(cfg.far_z > cfg.near_z)) SGS_FAIL(ctx, SGS_ERR_INVALID, "need 0 < near_z < far_z (got %g, %g)", cfg.near_z, cfg.far_z);
+    const int W = cams[0].width, H = cams[0].height;
+    if (W <= 0 || H <= 0 || W > 65535 * SGS_TILE || H > 65535 * SGS_TILE) SGS_FAIL(ctx, SGS_ERR_INVALID, "bad resolution %dx%d", W, H);
+    for (int i = 0; i < n; ++i) {
+        const sgs_camera* c = &cams[i];
+        if (c->width != W || c->height != H) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: %dx%d, camera 0: %dx%d (one resolution per call)", i, c->width, c->height, W, H);
+        if (!(c->fx > 0.f) || !(c->fy > 0.f)) SGS_FAIL(ctx, SGS_ERR_INVALID, "focal lengths must be positive");
+        if (!std::isfinite(c->cx) || !std::isfinite(c->cy)) SGS_FAIL(ctx, SGS_ERR_INVALID, "principal point must be finite");
+        const float* V = c->view;
+        for (int k = 0; k < 12; ++k)
+            if (!std::isfinite(V[k])) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: non-finite view", i);
+        for (int r = 0; r < 3; ++r)
+            for (int q = r; q < 3; ++q) {
+                const double d = (double)V[4 * r] * V[4 * q] + (double)V[4 * r + 1] * V[4 * q + 1] + (double)V[4 * r + 2] * V[4 * q + 2];
+                if (!(std::fabs(d - (r == q ? 1.0 : 0.0)) < 1.0e-5))
+                    SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: view is not rigid: rows %d.%d of its 3x3 give %g", i, r, q, d);
+            }
+    }
+    const int gy = (H + SGS_TILE - 1) / SGS_TILE, gx = (W + SGS_TILE - 1) / SGS_TILE;
+    if (row_end < 0 || row_end > gy) row_end = gy;
+    if (row_begin < 0) row_begin = 0;
+    if (row_begin > row_end) SGS_FAIL(ctx, SGS_ERR_INVALID, "tile_row_begin %d > tile_row_end %d", row_begin, row_end);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    MeshScratch& M = ctx->mesh;
+    if (!M.d_st) {
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1)));
+        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&M.h_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1), 0));
+    }
+    const bool timed = (cfg.flags & SGS_FLAG_TIMING) != 0;
+    if (timed && !M.ev[0]) { SGS_HIP(ctx, hipEventCreate(&M.ev[0])); SGS_HIP(ctx, hipEventCreate(&M.ev[1])); }
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const int n_tiles = (row_end - row_begin) * gx;
+    const int64_t F = mesh->n_tris;
+    for (int g0 = 0; g0 < n; g0 += SGS_MESH_MAX_GROUP) {
+        const int nf = std::min(SGS_MESH_MAX_GROUP, n - g0);
+        int64_t dummy = 0;
+        int rc;
+        if (M.slot_cap < F * nf || !M.rec) {
+            if ((rc = mesh_grow(ctx, M.rec, dummy, F * nf, 4)) != SGS_OK) return rc;
+            dummy = 0;
+            if ((rc = mesh_grow(ctx, M.rect, dummy, F * nf, 1)) != SGS_OK) return rc;
+            dummy = 0;
+            if ((rc = mesh_grow(ctx, M.big, dummy, F * nf, 1)) != SGS_OK) return rc;
+            M.slot_cap = std::max<int64_t>(F * nf, 1);
+        }
+        if (M.tile_cap < (int64_t)n_tiles * nf + nf || !M.counts) {
+            dummy = 0;
+            if ((rc = mesh_grow(ctx, M.counts, dummy, (int64_t)n_tiles * nf + nf, 1)) != SGS_OK) return rc;
+            dummy = 0;
+            if ((rc = mesh_grow(ctx, M.offs, dummy, (int64_t)n_tiles * nf + nf, 1)) != SGS_OK) return rc;
+            M.tile_cap = (int64_t)n_tiles * nf + nf;
+        }
+        int retries = 0;
+        for (;;) {
+            if (M.list_cap < M.cap_wanted || !M.list) {
+                if (M.list) { (void)hipFree(M.list); M.list = nullptr; M.list_cap = 0; }
+                SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.list), (size_t)M.cap_wanted * sizeof(unsigned)));
+                M.list_cap = M.cap_wanted;
+            }
+            sgs::MeshGroup G;
+            memset(&G, 0, sizeof G);
+            for (int f = 0; f < nf; ++f) {
+                const sgs_camera& c = cams[g0 + f];
+                sgs::MeshFrame& P = G.f[f];
+                for (int k = 0; k < 12; ++k) P.view[k] = c.view[k];
+                P.fx = c.fx; P.fy = c.fy; P.cx = c.cx; P.cy = c.cy; P.near_z = cfg.near_z; P.far_z = cfg.far_z;
+                P.width = W; P.height = H; P.gx = gx; P.row_begin = row_begin; P.row_end = row_end;
+                P.out = out + (int64_t)(g0 + f) * frame_stride;
+            }
+            G.nf = nf; G.n_tiles = n_tiles; G.n_tris = F; G.cap = M.list_cap;
+            G.verts = mesh->verts; G.tris = mesh->tris;
+            G.rec = M.rec; G.rect = M.rect; G.big = M.big; G.counts = M.counts; G.offs = M.offs; G.list = M.list; G.st = M.d_st;
+            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[0], stream));
+            SGS_HIP(ctx, hipMemsetAsync(M.d_st, 0, sizeof(sgs::MeshStatus) * nf, stream));
+            if (n_tiles > 0) {
+                SGS_HIP(ctx, hipMemsetAsync(M.counts, 0, sizeof(unsigned) * (size_t)n_tiles * nf, stream));
+                if (F > 0) {
+                    hipLaunchKernelGGL(sgs::k_mesh_setup, dim3((unsigned)((F + 255) / 256), (unsigned)nf), dim3(256), 0, stream, G);
+                    const unsigned bin_grid = (unsigned)std::min<int64_t>((F + 255) / 256, SGS_MESH_BIN_BLOCKS);
+                    hipLaunchKernelGGL(sgs::k_mesh_bin<false>, dim3(bin_grid, (unsigned)nf), dim3(256), 0, stream, G);
+                    hipLaunchKernelGGL(sgs::k_mesh_scan, dim3(1, (unsigned)nf), dim3(SGS_MESH_SCAN_THREADS), 0, stream, G);
+                    hipLaunchKernelGGL(sgs::k_mesh_bin<true>, dim3(bin_grid, (unsigned)nf), dim3(256), 0, stream, G);
+                } else {
+                    hipLaunchKernelGGL(sgs::k_mesh_scan, dim3(1, (unsigned)nf), dim3(SGS_MESH_SCAN_THREADS), 0, stream, G);
+                }
+                hipLaunchKernelGGL(sgs::k_mesh_depth, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
+            }
+            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[1], stream));
+            SGS_HIP(ctx, hipGetLastError());
+            SGS_HIP(ctx, hipMemcpyAsync(M.h_st, M.d_st, sizeof(sgs::MeshStatus) * nf, hipMemcpyDeviceToHost, stream));
+            SGS_HIP(ctx, hipStreamSynchronize(stream));
+            int64_t total = 0;
+            for (int f = 0; f < nf; ++f) total += M.h_st[f].d_total;
+            if (total <= M.list_cap) {
+                float ms = 0.f;
+                if (timed) SGS_HIP(ctx, hipEventElapsedTime(&ms, M.ev[0], M.ev[1]));
+                for (int f = 0; f < nf && stats; ++f) {
+                    sgs_stats& s = stats[g0 + f];
+                    memset(&s, 0, sizeof s);
+                    s.n_visible = M.h_st[f].n_visible;
+                    s.d_total = M.h_st[f].d_total;
+                    s.max_tile_len = (int32_t)M.h_st[f].max_tile_len;
+                    s.n_tiles = n_tiles;
+                    s.n_pixels = (int64_t)W * (std::min(H, SGS_TILE * row_end) - SGS_TILE * row_begin);
+                    s.retries = retries;
+                    s.ms_total = ms / (float)nf;
+                }
+                break;
+            }
+            // the record buffer overflowed: grow it to fit and render the group again
+            if (++retries > 4) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "mesh record buffer still too small after 4 retries");
+            M.cap_wanted = std::min<int64_t>(std::max<int64_t>(total + total / 4, M.list_cap * 2), kMaxRecords);
+            if (total > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "mesh depth: %lld records exceed 2^32", (long long)total);
+        }
+    }
+    return SGS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sgs_render_mesh_depth(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cam, const sgs_config* cfg, int tile_row_begin,
+                          int tile_row_end, float* out_depth, sgs_stats* stats, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    return mesh_frames(ctx, mesh, cam, 1, cfg, tile_row_begin, tile_row_end, out_depth, 0, stats, hip_stream);
+}
+
+int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams, const sgs_config* cfg,
+                                float* out_depth, sgs_stats* stats, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (!cams || n_cams < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "no cameras");
+    return mesh_frames(ctx, mesh, cams, n_cams, cfg, 0, -1, out_depth, (int64_t)cams[0].width * cams[0].height, stats, hip_stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,298 @@
+// sgs_mesh.h — gfx950 kernels of the collision-mesh depth path (sgs_render_mesh_depth*, include/sage_gs.h).
+//
+// A group of up to SGS_MESH_MAX_GROUP frames of one resolution is five stream-ordered launches with no host synchronisation in between:
+//   k_mesh_setup      one thread per (triangle, frame): fp64 transform, cull, 16-float record, tile rect of the part with z >= near_z
+//   k_mesh_bin<0>     per-tile counts: a rect of at most SGS_MESH_SMALL tiles is walked by its own thread, a larger one by a wave
+//   k_mesh_scan       one workgroup per frame: exclusive scan of the counts -> tile offsets, D, the longest list
+//   k_mesh_bin<1>     the same walk again, scattering triangle ids into the per-tile lists (the record buffer)
+//   k_mesh_depth      one 256-lane workgroup per 16x16-pixel tile: the list's records staged through LDS, a running min per pixel
+// The result of a pixel is a MINIMUM over the triangles its tile lists, so it depends neither on the order of a list nor on which other
+// tiles / frames share the launches: batch, band and single frame agree bit for bit, as do permutations of the triangles.
+//
+// Watertightness: the inside test of pixel ray r = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1) against triangle (p0, p1, p2) is
+// sign(det) * e_k . r >= 0 for the three edge planes e_k = p_a x p_b through the camera (homogeneous edge functions in camera space: no
+// projection, no division, linear in r; the mirrored cone behind the camera is what the z > near_z test removes).  Two triangles that
+// share an edge compute its e from the same two fp64 vertices, in the order of their indices (lower first) and with a product that is
+// anti-commutative bit for bit (mul and sub each rounded on their own, never fused), then round it to fp32 and flip its sign exactly.
+// Both then evaluate +-the same fp32 value at every pixel, and e . r == 0 counts as inside for both: no pixel falls between them.
+#pragma once
+#include "sgs_common.h"
+
+#define SGS_MESH_MAX_GROUP 8        // frames per set of launches (blockIdx.y = frame)
+#define SGS_MESH_SMALL 16           // rects of at most this many tiles are binned by one thread; larger ones by a whole wave
+#define SGS_MESH_BIN_BLOCKS 1024    // binning workgroups (grid-stride over the triangles)
+#define SGS_MESH_SCAN_THREADS 1024
+
+namespace sgs {
+
+struct MeshFrame {
+    float view[12];                 // model -> camera, rows of a rigid 3x4
+    float fx, fy, cx, cy, near_z, far_z;
+    int32_t width, height;
+    int32_t gx;                     // tiles per row
+    int32_t row_begin, row_end;     // the band of tile rows [row_begin, row_end) of the frame
+    float* out;                     // the frame's H*W depth buffer
+};
+
+struct MeshStatus {
+    unsigned n_visible;             // triangles with a non-empty rect in the band
+    unsigned d_total;               // records of the frame
+    unsigned max_tile_len;
+    unsigned n_big;                 // entries of the frame's big-rect list
+};
+
+struct MeshGroup {
+    MeshFrame f[SGS_MESH_MAX_GROUP];
+    int32_t nf;
+    int32_t n_tiles;                // tiles of one frame's band (the same for every frame of the group)
+    long long n_tris;
+    long long cap;                  // entries the record buffer holds
+    const float* verts;             // [V][3]
+    const int* tris;                // [F][3]
+    float4* rec;                    // [nf][F][4]: (e0, 0) (e1, 0) (e2, 0) (n, n.p0), edges already multiplied by sign(det)
+    uint2* rect;                    // [nf][F]: tile rect, x0 | x1 << 16, y0 | y1 << 16 (x0 > x1: empty)
+    unsigned* big;                  // [nf][F]: triangles whose rect exceeds SGS_MESH_SMALL tiles
+    unsigned* counts;               // [nf][n_tiles]: per-tile counts, then the emit's cursors (zeroed before every group)
+    unsigned* offs;                 // [nf][n_tiles + 1]: offsets within the frame's part of the record buffer
+    unsigned* list;                 // the record buffer: triangle ids, frame after frame
+    MeshStatus* st;                 // [nf] (zeroed before every group)
+};
+
+// Upload check: every vertex finite (bit 0 of *bad), every index in [0, n_verts) (bit 1).
+__global__ __launch_bounds__(256) void k_mesh_validate(long long n_verts, const float* __restrict__ verts, long long n_tris,
+                                                      const int* __restrict__ tris, unsigned* __restrict__ bad) {
+    unsigned flags = 0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * n_verts; i += stride)
+        if ((__float_as_uint(verts[i]) & 0x7f800000u) == 0x7f800000u) flags |= 1u;     // inf / NaN
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * n_tris; i += stride)
+        if (tris[i] < 0 || (long long)tris[i] >= n_verts) flags |= 2u;
+    if (flags) atomicOr(bad, flags);
+}
+
+struct MeshD3 { double x, y, z; };
+
+// a x b with every product and difference rounded on its own: b x a == -(a x b) exactly
+__device__ __forceinline__ MeshD3 mesh_cross_rn(const MeshD3& a, const MeshD3& b) {
+    return MeshD3{__dsub_rn(__dmul_rn(a.y, b.z), __dmul_rn(a.z, b.y)), __dsub_rn(__dmul_rn(a.z, b.x), __dmul_rn(a.x, b.z)),
+                  __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x))};
+}
+
+__device__ __forceinline__ unsigned mesh_tile_of(int x, int y, const MeshFrame& F) { return (unsigned)((y - F.row_begin) * F.gx + x); }
+
+__global__ __launch_bounds__(256) void k_mesh_setup(const MeshGroup G) {
+    const int f = blockIdx.y;
+    const MeshFrame& F = G.f[f];
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    bool live = false;
+    if (t < G.n_tris) {
+        const size_t slot = (size_t)f * (size_t)G.n_tris + (size_t)t;
+        uint2 rect = make_uint2(1u, 1u);                    // empty
+        int idx[3];
+        MeshD3 p[3];
+        for (int k = 0; k < 3; ++k) {
+            idx[k] = G.tris[3 * t + k];
+            const float* v = G.verts + 3 * (size_t)idx[k];
+            const double x = v[0], y = v[1], z = v[2];
+            // fp64, explicit fmas: the same vertex gives the same bits in every triangle that uses it
+            p[k].x = fma((double)F.view[0], x, fma((double)F.view[1], y, fma((double)F.view[2], z, (double)F.view[3])));
+            p[k].y = fma((double)F.view[4], x, fma((double)F.view[5], y, fma((double)F.view[6], z, (double)F.view[7])));
+            p[k].z = fma((double)F.view[8], x, fma((double)F.view[9], y, fma((double)F.view[10], z, (double)F.view[11])));
+        }
+        const double nz = F.near_z, fz = F.far_z, W = F.width, H = F.height;
+        const bool behind = p[0].z <= nz && p[1].z <= nz && p[2].z <= nz;
+        const bool beyond = p[0].z > fz && p[1].z > fz && p[2].z > fz;
+        // side planes of the whole frame (a band only clamps the rect, so that a band sees exactly the triangles the full frame does)
+        bool out_l = true, out_r = true, out_t = true, out_b = true;
+        for (int k = 0; k < 3; ++k) {
+            out_l = out_l && (F.fx * p[k].x + F.cx * p[k].z < 0.0);
+            out_r = out_r && (F.fx * p[k].x + (F.cx - W) * p[k].z > 0.0);
+            out_t = out_t && (F.fy * p[k].y + F.cy * p[k].z < 0.0);
+            out_b = out_b && (F.fy * p[k].y + (F.cy - H) * p[k].z > 0.0);
+        }
+        const MeshD3 c12 = mesh_cross_rn(p[1], p[2]);
+        const double det = c12.x * p[0].x + c12.y * p[0].y + c12.z * p[0].z;
+        if (!behind && !beyond && !out_l && !out_r && !out_t && !out_b && det != 0.0 && det == det) {
+            // tile rect of the part with z >= near_z (a triangle that straddles the camera plane projects without bound otherwise)
+            double umin = 1e300, umax = -1e300, vmin = 1e300, vmax = -1e300;
+            for (int k = 0; k < 3; ++k) {
+                const MeshD3& a = p[k];
+                const MeshD3& b = p[(k + 1) % 3];
+                MeshD3 q[2];
+                int nq = 0;
+                if (a.z >= nz) q[nq++] = a;
+                if ((a.z >= nz) != (b.z >= nz)) {
+                    const double s = (nz - a.z) / (b.z - a.z);
+                    q[nq++] = MeshD3{a.x + s * (b.x - a.x), a.y + s * (b.y - a.y), nz};
+                }
+                for (int j = 0; j < nq; ++j) {
+                    const double iz = 1.0 / q[j].z;
+                    const double u = fmin(fmax(F.fx * q[j].x * iz + F.cx, -2.0), W + 2.0);
+                    const double v = fmin(fmax(F.fy * q[j].y * iz + F.cy, -2.0), H + 2.0);
+                    umin = fmin(umin, u); umax = fmax(umax, u); vmin = fmin(vmin, v); vmax = fmax(vmax, v);
+                }
+            }
+            if (umin <= umax) {
+                // pixel x is sampled at u = x + 0.5; one pixel of slack on each side for the fp32 edge tests
+                const int x0 = max((int)floor(umin) - 1, 0), x1 = min((int)floor(umax) + 1, F.width - 1);
+                const int y0 = max((int)floor(vmin) - 1, 0), y1 = min((int)floor(vmax) + 1, F.height - 1);
+                const int tx0 = x0 >> 4, tx1 = x1 >> 4;
+                const int ty0 = max(y0 >> 4, F.row_begin), ty1 = min(y1 >> 4, F.row_end - 1);
+                if (x0 <= x1 && ty0 <= ty1) {
+                    live = true;
+                    rect = make_uint2((unsigned)tx0 | ((unsigned)tx1 << 16), (unsigned)ty0 | ((unsigned)ty1 << 16));
+                    const double sg = det > 0.0 ? 1.0 : -1.0;
+                    float4* R = G.rec + 4 * slot;
+                    for (int k = 0; k < 3; ++k) {
+                        const int a = (k + 1) % 3, b = (k + 2) % 3;
+                        // the edge's plane from its vertices in index order, sign flipped exactly afterwards
+                        const bool swap = idx[a] > idx[b];
+                        const MeshD3 e = swap ? mesh_cross_rn(p[b], p[a]) : mesh_cross_rn(p[a], p[b]);
+                        const double s = swap ? -sg : sg;
+                        R[k] = make_float4((float)(s * e.x), (float)(s * e.y), (float)(s * e.z), 0.f);
+                    }
+                    const MeshD3 u1{p[1].x - p[0].x, p[1].y - p[0].y, p[1].z - p[0].z}, u2{p[2].x - p[0].x, p[2].y - p[0].y, p[2].z - p[0].z};
+                    const MeshD3 n{u1.y * u2.z - u1.z * u2.y, u1.z * u2.x - u1.x * u2.z, u1.x * u2.y - u1.y * u2.x};
+                    R[3] = make_float4((float)n.x, (float)n.y, (float)n.z, (float)(n.x * p[0].x + n.y * p[0].y + n.z * p[0].z));
+                    if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) > SGS_MESH_SMALL) {
+                        const unsigned k = atomicAdd(&G.st[f].n_big, 1u);
+                        G.big[(size_t)f * (size_t)G.n_tris + k] = (unsigned)t;
+                    }
+                }
+            }
+        }
+        G.rect[slot] = rect;
+    }
+    const unsigned long long m = __ballot(live);
+    if ((threadIdx.x & (SGS_WAVE - 1)) == 0 && m) atomicAdd(&G.st[f].n_visible, (unsigned)__popcll(m));
+}
+
+// The frame's base in the record buffer: the records of the frames before it in the group.
+__device__ __forceinline__ unsigned long long mesh_base(const MeshGroup& G, int f) {
+    unsigned long long b = 0;
+    for (int g = 0; g < f; ++g) b += G.st[g].d_total;
+    return b;
+}
+
+template <bool EMIT>
+__device__ __forceinline__ void mesh_bin_one(const MeshGroup& G, int f, unsigned tile, unsigned tri, unsigned long long base) {
+    unsigned* c = G.counts + (size_t)f * G.n_tiles + tile;
+    if (!EMIT) {
+        atomicAdd(c, 1u);
+    } else {
+        const unsigned long long pos = base + G.offs[(size_t)f * (G.n_tiles + 1) + tile] + atomicAdd(c, 1u);
+        if (pos < (unsigned long long)G.cap) G.list[pos] = tri;
+    }
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_mesh_bin(const MeshGroup G) {
+    const int f = blockIdx.y;
+    const MeshFrame& F = G.f[f];
+    const unsigned long long base = EMIT ? mesh_base(G, f) : 0ull;
+    const uint2* rects = G.rect + (size_t)f * (size_t)G.n_tris;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < G.n_tris; t += (long long)gridDim.x * blockDim.x) {
+        const uint2 r = rects[t];
+        const int x0 = r.x & 0xffff, x1 = r.x >> 16, y0 = r.y & 0xffff, y1 = r.y >> 16;
+        if (x0 > x1 || y0 > y1 || (x1 - x0 + 1) * (y1 - y0 + 1) > SGS_MESH_SMALL) continue;
+        for (int y = y0; y <= y1; ++y)
+            for (int x = x0; x <= x1; ++x) mesh_bin_one<EMIT>(G, f, mesh_tile_of(x, y, F), (unsigned)t, base);
+    }
+    // large rects (walls, floors): a wave per triangle, a lane per tile
+    const unsigned n_big = G.st[f].n_big;
+    const unsigned lane = threadIdx.x & (SGS_WAVE - 1);
+    const unsigned waves = blockDim.x / SGS_WAVE;
+    for (unsigned k = blockIdx.x * waves + threadIdx.x / SGS_WAVE; k < n_big; k += gridDim.x * waves) {
+        const unsigned t = G.big[(size_t)f * (size_t)G.n_tris + k];
+        const uint2 r = rects[t];
+        const int x0 = r.x & 0xffff, x1 = r.x >> 16, y0 = r.y & 0xffff, y1 = r.y >> 16;
+        const int w = x1 - x0 + 1, area = w * (y1 - y0 + 1);
+        for (int j = (int)lane; j < area; j += SGS_WAVE) mesh_bin_one<EMIT>(G, f, mesh_tile_of(x0 + j % w, y0 + j / w, F), t, base);
+    }
+}
+
+// One workgroup per frame: offs = exclusive scan of counts, counts zeroed (they are the emit's cursors next).
+__global__ __launch_bounds__(SGS_MESH_SCAN_THREADS) void k_mesh_scan(const MeshGroup G) {
+    __shared__ unsigned s_wave[SGS_MESH_SCAN_THREADS / SGS_WAVE];
+    __shared__ unsigned s_carry, s_max;
+    const int f = blockIdx.y;
+    const unsigned tid = threadIdx.x, lane = tid & (SGS_WAVE - 1), wv = tid / SGS_WAVE;
+    unsigned* counts = G.counts + (size_t)f * G.n_tiles;
+    unsigned* offs = G.offs + (size_t)f * (G.n_tiles + 1);
+    if (tid == 0) { s_carry = 0; s_max = 0; }
+    __syncthreads();
+    for (int b = 0; b < G.n_tiles; b += SGS_MESH_SCAN_THREADS) {
+        const int i = b + (int)tid;
+        const unsigned v = i < G.n_tiles ? counts[i] : 0u;
+        unsigned inc = v;
+        for (int d = 1; d < SGS_WAVE; d <<= 1) {
+            const unsigned o = __shfl_up(inc, d);
+            if ((int)lane >= d) inc += o;
+        }
+        if (lane == SGS_WAVE - 1) s_wave[wv] = inc;
+        if (v) atomicMax(&s_max, v);
+        __syncthreads();
+        if (wv == 0) {
+            const unsigned w = lane < SGS_MESH_SCAN_THREADS / SGS_WAVE ? s_wave[lane] : 0u;
+            unsigned winc = w;
+            for (int d = 1; d < SGS_MESH_SCAN_THREADS / SGS_WAVE; d <<= 1) {
+                const unsigned o = __shfl_up(winc, d);
+                if ((int)lane >= d) winc += o;
+            }
+            if (lane < SGS_MESH_SCAN_THREADS / SGS_WAVE) s_wave[lane] = winc - w;       // exclusive prefix of the waves
+        }
+        __syncthreads();
+        const unsigned carry = s_carry;
+        if (i < G.n_tiles) { offs[i] = carry + s_wave[wv] + inc - v; counts[i] = 0u; }
+        __syncthreads();
+        if (tid == SGS_MESH_SCAN_THREADS - 1) s_carry = carry + s_wave[wv] + inc;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        offs[G.n_tiles] = s_carry;
+        G.st[f].d_total = s_carry;
+        G.st[f].max_tile_len = s_max;
+    }
+}
+
+// One workgroup per tile of the band, one pixel per lane.
+__global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
+    __shared__ float4 s_rec[4][256];
+    const int f = blockIdx.y;
+    const MeshFrame& F = G.f[f];
+    unsigned long long total = 0, base = 0;
+    for (int g = 0; g < G.nf; ++g) { if (g == f) base = total; total += G.st[g].d_total; }
+    if (total > (unsigned long long)G.cap) return;           // overflow: the host grows the record buffer and renders again
+    const unsigned tile = blockIdx.x;
+    const unsigned* offs = G.offs + (size_t)f * (G.n_tiles + 1);
+    const unsigned long long begin = base + offs[tile], end = base + offs[tile + 1];
+    const int px = (int)(tile % (unsigned)F.gx) * SGS_TILE_PX + (int)(threadIdx.x & 15);
+    const int py = (F.row_begin + (int)(tile / (unsigned)F.gx)) * SGS_TILE_PX + (int)(threadIdx.x >> 4);
+    const float rx = ((float)px + 0.5f - F.cx) / F.fx, ry = ((float)py + 0.5f - F.cy) / F.fy;
+    const float near_z = F.near_z, far_z = F.far_z;
+    const float4* rec = G.rec + 4 * (size_t)f * (size_t)G.n_tris;
+    float best = __uint_as_float(0x7f800000u);
+    for (unsigned long long b = begin; b < end; b += 256) {
+        const int n = end - b < 256ull ? (int)(end - b) : 256;
+        if ((int)threadIdx.x < n) {
+            const float4* R = rec + 4 * (size_t)G.list[b + threadIdx.x];
+            s_rec[0][threadIdx.x] = R[0]; s_rec[1][threadIdx.x] = R[1]; s_rec[2][threadIdx.x] = R[2]; s_rec[3][threadIdx.x] = R[3];
+        }
+        __syncthreads();
+        for (int k = 0; k < n; ++k) {
+            const float4 e0 = s_rec[0][k], e1 = s_rec[1][k], e2 = s_rec[2][k];
+            const float s0 = fmaf(e0.x, rx, fmaf(e0.y, ry, e0.z));
+            const float s1 = fmaf(e1.x, rx, fmaf(e1.y, ry, e1.z));
+            const float s2 = fmaf(e2.x, rx, fmaf(e2.y, ry, e2.z));
+            if (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f) {
+                const float4 pl = s_rec[3][k];
+                const float z = pl.w / fmaf(pl.x, rx, fmaf(pl.y, ry, pl.z));
+                if (z > near_z && z <= far_z) best = fminf(best, z);
+            }
+        }
+        __syncthreads();
+    }
+    if (px < F.width && py < F.height) F.out[(size_t)py * F.width + px] = best;
+}
+
+}  // namespace sgs

@@ -30,7 +30,8 @@ DEFAULT_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create", "sgs_destroy", "sgs_last_error",
            "sgs_set_record_capacity", "sgs_scene_upload", "sgs_scene_upload_compressed", "sgs_scene_free", "sgs_render",
            "sgs_render_rgbd", "sgs_render_batch", "sgs_render_batch_strided", "sgs_frame_sync", "sgs_row_records", "sgs_pack_rgba8", "sgs_debug_read",
-           "sgs_tuning_default", "sgs_set_tuning", "sgs_get_tuning")
+           "sgs_tuning_default", "sgs_set_tuning", "sgs_get_tuning",
+           "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch")
 
 
 class SgsError(RuntimeError):
@@ -129,6 +130,11 @@ class Lib:
         lib.sgs_tuning_default.argtypes = [C.POINTER(SgsTuning)]; lib.sgs_tuning_default.restype = None
         lib.sgs_set_tuning.argtypes = [vp, C.POINTER(SgsTuning)]
         lib.sgs_get_tuning.argtypes = [vp, C.POINTER(SgsTuning)]
+        lib.sgs_mesh_upload.argtypes = [vp, i64, vp, i64, vp, i32, C.POINTER(vp)]
+        lib.sgs_mesh_free.argtypes = [vp, vp]
+        lib.sgs_mesh_set_record_capacity.argtypes = [vp, i64]
+        lib.sgs_render_mesh_depth.argtypes = [vp, vp, C.POINTER(SgsCamera), C.POINTER(SgsConfig), i32, i32, vp, C.POINTER(SgsStats), vp]
+        lib.sgs_render_mesh_depth_batch.argtypes = [vp, vp, vp, i32, C.POINTER(SgsConfig), vp, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -18,10 +18,20 @@ from . import camera as cam_conv
 from .renderer import Camera, RenderConfig, Renderer
 
 
+# near / far of collision-mesh depth: Isaac Sim's default camera clipping range starts at 0.01 m (below get_depth's 0.1 m clip)
+MESH_CONFIG = RenderConfig(near=0.01)
+
+
 class GsCamera:
     def __init__(self, renderer: Renderer, scene, prim_path: str = "/World/Camera", frequency: int = 30,
-                 resolution: Tuple[int, int] = (640, 480), config: Optional[RenderConfig] = None):
+                 resolution: Tuple[int, int] = (640, 480), config: Optional[RenderConfig] = None, collision_mesh=None,
+                 mesh_config: Optional[RenderConfig] = None):
+        """collision_mesh: a Mesh (Renderer.upload_mesh) — get_depth() / get_current_frame()["distance_to_image_plane"] then come
+        from it, as the reference's come from /World/scene_collision (simple_env.py:1395-1589); mesh_config: its near / far (default
+        MESH_CONFIG).  Without a mesh, depth is the Gaussians' expected depth, as before."""
         self._r, self._scene, self.prim_path, self.frequency = renderer, scene, prim_path, frequency
+        self._mesh = collision_mesh
+        self._mesh_config = mesh_config if mesh_config is not None else MESH_CONFIG
         self._w, self._h = int(resolution[0]), int(resolution[1])         # Isaac resolution = (width, height)
         self._pos = np.zeros(3, np.float32)
         self._orient = np.array([1.0, 0.0, 0.0, 0.0], np.float32)         # (w, x, y, z)
@@ -68,6 +78,10 @@ class GsCamera:
         img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config)
         return img.copy() if copy else img
 
+    def _mesh_depth(self):
+        """depth [H,W] float32 on the GPU: distance to the image plane of the nearest collision-mesh triangle, +inf where none."""
+        return self._r.render_mesh_depth(self._camera(), self._mesh, config=self._mesh_config)
+
     def _rgb_depth(self):
         """(rgb [H,W,3] float32 on the GPU, depth [H,W] float32 on the GPU): depth = the scene's expected view depth along
         the optical axis, sum(T alpha z) / coverage — the Gaussian-scene counterpart of Isaac Sim's
@@ -81,14 +95,18 @@ class GsCamera:
 
     def get_current_frame(self) -> dict:
         """{'rgba': uint8 [H,W,4], 'distance_to_image_plane': float32 [H,W]} (simple_env.py:286,1425,1659)."""
-        rgb, depth = self._rgb_depth()
+        if self._mesh is not None:
+            rgb = self._r.render(self._camera(), self._scene, config=self._config)
+            depth = self._mesh_depth()
+        else:
+            rgb, depth = self._rgb_depth()
         return {"rgba": self._r.pack_rgba8(rgb).cpu().numpy(), "distance_to_image_plane": depth.cpu().numpy()}
 
     def get_depth(self, clip=(0.1, 6.5)) -> np.ndarray:
         """float32 [H,W] metres, limited to [0.1, 6.5] exactly as SimpleVLNEnv.get_depth does with the simulator's
         distance_to_image_plane (simple_env.py:1573-1578: astype(float32), np.clip(depth, 0.1, 6.5)); a pixel that hit
-        nothing (inf) therefore reads 6.5."""
-        _, depth = self._rgb_depth()
+        nothing (inf) therefore reads 6.5.  With a collision mesh, from the mesh (the reference's source)."""
+        depth = self._mesh_depth() if self._mesh is not None else self._rgb_depth()[1]
         d = depth.cpu().numpy().astype(np.float32)
         return np.clip(d, clip[0], clip[1]) if clip is not None else d
 
@@ -132,7 +150,7 @@ def parse_scene_usda(text: str) -> dict:
     /World/scene_collision (:156-158), and the gauss prim's transform ops — `double3 xformOp:rotateXYZ / :scale /
     :translate` and their `xformOpOrder` (:119-123) — plus the stage's upAxis and metersPerUnit (:105-108)."""
     out = {"usdz": None, "collision": None, "rotate_xyz": None, "scale": None, "translate": None, "xform_op_order": None,
-           "up_axis": None, "meters_per_unit": None}
+           "up_axis": None, "meters_per_unit": None, "collision_ops": None}
     m = re.search(r"@([^@\n]+\.usdz)\[gauss\.usda\]@", text)
     if m:
         out["usdz"] = m.group(1)
@@ -149,6 +167,10 @@ def parse_scene_usda(text: str) -> dict:
         m = re.search(r"xformOpOrder\s*=\s*\[([^\]]*)\]", body)
         if m:
             out["xform_op_order"] = tuple(t.strip().strip('"') for t in m.group(1).split(",") if t.strip())
+    body = _prim_body(text, r'(?:def|over)\s+(?:Xform\s+)?"scene_collision"\s*')
+    if body is not None:
+        from .mesh import split_prim
+        out["collision_ops"] = split_prim(body, 0, len(body))[0]            # the prim's own attributes (its child prims cut out)
     m = re.search(r'upAxis\s*=\s*"([XYZ])"', text)
     if m:
         out["up_axis"] = m.group(1)
@@ -156,6 +178,15 @@ def parse_scene_usda(text: str) -> dict:
     if m:
         out["meters_per_unit"] = float(m.group(1))
     return out
+
+
+def collision_model_to_world(parsed: dict) -> np.ndarray:
+    """The 4x4 model->world matrix of /World/scene_collision from `parse_scene_usda`'s `collision_ops` (its xformOps in
+    `xformOpOrder`; identity when the stage has no such prim).  The template's (translate 0, orient (6.123234e-17, 0, 0, 1), scale 1)
+    is a rotation by 180 degrees about Z (template.usda:156-165)."""
+    from .mesh import xform_from_attrs
+    ops = parsed.get("collision_ops")
+    return xform_from_attrs(ops) if ops else np.eye(4)
 
 
 def asset_model_to_world(parsed: dict) -> np.ndarray:

@@ -28,7 +28,8 @@ get_rgb()-shaped callers are served through adapter.GsCamera directly.
 (adapter.parse_scene_usda; sage3d_usda_builder.py:93-149) -> the Gaussians beside that USDZ — `<stem>.ply`, `<dir>/3dgs.ply`, or the
 PlayCanvas-compressed `<stem>_compressed.ply` / `<dir>/3dgs_compressed.ply` the USDZ was converted from (README.md:210-253) — with the
 prim's model->world transform (template.usda:115-124); a `.ply` path is opened as such.  The scene is uploaded once per stage, as
-the reference loads a stage once per scene.  Lights, physics and collision payloads are accepted and ignored: the renderer produces
+the reference loads a stage once per scene.  Lights and physics are accepted and ignored; the collision payload is loaded only under
+configure(collision=True), for the cameras' depth (otherwise it is ignored too).  The renderer produces
 linear radiance from the Gaussians alone.  Failures raise (no silent `False` for a missing asset: `open_stage`
 returns False only where the reference's would — the stage file does not exist).
 """
@@ -43,11 +44,14 @@ import numpy as np
 
 from . import adapter
 
-_state = {"renderer": None, "loader": None, "stage": None, "app": None, "scene_root": None}
+_state = {"renderer": None, "loader": None, "stage": None, "app": None, "scene_root": None, "collision": False}
 
 
-def configure(renderer=None, loader=None, scene_root=None):
-    """renderer: the sage_gs.Renderer frames are drawn with (default: one on cuda:LOCAL_RANK / cuda:0, created at the first
+def configure(renderer=None, loader=None, scene_root=None, collision=None):
+    """collision=True: open_stage also loads the stage's collision payload (/World/scene_collision, an ASCII .usda — a crate file must
+    be converted with usdcat first) and the cameras' get_depth() / distance_to_image_plane come from it, as the reference's do
+    (simple_env.py:1395-1589); a missing or unreadable payload then raises.  Default off: depth from the Gaussians.
+    renderer: the sage_gs.Renderer frames are drawn with (default: one on cuda:LOCAL_RANK / cuda:0, created at the first
     open_stage).  loader(path, compressed) -> (means, scales, quats, opacities, sh, degree) (default: sage_gs.ply).  scene_root: an
     extra directory searched for `<scene_id>.ply` / `<scene_id>_compressed.ply` when nothing lies beside the referenced USDZ."""
     if renderer is not None:
@@ -56,6 +60,8 @@ def configure(renderer=None, loader=None, scene_root=None):
         _state["loader"] = loader
     if scene_root is not None:
         _state["scene_root"] = scene_root
+    if collision is not None:
+        _state["collision"] = bool(collision)
 
 
 def _renderer():
@@ -123,8 +129,9 @@ class _Attr:
 class Stage:
     """What `omni.usd.get_context().get_stage()` hands the callers: the prims they ask about, and the scene the stage holds."""
 
-    def __init__(self, path, parsed, scene, model_to_world, asset):
+    def __init__(self, path, parsed, scene, model_to_world, asset, collision_mesh=None):
         self.path, self.parsed, self.scene, self.model_to_world, self.asset = path, parsed, scene, model_to_world, asset
+        self.collision_mesh = collision_mesh
         self._prims = {"/World": Prim(self, "/World"), "/World/gauss": Prim(self, "/World/gauss")}
         self.cameras = {}
 
@@ -161,6 +168,8 @@ class UsdContext:
         st = _state["stage"]
         if st is not None and st.scene is not None and hasattr(st.scene, "free"):
             st.scene.free()
+        if st is not None and st.collision_mesh is not None:
+            st.collision_mesh.free()
         _state["stage"] = None
         return True
 
@@ -217,9 +226,23 @@ def open_stage(usd_path: str) -> bool:
     arrays = _load(asset, comp)
     r = _renderer()
     from . import ply
+    mesh = _load_collision(usd_path, parsed, r) if _state["collision"] else None
     scene = r.upload(ply.to_gaussians(arrays, r.device, m2w))
-    _state["stage"] = Stage(usd_path, parsed, scene, m2w, asset)
+    _state["stage"] = Stage(usd_path, parsed, scene, m2w, asset, mesh)
     return True
+
+
+def _load_collision(usd_path, parsed, r):
+    """The stage's collision payload as a Mesh, placed by /World/scene_collision's ops (configure(collision=True))."""
+    from . import mesh as mesh_io
+    rel = parsed.get("collision")
+    if not rel:
+        raise FileNotFoundError(f"{usd_path}: configure(collision=True), but the stage names no collision payload (/World/scene_collision)")
+    path = rel if os.path.isabs(rel) else os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(usd_path)), rel))
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{usd_path}: collision payload {path} not found")
+    verts, tris = mesh_io.read_usda_mesh(path)
+    return r.upload_mesh(verts, tris, adapter.collision_model_to_world(parsed))
 
 
 class World:
@@ -276,7 +299,8 @@ def Camera(prim_path: str = "/World/Camera", frequency: int = 30, resolution: Tu
     st = _state["stage"]
     if st is None:
         raise RuntimeError("Camera(): no stage is open (call open_stage first)")
-    cam = adapter.GsCamera(_renderer(), st.scene, prim_path=str(prim_path), frequency=int(frequency), resolution=tuple(resolution))
+    cam = adapter.GsCamera(_renderer(), st.scene, prim_path=str(prim_path), frequency=int(frequency), resolution=tuple(resolution),
+                           collision_mesh=st.collision_mesh)
     if "position" in kwargs or "orientation" in kwargs:
         cam.set_world_pose(kwargs.get("position"), kwargs.get("orientation"))
     st.DefinePrim(str(prim_path), "Camera")

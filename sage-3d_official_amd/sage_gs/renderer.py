@@ -96,6 +96,44 @@ class Scene:
             pass
 
 
+class Mesh:
+    """A device-resident triangle mesh for depth rendering (the collision mesh of a scene, include/sage_gs.h sgs_mesh_upload).
+    `model_to_world` is the RIGID part of the transform it was uploaded with (any scale / shear is already in the vertices)."""
+
+    def __init__(self, renderer: "Renderer", handle, n_vertices, n_triangles, model_to_world):
+        self._r, self.handle, self.n_vertices, self.n_triangles = renderer, handle, n_vertices, n_triangles
+        self.model_to_world = model_to_world
+
+    def free(self):
+        if self.handle:
+            self._r._lib.sgs_mesh_free(self._r._ctx, self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _split_model_to_world(m):
+    """(rigid 4x4, 3x3 to bake into the vertices) with m[:3,:3] = R @ S, R the rotation nearest to it (polar decomposition).  A rigid m
+    gives (m, None) — re-orthonormalised as _check_model_to_world does."""
+    m = np.array(m, np.float64, copy=True).reshape(4, 4)
+    if not np.allclose(m[3], [0.0, 0.0, 0.0, 1.0], atol=1e-12) or not np.isfinite(m).all():
+        raise ValueError("model_to_world must be an affine 4x4 with last row (0, 0, 0, 1)")
+    a = m[:3, :3]
+    if float(np.abs(a @ a.T - np.eye(3)).max()) <= 1.0e-5 and np.linalg.det(a) > 0:
+        return _check_model_to_world(m), None
+    u, _, vt = np.linalg.svd(a)
+    if np.linalg.det(u @ vt) < 0:
+        u[:, -1] = -u[:, -1]
+    r = u @ vt
+    rigid = np.eye(4)
+    rigid[:3, :3], rigid[:3, 3] = r, m[:3, 3]
+    return rigid, r.T @ a
+
+
 def _rigid(views: np.ndarray) -> np.ndarray:
     """[...,4,4] float64 CAMERA poses (world -> camera) -> the same, with every 3x3 that is measurably off orthonormal AFTER the cast to
     fp32 (a view composed or inverted in fp32: torch.linalg.inv of a c2w matrix, poses parsed from 6-digit text) replaced by the nearest
@@ -541,6 +579,85 @@ class Renderer:
         splats = self.debug_buffer(_capi.BUF_SPLATS, np.uint32).reshape(-1, 12)
         live = ids != 0xFFFFFFFF
         return off, ids[slots].astype(np.int64), ids[live].astype(np.int64), splats[live]
+
+    # -- collision-mesh depth (include/sage_gs.h sgs_render_mesh_depth*) ---------------------------------------------------------
+    def upload_mesh(self, vertices, triangles, model_to_world=None) -> Mesh:
+        """vertices [V,3] and triangles [F,3] (int) — NumPy arrays or tensors, on the host or on a device.  The non-rigid part of
+        model_to_world (a scale, a shear: USD xformOp:scale / metersPerUnit) is baked into the vertices here, so that the view the
+        library gets stays rigid; the rotation + translation travel with the Mesh and are applied by moving the camera."""
+        rigid, bake = (None, None) if model_to_world is None else _split_model_to_world(model_to_world)
+        v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
+        t = triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else np.asarray(triangles)
+        v = np.asarray(v, np.float64).reshape(-1, 3)
+        if t.size and (not np.issubdtype(t.dtype, np.integer)):
+            raise ValueError("triangles must be integer indices")
+        t = np.ascontiguousarray(np.asarray(t, np.int64).reshape(-1, 3))
+        if t.size and (t.min() < -(1 << 31) or t.max() >= (1 << 31)):
+            raise ValueError("triangle indices do not fit int32")
+        if bake is not None:
+            v = v @ bake.T
+        vf = torch.from_numpy(np.ascontiguousarray(v, np.float32)).to(self.device)
+        tf = torch.from_numpy(t.astype(np.int32)).to(self.device)
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)
+            h = C.c_void_p()
+            self._lib.check(self._lib.sgs_mesh_upload(self._ctx, int(vf.shape[0]), vf.data_ptr() if vf.numel() else None, int(tf.shape[0]),
+                                                      tf.data_ptr() if tf.numel() else None, 1, C.byref(h)), self._ctx)
+        return Mesh(self, h, int(vf.shape[0]), int(tf.shape[0]), rigid)
+
+    def _mesh_of(self, mesh: Mesh) -> Mesh:
+        if not isinstance(mesh, Mesh) or mesh._r is not self:
+            raise ValueError("the mesh must be a Mesh uploaded by this Renderer (upload_mesh)")
+        if mesh.handle is None:
+            raise ValueError("this Mesh has been freed")
+        return mesh
+
+    def render_mesh_depth(self, camera: Camera, mesh: Mesh, *, config: Optional[RenderConfig] = None, tile_rows=None,
+                          out: Optional[torch.Tensor] = None, timing=False) -> torch.Tensor:
+        """float32 [H,W] on the device: per pixel the camera-space z (distance to the image plane) of the nearest triangle of `mesh`
+        hit with near < z <= far (config; both faces count), +inf where none is.  tile_rows=(r0,r1): only that band of 16-pixel tile
+        rows is written (the rest of `out` is left as it was).  Statistics in last_stats."""
+        mesh = self._mesh_of(mesh)
+        h, w = camera.height, camera.width
+        if out is None:
+            out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
+        elif out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (h, w) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [H, W] tensor on the renderer's device")
+        r0, r1 = (0, -1) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
+        cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
+        cam = self._c_camera(camera, mesh)
+        st = _capi.SgsStats()
+        self._lib.check(self._lib.sgs_render_mesh_depth(self._ctx, mesh.handle, C.byref(cam), C.byref(cfg), r0, r1, out.data_ptr(),
+                                                        C.byref(st), self._stream()), self._ctx)
+        self.last_stats = st.as_dict()
+        return out
+
+    def render_mesh_depth_batch(self, cameras: Sequence[Camera], mesh: Mesh, *, config: Optional[RenderConfig] = None,
+                                out: Optional[torch.Tensor] = None, timing=False, want_stats=False):
+        """render_mesh_depth for B cameras of one resolution in one call: float32 [B,H,W] (and the frames' statistics with want_stats).
+        Every frame equals the one render_mesh_depth draws, bit for bit."""
+        mesh = self._mesh_of(mesh)
+        b = len(cameras)
+        if b == 0:
+            raise ValueError("no cameras")
+        h, w = cameras[0].height, cameras[0].width
+        if any(c.height != h or c.width != w for c in cameras):
+            raise ValueError("all cameras of a batch must share a resolution")
+        if out is None:
+            out = torch.zeros((b, h, w), dtype=torch.float32, device=self.device)
+        elif out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [B, H, W] tensor on the renderer's device")
+        cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
+        arr = self._c_cameras(cameras, mesh)
+        stats = (_capi.SgsStats * b)()
+        self._lib.check(self._lib.sgs_render_mesh_depth_batch(self._ctx, mesh.handle, arr.ctypes.data, b, C.byref(cfg), out.data_ptr(),
+                                                              stats, self._stream()), self._ctx)
+        self.last_stats = stats[b - 1].as_dict()
+        return (out, [s.as_dict() for s in stats]) if want_stats else out
+
+    def set_mesh_record_capacity(self, n: int):
+        """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
+        self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)
 
     def set_record_capacity(self, n: int):
         self._lib.check(self._lib.sgs_set_record_capacity(self._ctx, int(n)), self._ctx)

@@ -331,3 +331,120 @@ def to_gaussians(scene: SceneArrays, device):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     return Gaussians(t(scene.means), t(scene.scales), t(scene.quats), t(scene.opacities), t(scene.sh),
                      scene.sh_degree, scene.model_to_world)
+
+
+# ---- synthetic collision meshes (the depth channel's geometry: sgs_render_mesh_depth) ---------------------------------------------------
+@dataclass
+class RoomMesh:
+    """A triangle mesh in the world frame (Z up, metres): vertices float64 [V,3], triangles int64 [F,3].  extent / rooms as in
+    SceneArrays, so that room_cameras() places cameras in it; model_to_world is the identity (the vertices are in world space)."""
+    vertices: np.ndarray
+    triangles: np.ndarray
+    extent: tuple = (0.0, 0.0, 0.0)
+    rooms: tuple = ()
+    model_to_world: np.ndarray = None
+
+
+def grid_box(lo, hi, n):
+    """The closed surface of the axis-aligned box [lo, hi] as a grid of n = (nx, ny, nz) cells per axis, two triangles per cell.
+    Faces that meet share the vertices of their seam (one lattice for the whole surface): the mesh is closed, without T-junctions."""
+    nx, ny, nz = (max(1, int(v)) for v in n)
+    xs, ys, zs = (np.linspace(float(lo[k]), float(hi[k]), m + 1) for k, m in enumerate((nx, ny, nz)))
+    idx = -np.ones((nx + 1, ny + 1, nz + 1), np.int64)
+    on = np.zeros(idx.shape, bool)
+    on[[0, -1], :, :] = True; on[:, [0, -1], :] = True; on[:, :, [0, -1]] = True
+    ii, jj, kk = np.nonzero(on)
+    idx[ii, jj, kk] = np.arange(len(ii))
+    verts = np.stack([xs[ii], ys[jj], zs[kk]], 1)
+    tris = []
+    def face(a, b):            # a, b: [ (m+1) x (l+1) ] index grids of one face
+        q00, q10, q01, q11 = a[:-1, :-1], a[1:, :-1], a[:-1, 1:], a[1:, 1:]
+        t = np.concatenate([np.stack([q00, q10, q11], -1).reshape(-1, 3), np.stack([q00, q11, q01], -1).reshape(-1, 3)])
+        tris.append(t[:, ::-1] if b else t)
+    face(idx[:, :, 0], True); face(idx[:, :, -1], False)
+    face(idx[:, 0, :], False); face(idx[:, -1, :], True)
+    face(idx[0, :, :], True); face(idx[-1, :, :], False)
+    return verts, np.concatenate(tris)
+
+
+def icosphere(level, centre=(0.0, 0.0, 0.0), radius=1.0):
+    """Closed geodesic sphere of 20 * 4^level triangles (each edge split once per level, midpoints shared)."""
+    t = (1.0 + math.sqrt(5.0)) / 2.0
+    V = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], np.float64)
+    V /= np.linalg.norm(V, axis=1, keepdims=True)
+    F = np.array([[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+                  [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]], np.int64)
+    for _ in range(int(level)):
+        a, b, c = F[:, 0], F[:, 1], F[:, 2]
+        e = np.sort(np.stack([np.stack([a, b], 1), np.stack([b, c], 1), np.stack([c, a], 1)], 1).reshape(-1, 2), axis=1)
+        uniq, inv = np.unique(e, axis=0, return_inverse=True)
+        mid = V[uniq[:, 0]] + V[uniq[:, 1]]
+        mid /= np.linalg.norm(mid, axis=1, keepdims=True)
+        m = len(V) + inv.reshape(-1, 3)
+        V = np.concatenate([V, mid])
+        F = np.concatenate([np.stack([a, m[:, 0], m[:, 2]], 1), np.stack([b, m[:, 1], m[:, 0]], 1),
+                            np.stack([c, m[:, 2], m[:, 1]], 1), m])
+    return V * radius + np.asarray(centre, np.float64), F
+
+
+def cylinder(centre, radius, height, segments, rings):
+    """Closed upright cylinder (base at centre, axis +Z): `segments` around, `rings` bands up the side, fan caps.  Many segments and few
+    rings make long slivers."""
+    s, r = max(3, int(segments)), max(1, int(rings))
+    ang = 2 * math.pi * np.arange(s) / s
+    ring = np.stack([radius * np.cos(ang), radius * np.sin(ang)], 1)
+    V = np.concatenate([np.concatenate([ring, np.full((s, 1), height * k / r)], 1) for k in range(r + 1)] +
+                       [np.array([[0.0, 0.0, 0.0], [0.0, 0.0, height]])])
+    V = V + np.asarray(centre, np.float64)
+    j = np.arange(s); jn = (j + 1) % s
+    T = []
+    for k in range(r):
+        a, b = k * s + j, k * s + jn
+        c, d = (k + 1) * s + j, (k + 1) * s + jn
+        T += [np.stack([a, b, d], 1), np.stack([a, d, c], 1)]
+    bot, top = (r + 1) * s, (r + 1) * s + 1
+    T += [np.stack([np.full(s, bot), jn, j], 1), np.stack([np.full(s, top), r * s + j, r * s + jn], 1)]
+    return V, np.concatenate(T)
+
+
+def make_room_mesh(n_triangles=50_000, seed=1, size=(6.0, 5.0), height=2.8):
+    """A synthetic collision mesh of about `n_triangles` triangles (10^3 .. 10^6): the closed shell of make_room's default 6 x 5 x 2.8 m
+    room (floor, ceiling, walls: one gridded box), six furniture boxes against the walls (gridded, closed), two tessellated spheres, a
+    hanging one and one on a box, and three cylinders whose many segments over few rings make long slivers.  Everything stays more than
+    0.3 m from where room_cameras() puts its cameras (at least 1 m from the walls, eye height 1.2 m).  make_room is not changed."""
+    rng = np.random.default_rng(seed)
+    n = max(1000, int(n_triangles))
+    sx, sy = size
+    parts = []
+    def cells(lo, hi, budget):                      # grid cells per axis for about `budget` triangles on the box's surface
+        d = np.asarray(hi, float) - np.asarray(lo, float)
+        area = 2.0 * (d[0] * d[1] + d[0] * d[2] + d[1] * d[2])
+        h = math.sqrt(2.0 * area / max(budget, 12))
+        return [max(1, int(round(v / h))) for v in d]
+    parts.append(grid_box((0.0, 0.0, 0.0), (sx, sy, height), cells((0, 0, 0), (sx, sy, height), 0.35 * n)))
+    boxes = []
+    for k in range(6):                               # against the walls, at most 0.7 m deep
+        wall = k % 4
+        w, d, h = rng.uniform(0.5, 1.5), rng.uniform(0.3, 0.6), rng.uniform(0.4, 1.9)
+        if wall in (0, 1):
+            x0 = rng.uniform(0.1, sx - 0.1 - w); y0 = 0.05 if wall == 0 else sy - 0.05 - d
+            lo, hi = (x0, y0, 0.0), (x0 + w, y0 + d, h)
+        else:
+            y0 = rng.uniform(0.1, sy - 0.1 - w); x0 = 0.05 if wall == 2 else sx - 0.05 - d
+            lo, hi = (x0, y0, 0.0), (x0 + d, y0 + w, h)
+        boxes.append((lo, hi))
+        parts.append(grid_box(lo, hi, cells(lo, hi, 0.2 * n / 6)))
+    lvl = max(1, int(round(math.log(max(0.12 * n / 20.0, 1.0), 4))))
+    parts.append(icosphere(lvl, (sx / 2, sy / 2, 2.35), 0.3))                              # hanging lamp above the cameras
+    lo, hi = boxes[0]
+    parts.append(icosphere(lvl, ((lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, hi[2] + 0.2), 0.2))
+    for k in range(3):                               # pillars in the corners: slivers
+        segs = max(16, int(math.sqrt(0.1 * n / 2 * 64)))
+        rings = max(1, segs // 64)
+        cx_, cy_ = [(0.45, 0.45), (sx - 0.45, 0.45), (0.45, sy - 0.45)][k]
+        parts.append(cylinder((cx_, cy_, 0.0), 0.15, height, segs, rings))
+    V, T, off = [], [], 0
+    for v, t in parts:
+        V.append(v); T.append(t + off); off += len(v)
+    return RoomMesh(np.concatenate(V), np.concatenate(T), (sx, sy, height), ((0.0, 0.0, sx, sy),), np.eye(4))

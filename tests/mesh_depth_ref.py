@@ -1,0 +1,165 @@
+"""fp64 NumPy ray caster: the reference the collision-mesh depth kernels (sgs_render_mesh_depth*) are checked against.
+
+Same rays as the kernels — pixel (x, y) samples r = ((x + 0.5 - cx) / fx, (y + 0.5 - cy) / fy, 1) in camera space — the same near / far
+rule (near < z <= far) and both faces of every triangle.  The camera's view and the vertices are rounded to fp32 first, as the library
+receives them; everything after that is fp64.
+
+Per pixel it returns three depths:
+  nominal   the exact answer of this arithmetic: min z over the triangles whose three edge functions sign(det) e_k . r are >= 0;
+  lenient   the same with every edge function relaxed by eps_k, and every candidate z lowered by its tolerance:  min z (1 - tol);
+  strict    every edge function tightened by eps_k, every candidate raised:                                           min z (1 + tol).
+A kernel's value `got` passes when  lenient <= got <= strict  (inf compared exactly: lenient = inf demands inf).  Away from edges the
+two agree up to the tolerances, so this is a relative check of ~1e-5; pixels within eps of an edge of some triangle ("edge band") may
+take either side's value.
+
+The bounds, from fp32 rounding (u = 2^-24).  The kernel rounds each e_k (computed in fp64 from fp64 vertices) to fp32 — |de_i| <= u |e_i|
+— forms r in fp32 — |dr_i| <= u |r_i| (x + 0.5 - cx is exact, the division rounds once) — and evaluates fma(e.x, r.x, fma(e.y, r.y, e.z)):
+two more roundings, each <= u times a partial sum bounded by sum_i |e_i r_i|.  To first order the error of e . r is therefore at most
+u (1 + 1 + 2) sum_i |e_i r_i| = 4 u sum_i |e_i r_i|; the reference uses eps_k = 5 u sum_i |e_k,i r_i| (one u of slack for the fp64
+steps and second-order terms).  That is ~3e-7 |e||r| at most — the "1e-7 relative to |e| |r|" order of the plain estimate, derived.
+The depth z = d / (n . r) goes through the same steps (n, d rounded to fp32: 1 u for d, 4 u sum_i |n_i r_i| for the denominator, 1 u
+for the division), so its relative error is at most u (2 + 4 G) with G = sum_i |n_i r_i| / |n . r| — G is ~1 for a surface seen face
+on and grows as 1 / sin(angle) for grazing ones.  The per-candidate tolerance is tol = 1e-5 + u (3 + 5 G): the 1e-5 of the pass rule
+plus the derived term, which only matters for rays within a few degrees of a triangle's plane.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+U = 2.0 ** -24
+EDGE_K = 5.0
+REL = 1.0e-5
+TILE = 8
+
+
+def _rays(cam, xs, ys):
+    return np.stack([(xs + 0.5 - cam["cx"]) / cam["fx"], (ys + 0.5 - cam["cy"]) / cam["fy"], np.ones(len(xs))], 1)
+
+
+def cam_dict(width, height, fx, fy, cx, cy, view):
+    return dict(width=int(width), height=int(height), fx=float(np.float32(fx)), fy=float(np.float32(fy)), cx=float(np.float32(cx)),
+                cy=float(np.float32(cy)), view=np.asarray(view, np.float32).astype(np.float64).reshape(4, 4))
+
+
+def of_camera(c, model_to_world=None):
+    """cam_dict of a sage_gs Camera (its view composed with model_to_world, rounded to fp32 as the library receives it)."""
+    v = np.asarray(c.view, np.float64).reshape(4, 4)
+    if model_to_world is not None:
+        v = v @ np.asarray(model_to_world, np.float64).reshape(4, 4)
+    return cam_dict(c.width, c.height, c.fx, c.fy, c.cx, c.cy, v)
+
+
+def cast(vertices, triangles, cam, near=0.2, far=1.0e30, pixels=None, chunk=1 << 21):
+    """vertices [V,3] (model space), triangles [F,3], cam: cam_dict.  pixels: None (the whole frame) or (ys, xs) arrays.
+    Returns dict(nominal, lenient, strict, edge) — float64 [H,W] (or [P]) and the edge-band mask."""
+    W, H = cam["width"], cam["height"]
+    if pixels is None:
+        ys, xs = np.divmod(np.arange(W * H), W)
+        shape = (H, W)
+    else:
+        ys, xs = (np.asarray(a, np.int64) for a in pixels)
+        shape = (len(ys),)
+    P = len(ys)
+    nom = np.full(P, np.inf); lo = np.full(P, np.inf); hi = np.full(P, np.inf); edge = np.zeros(P, bool)
+    V = np.asarray(vertices, np.float32).astype(np.float64)
+    T = np.asarray(triangles, np.int64).reshape(-1, 3)
+    if len(T) == 0 or P == 0:
+        return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
+    M = cam["view"]
+    Pc = V @ M[:3, :3].T + M[:3, 3]
+    p0, p1, p2 = Pc[T[:, 0]], Pc[T[:, 1]], Pc[T[:, 2]]
+    E = np.stack([np.cross(p1, p2), np.cross(p2, p0), np.cross(p0, p1)], 1)          # [F,3 edges,3]
+    det = np.einsum("ij,ij->i", E[:, 0], p0)
+    E *= np.sign(det)[:, None, None]
+    N = np.cross(p1 - p0, p2 - p0)
+    D = np.einsum("ij,ij->i", N, p0)
+    # conservative pixel rect of each triangle: the part with z >= near (1 - 1e-6), projected, plus two pixels
+    zc = near * (1.0 - 1.0e-6)
+    umin = np.full(len(T), np.inf); umax = np.full(len(T), -np.inf); vmin = umin.copy(); vmax = umax.copy()
+    P3 = [p0, p1, p2]
+    for k in range(3):
+        a, b = P3[k], P3[(k + 1) % 3]
+        pts = []
+        ka = a[:, 2] >= zc
+        pts.append((a, ka))
+        cross = ka != (b[:, 2] >= zc)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            s = (zc - a[:, 2]) / (b[:, 2] - a[:, 2])
+            q = a + s[:, None] * (b - a)
+        q[:, 2] = zc
+        pts.append((q, cross))
+        for q, ok in pts:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                u = np.clip(cam["fx"] * q[:, 0] / q[:, 2] + cam["cx"], -4, W + 4)
+                v = np.clip(cam["fy"] * q[:, 1] / q[:, 2] + cam["cy"], -4, H + 4)
+            umin = np.where(ok, np.minimum(umin, u), umin); umax = np.where(ok, np.maximum(umax, u), umax)
+            vmin = np.where(ok, np.minimum(vmin, v), vmin); vmax = np.where(ok, np.maximum(vmax, v), vmax)
+    live = (umin <= umax) & (det != 0) & np.isfinite(det)
+    x0 = np.clip(np.floor(umin) - 2, 0, W - 1); x1 = np.clip(np.floor(umax) + 2, 0, W - 1)
+    y0 = np.clip(np.floor(vmin) - 2, 0, H - 1); y1 = np.clip(np.floor(vmax) + 2, 0, H - 1)
+    tid = np.nonzero(live)[0]
+    tx0, tx1 = (x0[tid] // TILE).astype(np.int64), (x1[tid] // TILE).astype(np.int64)
+    ty0, ty1 = (y0[tid] // TILE).astype(np.int64), (y1[tid] // TILE).astype(np.int64)
+    gx = (W + TILE - 1) // TILE
+    # pixels of the target set by tile (CSR)
+    ptile = (ys // TILE) * gx + xs // TILE
+    order = np.argsort(ptile, kind="stable")
+    n_t = gx * ((H + TILE - 1) // TILE)
+    start = np.searchsorted(ptile[order], np.arange(n_t + 1))
+    # (triangle, tile) pairs
+    w_ = tx1 - tx0 + 1; area = w_ * (ty1 - ty0 + 1)
+    tri_of = np.repeat(tid, area)
+    j = np.arange(int(area.sum())) - np.repeat(np.cumsum(area) - area, area)
+    wr = np.repeat(w_, area)
+    tile = (np.repeat(ty0, area) + j // wr) * gx + np.repeat(tx0, area) + j % wr
+    cnt = start[tile + 1] - start[tile]
+    keep = cnt > 0
+    tri_of, tile, cnt = tri_of[keep], tile[keep], cnt[keep]
+    # expand to (triangle, pixel) pairs, in chunks
+    cum = np.concatenate([[0], np.cumsum(cnt)])
+    total = int(cum[-1])
+    for c0 in range(0, total, chunk):
+        c1 = min(total, c0 + chunk)
+        k = np.arange(c0, c1)
+        pr = np.searchsorted(cum, k, side="right") - 1
+        pix = order[start[tile[pr]] + (k - cum[pr])]
+        t = tri_of[pr]
+        r = _rays(cam, xs[pix].astype(np.float64), ys[pix].astype(np.float64))
+        e = E[t]                                                    # [n,3,3]
+        s = np.einsum("nkc,nc->nk", e, r)
+        eps = EDGE_K * U * np.einsum("nkc,nc->nk", np.abs(e), np.abs(r))
+        den = np.einsum("nc,nc->n", N[t], r)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            z = D[t] / den
+            g = np.einsum("nc,nc->n", np.abs(N[t]), np.abs(r)) / np.abs(den)
+        tol = REL + U * (3.0 + 5.0 * g)
+        ok = np.isfinite(z)
+        ins = (s >= 0).all(1) & ok & (z > near) & (z <= far)
+        lin = (s >= -eps).all(1) & ok & (z * (1 + tol) > near) & (z * (1 - tol) <= far)
+        sin_ = (s >= eps).all(1) & ok & (z * (1 - tol) > near) & (z * (1 + tol) <= far)
+        np.minimum.at(nom, pix[ins], z[ins])
+        np.minimum.at(lo, pix[lin], (z * (1 - tol))[lin])
+        np.minimum.at(hi, pix[sin_], (z * (1 + tol))[sin_])
+        edge[pix[lin & ~sin_]] = True
+    return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
+
+
+def check(got, ref, what=""):
+    """The per-pixel pass rule; prints the frame's edge-band count.  Returns (n_fail, n_edge)."""
+    got = np.asarray(got, np.float64).reshape(ref["nominal"].shape)
+    lo, hi = ref["lenient"], ref["strict"]
+    ok = (lo <= got) & (got <= hi)
+    n_edge = int(ref["edge"].sum())
+    bad = ~ok
+    print(f"mesh depth {what}: {got.size} px, edge band {n_edge}, failing {int(bad.sum())}, inf {int(np.isinf(got).sum())}")
+    if bad.any():
+        i = np.flatnonzero(bad.reshape(-1))[:8]
+        raise AssertionError(f"{what}: {int(bad.sum())} pixels outside [lenient, strict]; first {i.tolist()}: got "
+                             f"{got.reshape(-1)[i].tolist()} lenient {lo.reshape(-1)[i].tolist()} strict {hi.reshape(-1)[i].tolist()}")
+    return int(bad.sum()), n_edge
+
+
+def sample_pixels(width, height, n=20000, seed=0):
+    rng = np.random.default_rng(seed)
+    k = rng.choice(width * height, size=min(n, width * height), replace=False)
+    return np.divmod(k, width)
