@@ -15,6 +15,13 @@
 // share an edge compute its e from the same two fp64 vertices, in the order of their indices (lower first) and with a product that is
 // anti-commutative bit for bit (mul and sub each rounded on their own, never fused), then round it to fp32 and flip its sign exactly.
 // Both then evaluate +-the same fp32 value at every pixel, and e . r == 0 counts as inside for both: no pixel falls between them.
+// A vertex needs more: each edge plane through it is rounded to fp32 on its own, so the rounded planes no longer meet in one line, and a
+// ray within that rounding of the vertex can see every edge through it with one strict sign (no triangle of the fan would claim it).  So
+// an edge whose fp32 value is negative but within the fp32 error bound of 0 (the record's prefilter w: 8 u max_k |e_k|_1, times
+// max(1, |rx|, |ry|)) is decided again in fp64 (mesh_edge64): the same index-ordered plane, kept in fp64, passes when its value is
+// >= -2^-50 sum_i P_i |r_i|, P the plane's products — above the fp64 rounding of the plane and of its evaluation.  Planes through one
+// vertex meet in one line up to that rounding, so some triangle of every fan passes; the rule is +-symmetric across a shared edge too,
+// and it only adds pixels within rounding of an edge (tests/mesh_depth_ref.py, "Edge-exact bounds").
 #pragma once
 #include "sgs_common.h"
 
@@ -78,6 +85,14 @@ __device__ __forceinline__ MeshD3 mesh_cross_rn(const MeshD3& a, const MeshD3& b
                   __dsub_rn(__dmul_rn(a.x, b.y), __dmul_rn(a.y, b.x))};
 }
 
+// Camera-space vertex in fp64 with explicit fmas: the same vertex gives the same bits in every triangle (and kernel) that uses it.
+__device__ __forceinline__ MeshD3 mesh_vertex(const MeshFrame& F, const float* v) {
+    const double x = v[0], y = v[1], z = v[2];
+    return MeshD3{fma((double)F.view[0], x, fma((double)F.view[1], y, fma((double)F.view[2], z, (double)F.view[3]))),
+                  fma((double)F.view[4], x, fma((double)F.view[5], y, fma((double)F.view[6], z, (double)F.view[7]))),
+                  fma((double)F.view[8], x, fma((double)F.view[9], y, fma((double)F.view[10], z, (double)F.view[11])))};
+}
+
 __device__ __forceinline__ unsigned mesh_tile_of(int x, int y, const MeshFrame& F) { return (unsigned)((y - F.row_begin) * F.gx + x); }
 
 __global__ __launch_bounds__(256) void k_mesh_setup(const MeshGroup G) {
@@ -92,12 +107,7 @@ __global__ __launch_bounds__(256) void k_mesh_setup(const MeshGroup G) {
         MeshD3 p[3];
         for (int k = 0; k < 3; ++k) {
             idx[k] = G.tris[3 * t + k];
-            const float* v = G.verts + 3 * (size_t)idx[k];
-            const double x = v[0], y = v[1], z = v[2];
-            // fp64, explicit fmas: the same vertex gives the same bits in every triangle that uses it
-            p[k].x = fma((double)F.view[0], x, fma((double)F.view[1], y, fma((double)F.view[2], z, (double)F.view[3])));
-            p[k].y = fma((double)F.view[4], x, fma((double)F.view[5], y, fma((double)F.view[6], z, (double)F.view[7])));
-            p[k].z = fma((double)F.view[8], x, fma((double)F.view[9], y, fma((double)F.view[10], z, (double)F.view[11])));
+            p[k] = mesh_vertex(F, G.verts + 3 * (size_t)idx[k]);
         }
         const double nz = F.near_z, fz = F.far_z, W = F.width, H = F.height;
         const bool behind = p[0].z <= nz && p[1].z <= nz && p[2].z <= nz;
@@ -143,6 +153,7 @@ __global__ __launch_bounds__(256) void k_mesh_setup(const MeshGroup G) {
                     rect = make_uint2((unsigned)tx0 | ((unsigned)tx1 << 16), (unsigned)ty0 | ((unsigned)ty1 << 16));
                     const double sg = det > 0.0 ? 1.0 : -1.0;
                     float4* R = G.rec + 4 * slot;
+                    double l1 = 0.0;
                     for (int k = 0; k < 3; ++k) {
                         const int a = (k + 1) % 3, b = (k + 2) % 3;
                         // the edge's plane from its vertices in index order, sign flipped exactly afterwards
@@ -150,7 +161,10 @@ __global__ __launch_bounds__(256) void k_mesh_setup(const MeshGroup G) {
                         const MeshD3 e = swap ? mesh_cross_rn(p[b], p[a]) : mesh_cross_rn(p[a], p[b]);
                         const double s = swap ? -sg : sg;
                         R[k] = make_float4((float)(s * e.x), (float)(s * e.y), (float)(s * e.z), 0.f);
+                        l1 = fmax(l1, fabs(e.x) + fabs(e.y) + fabs(e.z));
                     }
+                    R[0].w = (float)(0x1p-21 * l1);         // the fp64 recheck's prefilter: 8 u max_k |e_k|_1
+
                     const MeshD3 u1{p[1].x - p[0].x, p[1].y - p[0].y, p[1].z - p[0].z}, u2{p[2].x - p[0].x, p[2].y - p[0].y, p[2].z - p[0].z};
                     const MeshD3 n{u1.y * u2.z - u1.z * u2.y, u1.z * u2.x - u1.x * u2.z, u1.x * u2.y - u1.y * u2.x};
                     R[3] = make_float4((float)n.x, (float)n.y, (float)n.z, (float)(n.x * p[0].x + n.y * p[0].y + n.z * p[0].z));
@@ -255,9 +269,37 @@ __global__ __launch_bounds__(SGS_MESH_SCAN_THREADS) void k_mesh_scan(const MeshG
     }
 }
 
+// The inside test of triangle t at ray (rx, ry, 1) when its fp32 edge values s[] are not all >= 0 but within rounding of 0 (header):
+// every edge with s < 0 is decided again from its fp64 plane, built exactly as k_mesh_setup builds it before rounding.
+__device__ __forceinline__ bool mesh_inside64(const MeshGroup& G, const MeshFrame& F, unsigned t, const float4* e32, const float* s, float rx,
+                                           float ry) {
+    int idx[3];
+    MeshD3 p[3];
+    for (int k = 0; k < 3; ++k) {
+        idx[k] = G.tris[3 * (size_t)t + k];
+        p[k] = mesh_vertex(F, G.verts + 3 * (size_t)idx[k]);
+    }
+    const double x = rx, y = ry, ax = fabs(x), ay = fabs(y);
+    for (int k = 0; k < 3; ++k) {
+        if (s[k] >= 0.f) continue;
+        const int a = (k + 1) % 3, b = (k + 2) % 3;
+        const bool swap = idx[a] > idx[b];
+        const MeshD3& u = swap ? p[b] : p[a];
+        const MeshD3& v = swap ? p[a] : p[b];
+        const MeshD3 e = mesh_cross_rn(u, v);
+        // the record holds this plane times +-1, rounded: its sign is the sign of their dot product
+        const double sg = (double)e32[k].x * e.x + (double)e32[k].y * e.y + (double)e32[k].z * e.z >= 0.0 ? 1.0 : -1.0;
+        const double g = fma(sg * e.x, x, fma(sg * e.y, y, sg * e.z));
+        const double Px = fabs(u.y * v.z) + fabs(u.z * v.y), Py = fabs(u.z * v.x) + fabs(u.x * v.z), Pz = fabs(u.x * v.y) + fabs(u.y * v.x);
+        if (!(g >= -0x1p-50 * fma(Px, ax, fma(Py, ay, Pz)))) return false;
+    }
+    return true;
+}
+
 // One workgroup per tile of the band, one pixel per lane.
 __global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
     __shared__ float4 s_rec[4][256];
+    __shared__ unsigned s_id[256];
     const int f = blockIdx.y;
     const MeshFrame& F = G.f[f];
     unsigned long long total = 0, base = 0;
@@ -269,13 +311,16 @@ __global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
     const int px = (int)(tile % (unsigned)F.gx) * SGS_TILE_PX + (int)(threadIdx.x & 15);
     const int py = (F.row_begin + (int)(tile / (unsigned)F.gx)) * SGS_TILE_PX + (int)(threadIdx.x >> 4);
     const float rx = ((float)px + 0.5f - F.cx) / F.fx, ry = ((float)py + 0.5f - F.cy) / F.fy;
+    const float rmax = fmaxf(1.f, fmaxf(fabsf(rx), fabsf(ry)));
     const float near_z = F.near_z, far_z = F.far_z;
     const float4* rec = G.rec + 4 * (size_t)f * (size_t)G.n_tris;
     float best = __uint_as_float(0x7f800000u);
     for (unsigned long long b = begin; b < end; b += 256) {
         const int n = end - b < 256ull ? (int)(end - b) : 256;
         if ((int)threadIdx.x < n) {
-            const float4* R = rec + 4 * (size_t)G.list[b + threadIdx.x];
+            const unsigned id = G.list[b + threadIdx.x];
+            const float4* R = rec + 4 * (size_t)id;
+            s_id[threadIdx.x] = id;
             s_rec[0][threadIdx.x] = R[0]; s_rec[1][threadIdx.x] = R[1]; s_rec[2][threadIdx.x] = R[2]; s_rec[3][threadIdx.x] = R[3];
         }
         __syncthreads();
@@ -284,7 +329,13 @@ __global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
             const float s0 = fmaf(e0.x, rx, fmaf(e0.y, ry, e0.z));
             const float s1 = fmaf(e1.x, rx, fmaf(e1.y, ry, e1.z));
             const float s2 = fmaf(e2.x, rx, fmaf(e2.y, ry, e2.z));
-            if (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f) {
+            bool in = s0 >= 0.f && s1 >= 0.f && s2 >= 0.f;
+            if (!in && fmaf(e0.w, rmax, fminf(s0, fminf(s1, s2))) >= 0.f) {         // within rounding of an edge: fp64 (header)
+                const float4 e[3] = {e0, e1, e2};
+                const float sv[3] = {s0, s1, s2};
+                in = mesh_inside64(G, F, s_id[k], e, sv, rx, ry);
+            }
+            if (in) {
                 const float4 pl = s_rec[3][k];
                 const float z = pl.w / fmaf(pl.x, rx, fmaf(pl.y, ry, pl.z));
                 if (z > near_z && z <= far_z) best = fminf(best, z);

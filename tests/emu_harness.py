@@ -1,6 +1,6 @@
 """Builds and drives the product's kernels under the wave64 emulator (tests/hipemu) — CPU tests only.
 
-The emulated library is the product's own csrc/sgs_api.hip + csrc/sgs_kernels.h compiled by g++
+The emulated library is the product's own csrc/sgs_api.hip (+ the kernel headers it includes) compiled by g++
 against tests/hipemu/hip/hip_runtime.h.  It exists so that `-m "not gpu"` tests can check the kernel
 LOGIC (compaction, duplication, radix sort, composite) against the oracle; it is never the thing
 measured or shipped, and the product package cannot load it.
@@ -18,7 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "sage-3d_official_amd")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 EMU_LIB = os.path.join(EMU_DIR, "_build", "libsage_gs_emu.so")
-SRCS = [os.path.join(PKG, "csrc", n) for n in ("sgs_api.hip", "sgs_kernels.h", "sgs_common.h")] + \
+KERNEL_SRCS = ("sgs_api.hip", "sgs_kernels.h", "sgs_mesh.h", "sgs_common.h")        # csrc/ files the library is built from
+SRCS = [os.path.join(PKG, "csrc", n) for n in KERNEL_SRCS] + \
        [os.path.join(EMU_DIR, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "sage_gs.h")]
 
 if PKG not in sys.path:
@@ -32,7 +33,7 @@ def build_emu(force=False, src_dir=None, out=None, wait=True):
     its Popen (None when the library is up to date); the caller waits."""
     csrc = os.path.join(PKG, "csrc") if src_dir is None else str(src_dir)
     lib_out = EMU_LIB if out is None else str(out)
-    srcs = [os.path.join(csrc, n) for n in ("sgs_api.hip", "sgs_kernels.h", "sgs_common.h")] + SRCS[3:]
+    srcs = [os.path.join(csrc, n) for n in KERNEL_SRCS] + SRCS[len(KERNEL_SRCS):]
     os.makedirs(os.path.dirname(lib_out), exist_ok=True)
     stale = force or not os.path.exists(lib_out) or any(
         os.path.getmtime(s) > os.path.getmtime(lib_out) for s in srcs)

@@ -21,6 +21,26 @@ The depth z = d / (n . r) goes through the same steps (n, d rounded to fp32: 1 u
 for the division), so its relative error is at most u (2 + 4 G) with G = sum_i |n_i r_i| / |n . r| — G is ~1 for a surface seen face
 on and grows as 1 / sin(angle) for grazing ones.  The per-candidate tolerance is tol = 1e-5 + u (3 + 5 G): the 1e-5 of the pass rule
 plus the derived term, which only matters for rays within a few degrees of a triangle's plane.
+
+Edge-exact bounds (cast_continuous / check_continuous).  The edge band above is where `check` cannot see a crack: there `strict` is the
+next surface behind, or +inf.  The kernels promise more (csrc/sgs_mesh.h): the two triangles of a shared edge build its plane from the
+same two fp64 vertices in index order, with a product that is anti-commutative bit for bit, round it to fp32 and flip its sign exactly,
+so they evaluate +-the same fp32 value at every pixel, and "e . r >= 0" makes one of them claim it.  Around a vertex the rounded
+planes no longer meet in one line; the kernels decide an edge within fp32 rounding of 0 again from its fp64 plane with a margin above
+the fp64 rounding (sgs_mesh.h header), and the fp64 planes through a vertex meet in one line up to that margin, so some triangle of the
+fan claims the pixel.  Both rules only ever add a triangle whose exact edge values are >= -eps_k.  So for a mesh whose depth field
+is continuous across its shared edges and that every ray meets once (a coplanar sheet; a closed box seen from inside):
+  claimable   a triangle is a candidate of a pixel when its three edge functions are >= -eps_k and its z is inside (near, far] up to tol:
+              exactly the `lenient` candidates above.  A triangle whose fp32 test passes is one of them (the eps_k derivation).
+  value       the kernel returns the z of a claiming triangle, so a finite value lies in [min z (1 - tol), max z (1 + tol)] over the
+              candidates.  On a sheet the candidates share the plane (up to the fp32 rounding of the vertices: a relative 2^-24, inside
+              REL), so this is d / (n . r) within REL + u (3 + 5 G) — the tolerance above, with no edge band.  On the box's seams, where two
+              faces that are not coplanar meet, the candidates are the two faces: either face's depth, within the same tolerance.
+  need        the pixel must be finite when some candidate passes every edge either outright (s_k >= eps_k) or because the edge is shared
+              (s_k >= -eps_k: the neighbour across it takes the pixel if this one does not), with z inside (near, far] by tol.
+  outline     except within eps_k of an edge that no other triangle shares (the sheet's own boundary): such a pixel may be +inf or the
+              surface, as in `check`.  The closed box has no such edge: every pixel of it is needed, vertices included.
+No allowance beyond the module's eps_k and tol enters: the promise is exact, and the rounding it leaves is that of one triangle's value.
 """
 from __future__ import annotations
 
@@ -61,10 +81,26 @@ def cast(vertices, triangles, cam, near=0.2, far=1.0e30, pixels=None, chunk=1 <<
         shape = (len(ys),)
     P = len(ys)
     nom = np.full(P, np.inf); lo = np.full(P, np.inf); hi = np.full(P, np.inf); edge = np.zeros(P, bool)
+    if len(np.asarray(triangles).reshape(-1, 3)) == 0 or P == 0:
+        return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
+    for pix, t, s, eps, z, tol in _candidates(vertices, triangles, cam, near, xs, ys, chunk):
+        ok = np.isfinite(z)
+        ins = (s >= 0).all(1) & ok & (z > near) & (z <= far)
+        lin = (s >= -eps).all(1) & ok & (z * (1 + tol) > near) & (z * (1 - tol) <= far)
+        sin_ = (s >= eps).all(1) & ok & (z * (1 - tol) > near) & (z * (1 + tol) <= far)
+        np.minimum.at(nom, pix[ins], z[ins])
+        np.minimum.at(lo, pix[lin], (z * (1 - tol))[lin])
+        np.minimum.at(hi, pix[sin_], (z * (1 + tol))[sin_])
+        edge[pix[lin & ~sin_]] = True
+    return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
+
+
+def _candidates(vertices, triangles, cam, near, xs, ys, chunk):
+    """The (triangle, pixel) pairs of the conservative pixel rects, in chunks: (pixel index into xs / ys, triangle, s [n,3] = the
+    edge functions sign(det) e_k . r, eps [n,3], z = d / (n . r), tol).  Triangles with det == 0 have none."""
+    W, H = cam["width"], cam["height"]
     V = np.asarray(vertices, np.float32).astype(np.float64)
     T = np.asarray(triangles, np.int64).reshape(-1, 3)
-    if len(T) == 0 or P == 0:
-        return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
     M = cam["view"]
     Pc = V @ M[:3, :3].T + M[:3, 3]
     p0, p1, p2 = Pc[T[:, 0]], Pc[T[:, 1]], Pc[T[:, 2]]
@@ -132,16 +168,7 @@ def cast(vertices, triangles, cam, near=0.2, far=1.0e30, pixels=None, chunk=1 <<
         with np.errstate(divide="ignore", invalid="ignore"):
             z = D[t] / den
             g = np.einsum("nc,nc->n", np.abs(N[t]), np.abs(r)) / np.abs(den)
-        tol = REL + U * (3.0 + 5.0 * g)
-        ok = np.isfinite(z)
-        ins = (s >= 0).all(1) & ok & (z > near) & (z <= far)
-        lin = (s >= -eps).all(1) & ok & (z * (1 + tol) > near) & (z * (1 - tol) <= far)
-        sin_ = (s >= eps).all(1) & ok & (z * (1 - tol) > near) & (z * (1 + tol) <= far)
-        np.minimum.at(nom, pix[ins], z[ins])
-        np.minimum.at(lo, pix[lin], (z * (1 - tol))[lin])
-        np.minimum.at(hi, pix[sin_], (z * (1 + tol))[sin_])
-        edge[pix[lin & ~sin_]] = True
-    return dict(nominal=nom.reshape(shape), lenient=lo.reshape(shape), strict=hi.reshape(shape), edge=edge.reshape(shape))
+        yield pix, t, s, eps, z, REL + U * (3.0 + 5.0 * g)
 
 
 def check(got, ref, what=""):
@@ -163,3 +190,69 @@ def sample_pixels(width, height, n=20000, seed=0):
     rng = np.random.default_rng(seed)
     k = rng.choice(width * height, size=min(n, width * height), replace=False)
     return np.divmod(k, width)
+
+
+def _shared_edges(triangles):
+    """[F,3] bool: edge k of a triangle (the one opposite vertex k, as in E above) is shared with another triangle."""
+    T = np.asarray(triangles, np.int64).reshape(-1, 3)
+    ab = np.stack([np.stack([T[:, 1], T[:, 2]], 1), np.stack([T[:, 2], T[:, 0]], 1), np.stack([T[:, 0], T[:, 1]], 1)], 1)   # [F,3,2]
+    key = np.sort(ab, axis=2).reshape(-1, 2)
+    _, inv, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
+    return (cnt[inv.reshape(-1)] >= 2).reshape(-1, 3) & (key[:, 0] != key[:, 1]).reshape(-1, 3)
+
+
+def cast_continuous(vertices, triangles, cam, near=0.2, far=1.0e30, pixels=None, chunk=1 << 21):
+    """The edge-exact bounds of a mesh whose depth field is continuous across every shared edge and that the rays meet once (a coplanar
+    sheet; a closed convex box seen from inside).  See "Edge-exact bounds" in the module header.  Returns dict(lo, hi, need, outline,
+    shared_band, zeros, vertex): float64 lo / hi and bool masks, [H,W] (or [P]).  vertex: pixels within eps of two edges of one candidate
+    (a vertex; counted for the report, not exempt)."""
+    W, H = cam["width"], cam["height"]
+    if pixels is None:
+        ys, xs = np.divmod(np.arange(W * H), W)
+        shape = (H, W)
+    else:
+        ys, xs = (np.asarray(a, np.int64) for a in pixels)
+        shape = (len(ys),)
+    P = len(ys)
+    lo = np.full(P, np.inf); hi = np.full(P, -np.inf)
+    need = np.zeros(P, bool); outline = np.zeros(P, bool); band = np.zeros(P, bool); zeros = np.zeros(P, bool); vert = np.zeros(P, bool)
+    shared = _shared_edges(triangles)
+    if len(shared) and P:
+        for pix, t, s, eps, z, tol in _candidates(vertices, triangles, cam, near, xs, ys, chunk):
+            ok = np.isfinite(z)
+            sh = shared[t]
+            within = (s >= -eps).all(1)
+            lin = within & ok & (z * (1 + tol) > near) & (z * (1 - tol) <= far)
+            hit = ((s >= eps) | (sh & (s >= -eps))).all(1) & ok & (z * (1 - tol) > near) & (z * (1 + tol) <= far)
+            near_edge = within[:, None] & (np.abs(s) < eps)
+            np.minimum.at(lo, pix[lin], (z * (1 - tol))[lin])
+            np.maximum.at(hi, pix[lin], (z * (1 + tol))[lin])
+            need[pix[hit]] = True
+            outline[pix[(near_edge & ~sh).any(1)]] = True
+            band[pix[(near_edge & sh).any(1) & lin]] = True
+            zeros[pix[within & (s == 0).any(1)]] = True
+            vert[pix[near_edge.sum(1) >= 2]] = True
+    need &= ~outline
+    return dict(lo=lo.reshape(shape), hi=hi.reshape(shape), need=need.reshape(shape), outline=outline.reshape(shape),
+                shared_band=band.reshape(shape), zeros=zeros.reshape(shape), vertex=vert.reshape(shape))
+
+
+def check_continuous(got, cc, what=""):
+    """The edge-exact pass rule (cast_continuous): a finite value lies in [lo, hi]; +inf is allowed only where no pixel is `need`ed; a
+    pixel no triangle can claim is +inf.  Prints the counts; returns dict(n_px, shared_band, outline, zeros, need)."""
+    got = np.asarray(got, np.float64).reshape(cc["lo"].shape)
+    lo, hi, need = cc["lo"], cc["hi"], cc["need"]
+    fin = np.isfinite(got)
+    ok = np.where(fin, (lo <= got) & (got <= hi), (got == np.inf) & ~need)
+    n = dict(n_px=int(got.size), shared_band=int(cc["shared_band"].sum()), outline=int(cc["outline"].sum()), zeros=int(cc["zeros"].sum()),
+             need=int(need.sum()), vertex=int(cc["vertex"].sum()))
+    bad = ~ok
+    print(f"mesh depth (edge-exact) {what}: {n['n_px']} px, need {n['need']}, shared-edge band {n['shared_band']} (exact zeros "
+          f"{n['zeros']}), outline band {n['outline']}, vertex band {n['vertex']}, failing {int(bad.sum())}, inf {int((~fin).sum())}")
+    if bad.any():
+        i = np.flatnonzero(bad.reshape(-1))[:8]
+        raise AssertionError(f"{what} (edge-exact): {int(bad.sum())} pixels fail, {int((bad & ~fin & need).sum())} of them +inf where a "
+                             f"triangle must claim the pixel; first {i.tolist()}: got {got.reshape(-1)[i].tolist()} lo "
+                             f"{lo.reshape(-1)[i].tolist()} hi {hi.reshape(-1)[i].tolist()} shared-edge band "
+                             f"{cc['shared_band'].reshape(-1)[i].tolist()}")
+    return n

@@ -1,6 +1,5 @@
 """Collision-mesh depth (sgs_render_mesh_depth*) under the wave64 emulator: the product's kernels (csrc/sgs_mesh.h) against the fp64
 ray caster of tests/mesh_depth_ref.py, the ABI's refusals, and the USDA mesh reader.  CPU only."""
-import ctypes as C
 import json
 import math
 import os
@@ -10,6 +9,7 @@ import pytest
 
 import emu_harness as eh
 import mesh_depth_ref as ref
+import mesh_edge_cases as mc
 from sage_gs import _capi, scenes
 from sage_gs import mesh as mesh_io
 
@@ -18,58 +18,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 @pytest.fixture(scope="module")
 def lib():
-    # emu_harness checks only sgs_api.hip / sgs_kernels.h / sgs_common.h for staleness: rebuild when the mesh kernels are newer
-    mesh_h = os.path.join(eh.PKG, "csrc", "sgs_mesh.h")
-    force = os.path.exists(eh.EMU_LIB) and os.path.getmtime(mesh_h) > os.path.getmtime(eh.EMU_LIB)
-    eh.build_emu(force=force)
     return eh.lib()
 
 
-class Emu:
-    def __init__(self, lib):
-        self.lib = lib
-        self.ctx = C.c_void_p()
-        lib.check(lib.sgs_create(0, _capi.BACKEND_HIP, C.byref(self.ctx)))
-
-    def upload(self, V, T):
-        v = np.ascontiguousarray(V, np.float32); t = np.ascontiguousarray(T, np.int32)
-        h = C.c_void_p()
-        rc = self.lib.sgs_mesh_upload(self.ctx, len(v), v.ctypes.data if len(v) else None, len(t), t.ctypes.data if len(t) else None,
-                                      0, C.byref(h))
-        return rc, h
-
-    def mesh(self, V, T):
-        rc, h = self.upload(V, T)
-        self.lib.check(rc, self.ctx)
-        return h
-
-    def cfg(self, near=0.2, far=1e30, flags=0, stride=1):
-        k = self.lib.default_config()
-        k.near_z, k.far_z, k.flags, k.tile_row_stride = near, far, flags, stride
-        return k
-
-    def render(self, m, cam, rows=(0, -1), cfg=None, fill=-1.0):
-        c = _capi.make_camera(cam["width"], cam["height"], cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["view"].tolist())
-        out = np.full((cam["height"], cam["width"]), fill, np.float32)
-        st = _capi.SgsStats()
-        rc = self.lib.sgs_render_mesh_depth(self.ctx, m, C.byref(c), C.byref(cfg or self.cfg()), rows[0], rows[1], out.ctypes.data,
-                                            C.byref(st), None)
-        return rc, out, st.as_dict()
-
-    def batch(self, m, cams, cfg=None):
-        arr = (_capi.SgsCamera * len(cams))(*[_capi.make_camera(c["width"], c["height"], c["fx"], c["fy"], c["cx"], c["cy"],
-                                                                 c["view"].tolist()) for c in cams])
-        out = np.zeros((len(cams), cams[0]["height"], cams[0]["width"]), np.float32)
-        st = (_capi.SgsStats * len(cams))()
-        self.lib.check(self.lib.sgs_render_mesh_depth_batch(self.ctx, m, arr, len(cams), C.byref(cfg or self.cfg()), out.ctypes.data, st,
-                                                            None), self.ctx)
-        return out, [s.as_dict() for s in st]
-
-    def err(self):
-        return self.lib.sgs_last_error(self.ctx).decode()
-
-    def close(self):
-        self.lib.sgs_destroy(self.ctx)
+Emu = mc.EmuMesh
 
 
 @pytest.fixture

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import mesh_depth_ref as ref
+import mesh_edge_cases as mc
 
 pytestmark = pytest.mark.gpu
 
@@ -86,6 +87,10 @@ def test_watertight_room_and_icosphere(r):
         cams.append(Camera(640, 480, fx, fy, cx, cy, scenes.view_from_yaw(pos, rng.uniform(0, 2 * math.pi), rng.uniform(-1.2, 1.2))))
     got = r.render_mesh_depth_batch(cams, m).cpu().numpy()
     assert int(np.isinf(got).sum()) == 0, [int(np.isinf(g).sum()) for g in got]
+    for k in (0, 16):                      # the room is a grid_box: every pixel against the edge-exact bounds, seams included
+        cc = ref.cast_continuous(V, T, ref.of_camera(cams[k]), near=0.2)
+        ref.check_continuous(got[k], cc, f"closed room pose {k}")
+        assert cc["need"].all()
     Vs, Ts = scenes.icosphere(6, (0.0, 0.0, 0.0), 1.0)
     assert 70_000 < len(Ts) < 90_000
     ms = r.upload_mesh(Vs, Ts)
@@ -216,3 +221,61 @@ def test_gs_camera_and_isaac_shim_collision_depth(r, tmp_path):
         isaac_shim._state["stage"] = None
         isaac_shim._state["renderer"] = None
     mesh.free(); scene.free()
+
+
+@pytest.fixture(scope="module")
+def gdrv(r):
+    return mc.GpuMesh(r)
+
+
+@pytest.mark.parametrize("name", list(mc.EDGE_CASES))
+@pytest.mark.parametrize("w,h", [(640, 480), (1920, 1080)])
+def test_edge_cases_alone_and_batched(gdrv, name, w, h):
+    """tests/mesh_edge_cases.py's edge-aligned meshes: alone (every pixel at 640x480, 30k sampled at 1920x1080 — partial tiles), then in
+    a batch of 12 (groups of 8 + 4) whose first and last frames use the case's own camera (bit for bit the single frame) and whose
+    others are slightly moved (two of them checked on sampled pixels)."""
+    if w == 640:
+        case, single, n = mc.check_edge_case(gdrv, name, w, h, seed=w)
+    else:
+        case = mc.EDGE_CASES[name](w, h, w)
+        single, _ = gdrv.frame(case["V"], case["T"], case["cam"])
+        assert not np.isnan(single).any()
+        ys, xs = ref.sample_pixels(w, h, 30000, seed=1)
+        n = mc.check_frame(single[ys, xs], case, pixels=(ys, xs), what=case["name"] + " (sampled)")
+    print(f"[edges] {case['name']}: {len(case['T'])} triangles, {n}")
+    rng = np.random.default_rng(w)
+    cams = [case["cam"]] + [mc.nudged(case["cam"], rng) for _ in range(10)] + [case["cam"]]
+    got, st = gdrv.frames(case["V"], case["T"], cams)
+    assert np.array_equal(got[0], single) and np.array_equal(got[11], single)
+    for k in (3, 9):
+        ys, xs = ref.sample_pixels(w, h, 20000, seed=k)
+        mc.check_frame(got[k][ys, xs], case, cam=cams[k], pixels=(ys, xs), what=f"{case['name']} batch frame {k} (sampled)")
+
+
+def test_room_far_plane(r, room, room_mesh):
+    from sage_gs import RenderConfig
+    cams = _cams(room, 640, 480, n=4, seed=31)
+    got = r.render_mesh_depth_batch(cams, room_mesh, config=RenderConfig(far=3.0)).cpu().numpy()
+    for k, c in enumerate(cams):
+        ref.check(got[k], ref.cast(room.vertices, room.triangles, ref.of_camera(c), near=0.2, far=3.0), f"room 50k far 3 pose {k}")
+        assert (got[k][np.isfinite(got[k])] <= 3.0).all()
+    assert np.isinf(got).sum() > 10000 and np.isfinite(got).sum() > 10000
+
+
+def test_near_far_exact_and_straddling(gdrv):
+    mc.case_near_far_exact(gdrv)
+    mc.case_far_straddle(gdrv)
+
+
+def test_degenerate_and_culled_triangles(gdrv, room):
+    c = _cams(room, 640, 480, n=4, seed=41)[1]
+    mc.case_collinear_exact(gdrv)
+    want = mc.case_degenerate(gdrv, (room.vertices, room.triangles), ref.of_camera(c))
+    ys, xs = ref.sample_pixels(640, 480, 20000, seed=5)
+    ref.check(want[ys, xs], ref.cast(room.vertices, room.triangles, ref.of_camera(c), near=0.2, far=20.0, pixels=(ys, xs)),
+              "room 50k far 20 (sampled)")
+
+
+def test_more_than_1024_tiles(gdrv):
+    st = mc.case_many_tiles(gdrv)
+    print(f"[tiles] 528x528: {st['n_tiles']} tiles, {st['d_total']} records, longest list {st['max_tile_len']}")
