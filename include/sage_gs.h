@@ -243,7 +243,10 @@ int sgs_render(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, cons
 /* As sgs_render, plus out_aux: a DEVICE buffer of height*width*2 floats — per pixel the expected view
  * depth sum_i T_i alpha_i z_i (metres along the optical axis) and the coverage 1 - T_final.  This is the
  * natural Gaussian-scene counterpart of the reference's depth channel, which renders the depth of the
- * collision mesh instead (simple_env.py:1395-1589: get_depth, clipped to [0.1, 6.5] m). */
+ * collision mesh instead (simple_env.py:1395-1589: get_depth, clipped to [0.1, 6.5] m).
+ * out_aux is always the FULL frame's buffer: a band [tile_row_begin, tile_row_end) writes its own pixel rows of it and leaves the
+ * others alone, as in out_rgb.  There is no compact form: out_aux != NULL with cfg->tile_row_stride > 1 is refused with
+ * SGS_ERR_INVALID (render the interleaved rows' colours with sgs_render; depth / coverage by bands). */
 int sgs_render_rgbd(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const sgs_config* cfg,
                     int tile_row_begin, int tile_row_end, float* out_rgb, float* out_aux,
                     sgs_stats* stats, void* hip_stream);

@@ -1115,6 +1115,9 @@ int sgs_render_rgbd(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam,
     if (!ctx) return SGS_ERR_INVALID;
     int rc;
     int z = 0;                                       // the frame's fine-tile shift (fine_shift_of)
+    // out_aux is a full-frame buffer (sage_gs.h): the compact image of interleaved rows has no depth / coverage counterpart
+    if (out_aux && cfg_in && cfg_in->tile_row_stride > 1)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "out_aux with interleaved tile rows (tile_row_stride %d) is not supported", cfg_in->tile_row_stride);
     if ((rc = validate(ctx, scene, cam, cfg_in, tile_row_begin, tile_row_end, out_rgb, &z)) != SGS_OK) return rc;
     sgs_config cfg;
     if (cfg_in) cfg = *cfg_in; else sgs_config_default(&cfg);

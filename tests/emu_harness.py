@@ -96,6 +96,18 @@ class EmuRenderer:
         """float [N, K, 3] of the scene's SH coefficients as the projection kernel evaluates them (after one frame)."""
         return self.debug(_capi.BUF_SCENE_SH, np.float32).reshape(self.n, -1, 3)
 
+    def _config(self, cfg, flags):
+        """sgs_config of an oracle_np.Config (None: the library's defaults) with `flags`."""
+        k = self.lib.default_config()
+        if cfg is not None:
+            k.near_z, k.far_z, k.dilation, k.clamp = cfg.near, cfg.far, cfg.dilation, cfg.clamp
+            k.alpha_min, k.alpha_max, k.t_min = cfg.alpha_min, cfg.alpha_max, cfg.t_min
+            for i in range(3):
+                k.bg[i] = cfg.background[i]
+            k.sh_degree = cfg.sh_degree
+        k.flags = flags
+        return k
+
     def render(self, cam, cfg=None, rows=(0, -1), out=None, flags=0, full_sort=False, loose_cull=False, interleave=None,
                chunk_cull=True, stats=True, deep=True, fine=True):
         flags |= 0 if chunk_cull else _capi.FLAG_NO_CHUNK_CULL
@@ -106,14 +118,7 @@ class EmuRenderer:
         flags |= _capi.FLAG_LOOSE_CULL if loose_cull else 0
         c = _capi.make_camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy,
                               np.asarray(cam.view, np.float32).reshape(4, 4).tolist())
-        k = self.lib.default_config()
-        if cfg is not None:
-            k.near_z, k.far_z, k.dilation, k.clamp = cfg.near, cfg.far, cfg.dilation, cfg.clamp
-            k.alpha_min, k.alpha_max, k.t_min = cfg.alpha_min, cfg.alpha_max, cfg.t_min
-            for i in range(3):
-                k.bg[i] = cfg.background[i]
-            k.sh_degree = cfg.sh_degree
-        k.flags = flags
+        k = self._config(cfg, flags)
         if interleave is not None:         # (stride, phase): compact image of the owned tile rows
             k.tile_row_stride, k.tile_row_phase = interleave
             owned = len(range(interleave[1], (cam.height + 15) // 16, interleave[0]))
@@ -125,27 +130,41 @@ class EmuRenderer:
                                            out.ctypes.data, C.byref(st), None), self.ctx)
         return out, st.as_dict()
 
-    def render_batch(self, cams, fine=True):
+    def render_batch(self, cams, fine=True, cfg=None):
         """sgs_render_batch: the frames of `cams` (one resolution) as frame groups; [n, H, W, 3]."""
         arr = (_capi.SgsCamera * len(cams))(*[_capi.make_camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy,
                                                                 np.asarray(c.view, np.float32).reshape(4, 4).tolist()) for c in cams])
-        k = self.lib.default_config()
-        k.flags = 0 if fine else _capi.FLAG_NO_FINE_TILES
+        k = self._config(cfg, 0 if fine else _capi.FLAG_NO_FINE_TILES)
         out = np.zeros((len(cams), cams[0].height, cams[0].width, 3), np.float32)
         self.lib.check(self.lib.sgs_render_batch(self.ctx, self.scene, arr, len(cams), C.byref(k), 0, -1, out.ctypes.data, None, None), self.ctx)
         return out
 
-    def render_aux(self, cam, cfg=None, fine=True):
+    def render_aux(self, cam, cfg=None, rows=(0, -1), fine=True, deep=True, stats=False, out=None, out_aux=None, flags=0):
+        """sgs_render_rgbd: (rgb [H, W, 3], aux [H, W, 2] = expected depth and coverage, stats).  `out` / `out_aux`: pre-filled buffers
+        (a band of tile rows leaves the other rows alone).  flags: more SGS_FLAG_* bits (SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED: the
+        buffers are complete after sgs_frame_sync, the stats returned here are not filled in)."""
+        flags |= 0 if fine else _capi.FLAG_NO_FINE_TILES
+        flags |= 0 if deep else _capi.FLAG_NO_DEEP
+        flags |= _capi.FLAG_STATS if stats else 0
         c = _capi.make_camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy,
                               np.asarray(cam.view, np.float32).reshape(4, 4).tolist())
-        k = self.lib.default_config()
-        k.flags = 0 if fine else _capi.FLAG_NO_FINE_TILES
-        out = np.zeros((cam.height, cam.width, 3), np.float32)
-        aux = np.zeros((cam.height, cam.width, 2), np.float32)
+        k = self._config(cfg, flags)
+        if out is None:
+            out = np.zeros((cam.height, cam.width, 3), np.float32)
+        if out_aux is None:
+            out_aux = np.zeros((cam.height, cam.width, 2), np.float32)
+        assert out.dtype == np.float32 and out.shape == (cam.height, cam.width, 3) and out.flags.c_contiguous
+        assert out_aux.dtype == np.float32 and out_aux.shape == (cam.height, cam.width, 2) and out_aux.flags.c_contiguous
         st = _capi.SgsStats()
-        self.lib.check(self.lib.sgs_render_rgbd(self.ctx, self.scene, C.byref(c), C.byref(k), 0, -1, out.ctypes.data,
-                                                aux.ctypes.data, C.byref(st), None), self.ctx)
-        return out, aux
+        self.lib.check(self.lib.sgs_render_rgbd(self.ctx, self.scene, C.byref(c), C.byref(k), rows[0], rows[1], out.ctypes.data,
+                                                out_aux.ctypes.data, C.byref(st), None), self.ctx)
+        return out, out_aux, st.as_dict()
+
+    def sync(self):
+        """sgs_frame_sync: completes the frames issued with SGS_FLAG_ASYNC; the statistics of the last one."""
+        st = _capi.SgsStats()
+        self.lib.check(self.lib.sgs_frame_sync(self.ctx, C.byref(st)), self.ctx)
+        return st.as_dict()
 
     def set_record_capacity(self, n):
         self.lib.check(self.lib.sgs_set_record_capacity(self.ctx, int(n)), self.ctx)

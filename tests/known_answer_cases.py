@@ -2,7 +2,7 @@
 
 The same analytic cases that pin the oracle (tests/test_oracle_known_answers.py), restated for a driver of the
 product: `upload(*scene)`, `render(cam, cfg, rows, full_sort=, loose_cull=) -> (image, stats)`,
-`render_aux(cam) -> (image, aux[H,W,2])`, `intermediates()`.  tests/test_emu_parity.py runs them on the CPU (the
+`render_aux(cam, cfg, rows, ...) -> (image, aux[H,W,2], stats)`, `intermediates()`.  tests/test_emu_parity.py runs them on the CPU (the
 product's kernel source under the wave64 emulator), tests/test_gpu_parity.py on the MI355X through the C ABI.
 The composite is fp32 on the device, so pixel tolerances are a few fp32 ulps of O(1) values.
 """
@@ -92,7 +92,7 @@ def case_transmittance_termination(drv):
     col = 0.5 + C0 * 1.0
     assert np.allclose(img[32, 32], col * (0.95 + 0.05 * 0.95 + 0.0025 * 0.95), atol=TOL)
     drv.upload(*scene)
-    _, aux = drv.render_aux(_cam())
+    _, aux, _ = drv.render_aux(_cam())
     assert abs((1.0 - float(aux[32, 32, 1])) - 1.25e-4) < 2e-7               # coverage = 1 - T at the stop
     z = np.array([2.0, 2.1, 2.2])
     w = np.array([0.95, 0.05 * 0.95, 0.0025 * 0.95])

@@ -2,17 +2,20 @@
 kernel LOGIC) and on a real MI355X through the C ABI (test_gpu_parity.py, the parity tests proper).
 
 A `drv` offers: upload(means, scales, quats, opac, sh, deg); render(cam, cfg=None, rows=(0,-1))
--> (image ndarray, stats dict); intermediates() -> (tile_offsets, sorted ids, slot ids, splat words).
+-> (image ndarray, stats dict); render_aux(cam, cfg=None, rows=(0,-1), fine=True, deep=True, stats=False, out=None, out_aux=None)
+-> (image, aux [H, W, 2] = expected depth and coverage, stats dict); intermediates() -> (tile_offsets, sorted ids, slot ids, splat words).
 Cameras/configs are oracle_np.Camera / oracle_np.Config objects.
 """
+import dataclasses
 import math
+import time
 
 import numpy as np
 
 import oracle_c
 import oracle_np as onp
 from conftest import assert_frame_close
-from tight_parity import assert_depth_coverage_tight, assert_frame_tight
+from tight_parity import assert_aux_tilings_agree, assert_depth_coverage_tight, assert_frame_tight
 
 
 def random_scene(n, seed, deg=0, box=((-2, 2), (-2, 2), (2, 8)), scale=(0.02, 0.2), opac_mu=0.0):
@@ -177,6 +180,130 @@ def check_against_oracle(drv, scene, cam, cfg=None, rows=(0, -1), what="", queue
     return img, st, aux, worst
 
 
+BG = (0.25, 0.5, 0.75)        # the background of the variant checks, unless a case says otherwise
+SENTINEL = -7.0               # what band renders are pre-filled with: no pixel, depth or coverage is ever negative
+MAX_SKIPPED = 0.05            # the share of a frame the depth / coverage budget may leave to the flat checks (pixels near a threshold)
+
+
+def with_background(cfg, bg):
+    """`cfg` (None: the defaults) with another background."""
+    return dataclasses.replace(onp.Config() if cfg is None else cfg, background=tuple(float(v) for v in bg))
+
+
+def _aux_against_oracle(aux, o, what):
+    """The depth / coverage outputs against the oracle's frame `o` (black background or not: neither depends on it): the flat checks
+    (1e-3 of the frame's largest depth, 1e-3 of coverage, off-threshold pixels) and tight_parity's budget, which may leave at most
+    MAX_SKIPPED of the frame to the flat checks."""
+    assert np.isfinite(aux).all(), f"{what}: non-finite depth / coverage"
+    safe = o["margin"] >= 1e-4
+    zmax = max(1.0, float(np.max(o["depth_image"], initial=0.0)))
+    if safe.any():
+        assert np.abs(aux[..., 0] - o["depth_image"])[safe].max() < 1e-3 * zmax, f"{what}: depth"
+        assert np.abs(aux[..., 1] - (1.0 - o["final_T"]))[safe].max() < 1e-3, f"{what}: coverage"
+    worst, skipped = assert_depth_coverage_tight(aux, o, what=what)
+    assert skipped <= MAX_SKIPPED, f"{what}: {100 * skipped:.1f} % of the frame is near a threshold and skipped by the depth / coverage budget (at most {100 * MAX_SKIPPED:.0f} %)"
+    return worst, skipped
+
+
+def check_variants_against_oracle(drv, scene, cam, cfg=None, bg=BG, what="", fine=True, switches=True):
+    """The instantiations of the composite that a black-background frame never runs — TF (cfg.bg != 0: the final transmittance of stopped
+    pixels, 1 - sum of weights) and AUX (sgs_render_rgbd: expected depth and coverage, built for another occupancy) — on the scene ALREADY
+    UPLOADED in `drv` (`scene`: its arrays, for the oracle), whose black-background frame the caller has held against the oracle.
+    `cfg`: non-default thresholds (its own background is ignored: black and `bg` are rendered).  Per tiling — 16x16-pixel tiles, and, with
+    fine=True and a frame small enough, the fine tiles forced —:
+      1. img0, the black-background frame of the instantiation a sweep runs (no SGS_FLAG_STATS);
+      2. AUX, black background: RGB == img0 bit for bit; depth and coverage against the oracle (flat checks and the budget; at most
+         MAX_SKIPPED of the frame near a threshold); SGS_FLAG_NO_DEEP and SGS_FLAG_STATS change no bit of either; N_v and D are img0's;
+      3. TF: the frame over `bg` against the oracle rendered with that background (assert_frame_close, assert_frame_tight);
+         SGS_FLAG_NO_DEEP and SGS_FLAG_STATS change no bit;
+      4. AUX over `bg`: RGB == 3 bit for bit, depth and coverage == 2 bit for bit (neither depends on the background).
+    Between the tilings depth and coverage agree within the budget, not bit for bit (another tile origin, as for RGB): each is held to
+    the oracle, so they are within twice the budget of each other — asserted on the pixels away from a threshold.
+    switches=False (a few long emulator cases): the SGS_FLAG_NO_DEEP / SGS_FLAG_STATS renders of 2 and 3 are left out under fine tiles.
+    Returns a dict: the stats of the AUX and TF renders on 16x16-pixel tiles (both without SGS_FLAG_STATS: the deep-tile path is theirs),
+    the worst err / tol_px of the TF frames and of depth / coverage, the skipped share, the frames."""
+    t0 = time.time()
+    cfg0 = None if cfg is None else with_background(cfg, (0.0, 0.0, 0.0))
+    cfg_bg = with_background(cfg, bg)
+    _, o = oracle_c.render(*scene, cam, cfg0)
+    ref_bg, o_bg = oracle_c.render(*scene, cam, cfg_bg, want="image")
+    res = dict(worst_tf=0.0, worst_aux=0.0, skipped=0.0)
+    aux_by_tiling = []
+
+    def one_tiling(fine_flag, tag, sw):
+        w = f"{what} [{tag}]"
+        img0, st0 = drv.render(cam, cfg0, stats=False, fine=fine_flag)
+        rgb_a, aux_a, st_a = drv.render_aux(cam, cfg0, fine=fine_flag)
+        assert st_a["n_tiles"] == st0["n_tiles"]
+        assert (rgb_a == img0).all(), f"{w}: the AUX instantiation changed the colours"
+        assert st_a["n_visible"] == st0["n_visible"] == o["n_visible"] and st_a["d_total"] == st0["d_total"], (w, st_a, st0)
+        wa, sk = _aux_against_oracle(aux_a, o, w + " AUX")
+        img_bg, st_bg = drv.render(cam, cfg_bg, stats=False, fine=fine_flag)
+        assert st_bg["n_visible"] == st0["n_visible"] and st_bg["d_total"] == st0["d_total"]
+        assert_frame_close(img_bg, ref_bg, o_bg["margin"], o_bg["recheck"], what=w + " TF")
+        wt = assert_frame_tight(img_bg, ref_bg, o_bg, what=w + " TF")
+        if sw:
+            for kw, name in ((dict(deep=False), "SGS_FLAG_NO_DEEP"), (dict(stats=True), "SGS_FLAG_STATS")):
+                rgb_s, aux_s, st_s = drv.render_aux(cam, cfg0, fine=fine_flag, **kw)
+                assert (rgb_s == img0).all() and (aux_s == aux_a).all(), f"{w}: {name} changed the AUX render"
+                assert st_s["n_deep_windows"] == 0, (w, name, st_s["n_deep_windows"])
+                img_s, st_s = drv.render(cam, cfg_bg, fine=fine_flag, **{"stats": False, **kw})
+                assert (img_s == img_bg).all(), f"{w}: {name} changed the frame over a background"
+                assert st_s["n_deep_windows"] == 0, (w, name, st_s["n_deep_windows"])
+        rgb_ab, aux_ab, st_ab = drv.render_aux(cam, cfg_bg, fine=fine_flag)
+        assert (rgb_ab == img_bg).all(), f"{w}: the AUX instantiation changed the colours over a background"
+        assert (aux_ab == aux_a).all(), f"{w}: depth / coverage depend on the background"
+        res["worst_tf"] = max(res["worst_tf"], wt); res["worst_aux"] = max(res["worst_aux"], wa); res["skipped"] = max(res["skipped"], sk)
+        aux_by_tiling.append(aux_a)
+        return dict(st_aux=st_a, st_tf=st_bg, st_aux_bg=st_ab, img0=img0, img_bg=img_bg, aux=aux_a)
+
+    res.update(one_tiling(False, "16x16", True))
+    res["n_tiles_fine"] = res["st_aux"]["n_tiles"]
+    if fine:
+        with forced_fine(drv):
+            _, st_f = drv.render(cam, cfg0, stats=False)
+            if st_f["n_tiles"] != res["st_aux"]["n_tiles"]:
+                f = one_tiling(True, "fine tiles", switches)
+                res["n_tiles_fine"] = f["st_aux"]["n_tiles"]
+                assert res["n_tiles_fine"] == st_f["n_tiles"]
+                res["fine"] = f
+                # both tilings are within the budget of the oracle: twice the budget of each other, where no decision is near a threshold
+                assert_aux_tilings_agree(aux_by_tiling[0], aux_by_tiling[1], o, what=what)
+    o_bg["recheck"].close(); o["recheck"].close()
+    res["seconds"] = time.time() - t0
+    print(f"[variants] {what}: TF worst err/tol_px {res['worst_tf']:.3f}, depth/coverage {res['worst_aux']:.3f}, skipped {100 * res['skipped']:.2f} %, "
+          f"{cam.width}x{cam.height}, tiles {res['st_aux']['n_tiles']} / {res['n_tiles_fine']}, deep windows AUX {res['st_aux']['n_deep_windows']} TF {res['st_tf']['n_deep_windows']}, "
+          f"spill tiles AUX {res['st_aux']['n_spill_tiles']} TF {res['st_tf']['n_spill_tiles']}, {res['seconds']:.1f} s")
+    return res
+
+
+def check_aux_bands(drv, cam, cfg, cuts, what="", fine=True):
+    """Bands of tile rows through sgs_render_rgbd: into RGB and aux buffers pre-filled with SENTINEL, the band [r0, r1) of 16-pixel rows
+    writes its own rows only — bit for bit the rows of the whole-frame render — and leaves every other row of BOTH buffers alone; the
+    bands of a partition (cuts: r0 < r1 < ... covering the frame) reassemble the frame.  16x16-pixel tiles and the fine tiles, forced
+    (a 16-pixel row is then 2 or 4 rows of tiles)."""
+    h, w = cam.height, cam.width
+    gy = (h + 15) // 16
+    assert cuts[0] == 0 and cuts[-1] == gy and all(a < b for a, b in zip(cuts[:-1], cuts[1:])), cuts
+    with forced_fine(drv):
+        for fine_flag in ((False, True) if fine else (False,)):
+            full, full_aux, st_full = drv.render_aux(cam, cfg, fine=fine_flag)
+            union = np.full_like(full, SENTINEL); union_aux = np.full_like(full_aux, SENTINEL)
+            d_sum = 0
+            for r0, r1 in zip(cuts[:-1], cuts[1:]):
+                out = np.full((h, w, 3), SENTINEL, np.float32); out_aux = np.full((h, w, 2), SENTINEL, np.float32)
+                img, aux, st = drv.render_aux(cam, cfg, rows=(r0, r1), fine=fine_flag, out=out, out_aux=out_aux)
+                y0, y1 = 16 * r0, min(16 * r1, h)
+                tag = f"{what}: rows [{r0}, {r1}) (fine {fine_flag})"
+                assert (img[:y0] == SENTINEL).all() and (img[y1:] == SENTINEL).all(), f"{tag}: RGB rows outside the band were written"
+                assert (aux[:y0] == SENTINEL).all() and (aux[y1:] == SENTINEL).all(), f"{tag}: aux rows outside the band were written"
+                assert (img[y0:y1] == full[y0:y1]).all(), f"{tag}: the band's RGB differs from the whole frame's"
+                assert (aux[y0:y1] == full_aux[y0:y1]).all(), f"{tag}: the band's depth / coverage differ from the whole frame's"
+                union[y0:y1] = img[y0:y1]; union_aux[y0:y1] = aux[y0:y1]
+                d_sum += st["d_total"]
+            assert (union == full).all() and (union_aux == full_aux).all() and d_sum == st_full["d_total"], f"{what}: the bands do not reassemble the frame (fine {fine_flag})"
+
+
 # ------------------------------------------------------------------------------------------------
 def case_config1(drv, n=10_000):
     scene, cam = onp.config1_scene(n=n, seed=0)
@@ -201,39 +328,46 @@ def case_ragged(drv):
         check_against_oracle(drv, scene, cam, what=f"ragged n={n} {w}x{h}")
 
 
+def fuzz_frame(seed, max_n=700, max_res=(260, 160), wild=False):
+    """The scene, camera and non-default config of fuzz seed `seed` (case_fuzz's generator), and the generator's state for what a case
+    draws next: (rng, scene, cam, cfg, n, w, h, deg)."""
+    rng = np.random.default_rng(10_000 + seed)
+    n = int(rng.integers(1, max_n))
+    w, h = int(rng.integers(17, max_res[0])), int(rng.integers(17, max_res[1]))
+    deg = int(rng.integers(0, 4))
+    lo = float(10 ** rng.uniform(-2.7, -1.0)); hi = lo * float(10 ** rng.uniform(0.3, 2.0))
+    if wild:                     # needles and pancakes up to the size of the scene, specks far below a pixel
+        lo = float(10 ** rng.uniform(-4.0, -1.0)); hi = lo * float(10 ** rng.uniform(0.3, 4.0))
+    scene = random_scene(n, 20_000 + seed, deg, box=((-3, 3), (-2, 2), (-1, 9)), scale=(lo, min(hi, 20.0 if wild else 3.0)),
+                         opac_mu=float(rng.uniform(-3.0, 2.0)))
+    if wild and seed % 3 == 0:   # opacities at both ends of (0, 1); a tenth of the cloud pushed far away (last depth buckets)
+        scene[3][:] = np.clip(np.where(rng.random(n) < 0.5, 1.0 - 10 ** rng.uniform(-7, -2, n), 10 ** rng.uniform(-4, -1, n)), 1e-6, 1.0 - 1e-7).astype(np.float32)
+        far = rng.random(n) < 0.1
+        scene[0][far, 2] = (scene[0][far, 2] * float(10 ** rng.uniform(1, 3.5))).astype(np.float32)
+        scene[1][far] *= np.float32(30.0)
+    eye = np.array([rng.uniform(-3, 3), rng.uniform(-2, 2), rng.uniform(-3, 6)])
+    target = np.array([rng.uniform(-2, 2), rng.uniform(-1.5, 1.5), rng.uniform(3, 8)])
+    if np.linalg.norm(target - eye) < 0.5:
+        target = eye + np.array([0.1, 0.0, 1.0])
+    down = np.array([rng.normal(0, 0.3), 1.0, rng.normal(0, 0.3)])
+    view = look_at_view(eye, target, down)
+    f = float(w * rng.uniform(0.12 if wild else 0.35, 1.6))
+    cam = onp.Camera(w, h, f, f * float(rng.uniform(0.9, 1.1)), w / 2.0 + float(rng.uniform(-3, 3)),
+                     h / 2.0 + float(rng.uniform(-3, 3)), view)
+    cfg = onp.Config(near=float(rng.choice([0.2, 0.05, 0.5])), dilation=float(rng.choice([0.3, 0.1, 0.6])),
+                     alpha_min=float(rng.choice([1.0 / 255.0, 0.01, 0.002])), alpha_max=float(rng.choice([0.99, 0.9])),
+                     t_min=float(rng.choice([1.0e-4, 1.0e-3])), background=tuple(float(v) for v in rng.uniform(0, 1, 3)),
+                     sh_degree=int(rng.integers(0, deg + 1)) if rng.random() < 0.3 else -1)
+    return rng, scene, cam, cfg, n, w, h, deg
+
+
 def case_fuzz(drv, seeds, max_n=700, max_res=(260, 160), wild=False, thorough_every=1):
     """Seeded random small frames through the full comparison: scene size, resolution (ragged tiles), SH degree, splat
     sizes from sub-pixel to screen-filling, opacities down to the cut-off, cameras inside and outside the cloud (Gaussians
     behind the camera, across the near plane, off screen), non-default thresholds / dilation / background, and a band of
     tile rows now and then."""
     for seed in seeds:
-        rng = np.random.default_rng(10_000 + seed)
-        n = int(rng.integers(1, max_n))
-        w, h = int(rng.integers(17, max_res[0])), int(rng.integers(17, max_res[1]))
-        deg = int(rng.integers(0, 4))
-        lo = float(10 ** rng.uniform(-2.7, -1.0)); hi = lo * float(10 ** rng.uniform(0.3, 2.0))
-        if wild:                     # needles and pancakes up to the size of the scene, specks far below a pixel
-            lo = float(10 ** rng.uniform(-4.0, -1.0)); hi = lo * float(10 ** rng.uniform(0.3, 4.0))
-        scene = random_scene(n, 20_000 + seed, deg, box=((-3, 3), (-2, 2), (-1, 9)), scale=(lo, min(hi, 20.0 if wild else 3.0)),
-                             opac_mu=float(rng.uniform(-3.0, 2.0)))
-        if wild and seed % 3 == 0:   # opacities at both ends of (0, 1); a tenth of the cloud pushed far away (last depth buckets)
-            scene[3][:] = np.clip(np.where(rng.random(n) < 0.5, 1.0 - 10 ** rng.uniform(-7, -2, n), 10 ** rng.uniform(-4, -1, n)), 1e-6, 1.0 - 1e-7).astype(np.float32)
-            far = rng.random(n) < 0.1
-            scene[0][far, 2] = (scene[0][far, 2] * float(10 ** rng.uniform(1, 3.5))).astype(np.float32)
-            scene[1][far] *= np.float32(30.0)
-        eye = np.array([rng.uniform(-3, 3), rng.uniform(-2, 2), rng.uniform(-3, 6)])
-        target = np.array([rng.uniform(-2, 2), rng.uniform(-1.5, 1.5), rng.uniform(3, 8)])
-        if np.linalg.norm(target - eye) < 0.5:
-            target = eye + np.array([0.1, 0.0, 1.0])
-        down = np.array([rng.normal(0, 0.3), 1.0, rng.normal(0, 0.3)])
-        view = look_at_view(eye, target, down)
-        f = float(w * rng.uniform(0.12 if wild else 0.35, 1.6))
-        cam = onp.Camera(w, h, f, f * float(rng.uniform(0.9, 1.1)), w / 2.0 + float(rng.uniform(-3, 3)),
-                         h / 2.0 + float(rng.uniform(-3, 3)), view)
-        cfg = onp.Config(near=float(rng.choice([0.2, 0.05, 0.5])), dilation=float(rng.choice([0.3, 0.1, 0.6])),
-                         alpha_min=float(rng.choice([1.0 / 255.0, 0.01, 0.002])), alpha_max=float(rng.choice([0.99, 0.9])),
-                         t_min=float(rng.choice([1.0e-4, 1.0e-3])), background=tuple(float(v) for v in rng.uniform(0, 1, 3)),
-                         sh_degree=int(rng.integers(0, deg + 1)) if rng.random() < 0.3 else -1)
+        rng, scene, cam, cfg, n, w, h, deg = fuzz_frame(seed, max_n, max_res, wild)
         gy = (h + 15) // 16
         rows = (0, -1)
         if gy >= 3 and rng.random() < 0.3:
@@ -255,7 +389,7 @@ def case_fuzz(drv, seeds, max_n=700, max_res=(260, 160), wild=False, thorough_ev
             assert d_sum == st_full["d_total"], f"fuzz seed {seed}: interleaved shards queue {d_sum} records, the frame {st_full['d_total']}"
         if seed % 4 == 0:
             rgb0, _ = drv.render(cam, stats=False)          # (the production instantiation)
-            rgb, aux = drv.render_aux(cam)
+            rgb, aux, _ = drv.render_aux(cam)
             assert (rgb == rgb0).all(), f"fuzz seed {seed}: the aux instantiation changed the colours"
             ref, o = oracle_c.render(*scene, cam)
             safe = o["margin"] >= 1e-4
@@ -264,6 +398,23 @@ def case_fuzz(drv, seeds, max_n=700, max_res=(260, 160), wild=False, thorough_ev
                 assert np.abs(aux[..., 0] - o["depth_image"])[safe].max() < 1e-3 * zmax, f"fuzz seed {seed}: depth"
                 assert np.abs(aux[..., 1] - (1.0 - o["final_T"]))[safe].max() < 1e-3, f"fuzz seed {seed}: coverage"
             assert_depth_coverage_tight(aux, o, what=f"fuzz seed {seed} aux")
+
+
+def case_fuzz_variants(drv, seeds, max_n=700, max_res=(260, 160)):
+    """case_fuzz's generator, seeds of its own, and on EVERY seed what case_fuzz draws now and then: the seed's non-default thresholds,
+    dilation, near plane and SH degree, its random background, the depth / coverage outputs, and — wherever the frame has three tile
+    rows — a partition into bands.  The black-background frame through check_against_oracle, the TF and AUX instantiations through
+    check_variants_against_oracle, the bands through check_aux_bands.  (A driver whose render_aux drops `cfg` fails here on the first
+    seed: the oracle is rendered with the seed's thresholds and background.)"""
+    for seed in seeds:
+        rng, scene, cam, cfg, n, w, h, deg = fuzz_frame(seed, max_n, max_res)
+        what = f"fuzz variants seed {seed} (n={n} {w}x{h} deg {deg})"
+        check_against_oracle(drv, scene, cam, with_background(cfg, (0.0, 0.0, 0.0)), what=what, thorough=False)
+        check_variants_against_oracle(drv, scene, cam, cfg, bg=cfg.background, what=what)
+        gy = (h + 15) // 16
+        if gy >= 3:
+            r0 = int(rng.integers(1, gy - 1)); r1 = int(rng.integers(r0 + 1, gy))
+            check_aux_bands(drv, cam, cfg, [0, r0, r1, gy], what=what)
 
 
 def case_non_finite_gaussians(drv, n=3000, res=(160, 120), seed=3):
@@ -286,12 +437,20 @@ def case_non_finite_gaussians(drv, n=3000, res=(160, 120), seed=3):
     w, h = res
     cam = onp.Camera(w, h, 0.8 * w, 0.8 * w, w / 2.0, h / 2.0, np.eye(4, dtype=np.float32))
     keep = ~hit
-    drv.upload(means[keep], scales[keep], quats[keep], opac[keep], sh[keep], deg)
+    clean = (means[keep], scales[keep], quats[keep], opac[keep], sh[keep], deg)
+    cfg_bg = with_background(None, BG)
+    drv.upload(*clean)
     ref, st_ref = drv.render(cam)
+    # ... and the depth / coverage outputs over a background (the TF and AUX instantiations): held to the oracle on the clean scene
+    check_variants_against_oracle(drv, clean, cam, what=f"non-finite Gaussians removed (seed {seed})", switches=False)
+    ref_bg, ref_aux, _ = drv.render_aux(cam, cfg_bg)
     drv.upload(bm, bs, bq, bo, sh, deg)
     img, st = drv.render(cam)
     assert np.isfinite(img).all() and (img == ref).all(), "a non-finite Gaussian changed the frame"
     assert st["d_total"] == st_ref["d_total"]
+    img_bg, aux, _ = drv.render_aux(cam, cfg_bg)
+    assert np.isfinite(img_bg).all() and np.isfinite(aux).all(), "a non-finite Gaussian made depth / coverage or the frame over a background non-finite"
+    assert (img_bg == ref_bg).all() and (aux == ref_aux).all(), "a non-finite Gaussian changed depth / coverage or the frame over a background"
 
 
 def case_padding_lanes(drv):
@@ -302,6 +461,7 @@ def case_padding_lanes(drv):
     cam = onp.Camera(64, 64, 50.0, 50.0, 32.0, 32.0, view)
     img, st, aux, _ = check_against_oracle(drv, scene, cam, what="padding lanes")
     assert st["n_visible"] == aux["n_visible"] <= 70
+    check_variants_against_oracle(drv, scene, cam, what="padding lanes")
 
 
 def case_empty(drv):
@@ -312,11 +472,31 @@ def case_empty(drv):
     img, st = drv.render(cam, onp.Config(background=(0.25, 0.5, 0.75)))
     assert st["n_visible"] == 0 and st["d_total"] == 0
     assert np.allclose(img, [0.25, 0.5, 0.75], atol=1e-7)
+
+    def nothing_to_see(tag):
+        """No splat reaches a pixel: T_final is exactly 1 (alpha_max T / alpha_max), so RGB is exactly the background and depth and
+        coverage are exactly 0 — in the TF and in the AUX instantiation, on 16x16-pixel and on fine tiles, whole frame and band."""
+        bg = np.asarray(BG, np.float32)
+        with forced_fine(drv):
+            for fine in (False, True):
+                for kw in (dict(), dict(stats=True), dict(deep=False)):
+                    img, st = drv.render(cam, with_background(None, BG), fine=fine, **kw)
+                    assert st["n_visible"] == 0 and (img == bg).all(), f"{tag}: the frame over a background is not the background (fine {fine}, {kw})"
+                    rgb, aux, st = drv.render_aux(cam, with_background(None, BG), fine=fine, **kw)
+                    assert st["d_total"] == 0 and (rgb == bg).all() and (aux == 0.0).all(), f"{tag}: RGB-D of nothing (fine {fine}, {kw})"
+                    rgb, aux, _ = drv.render_aux(cam, None, fine=fine, **kw)
+                    assert (rgb == 0.0).all() and (aux == 0.0).all(), f"{tag}: RGB-D of nothing over black (fine {fine}, {kw})"
+                out = np.full((cam.height, cam.width, 3), SENTINEL, np.float32); out_aux = np.full((cam.height, cam.width, 2), SENTINEL, np.float32)
+                rgb, aux, _ = drv.render_aux(cam, with_background(None, BG), rows=(1, 2), fine=fine, out=out, out_aux=out_aux)
+                assert (rgb[16:32] == bg).all() and (aux[16:32] == 0.0).all() and (rgb[:16] == SENTINEL).all() and (aux[:16] == SENTINEL).all() \
+                    and (rgb[32:] == SENTINEL).all() and (aux[32:] == SENTINEL).all(), f"{tag}: a band of nothing (fine {fine})"
+    nothing_to_see("empty scene")
     # everything culled (all behind the camera)
     scene = random_scene(300, 1, 0, box=((-1, 1), (-1, 1), (-8, -2)))
     drv.upload(*scene)
     img, st = drv.render(cam)
     assert st["n_visible"] == 0 and st["d_total"] == 0 and (img == 0).all()
+    nothing_to_see("all culled")
 
 
 def case_interleaved_rows(drv, stride, n=2500, res=(208, 150)):
@@ -439,9 +619,10 @@ def case_depth_ties(drv):
     sh = rng.normal(size=(n, 1, 3)).astype(np.float32)
     cam = onp.Camera(64, 64, 64.0, 64.0, 32.0, 32.0, np.eye(4, dtype=np.float32))
     check_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what="depth ties")
+    check_variants_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what="depth ties")
 
 
-def case_sort_classes(drv, sizes=(700, 2500, 6000, 9500)):
+def case_sort_classes(drv, sizes=(700, 2500, 6000, 9500), variant_switches=True):
     """Queue lengths that land in each sort class: S (<=1024), M (<=4096), L (<=9216, all in LDS)
     and X (spill: ping-pong in HBM)."""
     for n in sizes:
@@ -454,6 +635,8 @@ def case_sort_classes(drv, sizes=(700, 2500, 6000, 9500)):
         cam = onp.Camera(32, 32, 32.0, 32.0, 16.0, 16.0, np.eye(4, dtype=np.float32))
         img, st, aux, _ = check_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what=f"sort class n={n}")
         assert st["max_tile_len"] == n
+        v = check_variants_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what=f"sort class n={n}", switches=variant_switches)
+        assert v["st_aux"]["max_tile_len"] == n and v["st_tf"]["max_tile_len"] == n
 
 
 def case_sparse_lists(drv, n=9000, res=(48, 40)):
@@ -479,14 +662,11 @@ def case_sparse_lists(drv, n=9000, res=(48, 40)):
         img, st, aux, _ = check_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what=f"sparse lists (seed {seed})")
         assert st["max_tile_len"] > 512, st["max_tile_len"]
         assert float((aux["final_T"] > 0.05).mean()) > 0.5 or big
+        check_variants_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what=f"sparse lists (seed {seed})")
 
 
-def case_deep_tile(drv, n_back=6000):
-    """Tiles that keep consuming batches for a few pixels: three opaque layers saturate every pixel of a 32x32 image except a 5x5 hole
-    per tile, and thousands of splats behind them are visible only through the holes.  After SGS_DEEP_AFTER batches such a tile culls every
-    resident window of its queue against the live pixels BEFORE ranking / staging (k_tile_render, deep tiles) and blends the survivors as one
-    batch: the frame must equal the oracle's AND the frame of the ordinary path (the D_f-counting instantiation) bit for bit — both
-    checked by check_against_oracle — and the path must actually have run."""
+def deep_tile_scene(n_back=6000):
+    """(scene, camera) of case_deep_tile."""
     rng = np.random.default_rng(21)
     ys, xs = np.mgrid[0:32, 0:32]
     hole = ((xs % 16 >= 8) & (xs % 16 <= 12) & (ys % 16 >= 3) & (ys % 16 <= 7))
@@ -507,21 +687,31 @@ def case_deep_tile(drv, n_back=6000):
     sh = rng.normal(size=(means.shape[0], 1, 3)).astype(np.float32)
     perm = rng.permutation(means.shape[0])
     scene = (means[perm], scales[perm], quats[perm], opac[perm], sh[perm], 0)
-    cam = onp.Camera(32, 32, f, f, c, c, np.eye(4, dtype=np.float32))
+    return scene, onp.Camera(32, 32, f, f, c, c, np.eye(4, dtype=np.float32))
+
+
+def case_deep_tile(drv, n_back=6000):
+    """Tiles that keep consuming batches for a few pixels: three opaque layers saturate every pixel of a 32x32 image except a 5x5 hole
+    per tile, and thousands of splats behind them are visible only through the holes.  After SGS_DEEP_AFTER batches such a tile culls every
+    resident window of its queue against the live pixels BEFORE ranking / staging (k_tile_render, deep tiles) and blends the survivors as one
+    batch: the frame must equal the oracle's AND the frame of the ordinary path (the D_f-counting instantiation) bit for bit — both
+    checked by check_against_oracle — and the path must actually have run."""
+    scene, cam = deep_tile_scene(n_back)
     img, st, aux, _ = check_against_oracle(drv, scene, cam, what="deep tile")
     assert st["max_tile_len"] > 1024 and st["n_deep_windows_plain"] >= 4, (st["max_tile_len"], st["n_deep_windows_plain"])
     # most pixels stopped inside the front layers, the holes read on deep into the queue
     stopped = float((aux["final_T"] < 1e-3).mean())
     assert stopped > 0.5 and st["d_fetched"] > 0.1 * st["d_total"], (stopped, st["d_fetched"], st["d_total"], st["n_deep_windows_plain"])
+    # the same frame through the TF and AUX instantiations, which take the deep-tile path too (their renders without SGS_FLAG_STATS): the
+    # windows culled against the live pixels must not lose or repeat a record's share of sum w (coverage, T_final bg) or of sum w z
+    v = check_variants_against_oracle(drv, scene, cam, what="deep tile")
+    assert v["st_aux"]["n_deep_windows"] >= 4 and v["st_tf"]["n_deep_windows"] >= 4 and v["st_aux_bg"]["n_deep_windows"] >= 4, \
+        (v["st_aux"]["n_deep_windows"], v["st_tf"]["n_deep_windows"], v["st_aux_bg"]["n_deep_windows"])
     print(f"[deep tile] {st['n_deep_windows_plain']} windows culled first; {100 * stopped:.0f} % of the pixels stopped; D_f / D = {st['d_fetched'] / st['d_total']:.2f}")
 
 
-def case_big_depth_bucket(drv, n_slab=3000):
-    """Thousands of splats of one tile inside a 2-cm slab of a queue that spans 1-12 m (a wall facing the camera), four fifths
-    of them at EXACTLY the same depth.  The composite cuts 256 depth buckets from the queue's own range (~3 cm each here), finds
-    the slab's bucket longer than one batch and partitions the queue again over that bucket's key range (refinement) — which
-    separates everything but the equal depths: that bucket exceeds the LDS capacity, cannot be refined and is sorted through
-    HBM, its run of equal keys ordered by index."""
+def big_depth_bucket_scene(n_slab=3000):
+    """(scene, camera) of case_big_depth_bucket."""
     rng = np.random.default_rng(8)
     n = n_slab + 500
     means = np.stack([rng.uniform(-0.1, 0.1, n), rng.uniform(-0.1, 0.1, n), rng.uniform(1.0, 12.0, n)], 1).astype(np.float32)
@@ -532,12 +722,26 @@ def case_big_depth_bucket(drv, n_slab=3000):
     quats = rng.normal(size=(n, 4)).astype(np.float32)
     opac = rng.uniform(0.005, 0.012, n).astype(np.float32)
     sh = rng.normal(size=(n, 1, 3)).astype(np.float32)
-    cam = onp.Camera(32, 32, 32.0, 32.0, 16.0, 16.0, np.eye(4, dtype=np.float32))
-    img, st, aux, _ = check_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what="big depth bucket")
+    return (means, scales, quats, opac, sh, 0), onp.Camera(32, 32, 32.0, 32.0, 16.0, 16.0, np.eye(4, dtype=np.float32))
+
+
+def case_big_depth_bucket(drv, n_slab=3000):
+    """Thousands of splats of one tile inside a 2-cm slab of a queue that spans 1-12 m (a wall facing the camera), four fifths
+    of them at EXACTLY the same depth.  The composite cuts 256 depth buckets from the queue's own range (~3 cm each here), finds
+    the slab's bucket longer than one batch and partitions the queue again over that bucket's key range (refinement) — which
+    separates everything but the equal depths: that bucket exceeds the LDS capacity, cannot be refined and is sorted through
+    HBM, its run of equal keys ordered by index."""
+    scene, cam = big_depth_bucket_scene(n_slab)
+    img, st, aux, _ = check_against_oracle(drv, scene, cam, what="big depth bucket")
     assert st["n_spill_tiles"] >= 1
+    # the long-sum case of the TF / AUX instantiations: every pixel adds thousands of weights of ~0.01 T into 1 - T_final and sum w z
+    # (each add rounds to half an ulp of a sum below 1: n 2^-25, inside B n of tight_parity's budget)
+    v = check_variants_against_oracle(drv, scene, cam, what="big depth bucket")
+    assert v["st_aux"]["n_spill_tiles"] >= 1 and v["st_tf"]["n_spill_tiles"] >= 1, (v["st_aux"]["n_spill_tiles"], v["st_tf"]["n_spill_tiles"])
+    assert int(aux["n_contrib"].max()) > 700, int(aux["n_contrib"].max())      # (alpha <= 0.012: a pixel blends ln(1 / t_min) / 0.012 = 767 records before it may stop)
 
 
-def case_full_grid_splat(drv, res=(1920, 1080), thorough=True):
+def case_full_grid_splat(drv, res=(1920, 1080), thorough=True, variants=False):
     """One huge splat covering every tile of a 1080p grid (120x68 = 8160 records from one lane) plus
     small ones: exercises the balanced duplication's row-major expansion over a wide rect."""
     w, h = res
@@ -552,6 +756,8 @@ def case_full_grid_splat(drv, res=(1920, 1080), thorough=True):
     cam = onp.Camera(w, h, 0.38 * w, 0.38 * w, w / 2.0, h / 2.0, np.eye(4, dtype=np.float32))
     img, st, aux, _ = check_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what="full-grid splat", thorough=thorough)
     assert aux["tiles"][17] == ((w + 15) // 16) * ((h + 15) // 16)
+    if variants:
+        check_variants_against_oracle(drv, (means, scales, quats, opac, sh, 0), cam, what=f"full-grid splat {w}x{h}", switches=thorough)
 
 
 def case_overflow_retry(drv):
@@ -563,6 +769,22 @@ def case_overflow_retry(drv):
     # and once grown, no more retries
     img2, st2 = drv.render(cam, fine=False)
     assert st2["retries"] == 0 and (img2 == img).all()
+    # the same entered through sgs_render_rgbd over a background: the frame that overflowed, grew the queues and was rendered again is
+    # the frame (and the depth / coverage) of the context that never overflowed — which is held against the oracle
+    cfg_bg = with_background(None, BG)
+    got = {}
+    with forced_fine(drv):
+        for fine in (False, True):
+            drv.set_record_capacity(1024)
+            out = np.full((cam.height, cam.width, 3), SENTINEL, np.float32); out_aux = np.full((cam.height, cam.width, 2), SENTINEL, np.float32)
+            rgb1, aux1, st1 = drv.render_aux(cam, cfg_bg, fine=fine, out=out, out_aux=out_aux)
+            assert st1["d_total"] > 1024 and st1["retries"] >= 1, (fine, st1["d_total"], st1["retries"])
+            rgb2, aux2, st2 = drv.render_aux(cam, cfg_bg, fine=fine)
+            assert st2["retries"] == 0 and (rgb2 == rgb1).all() and (aux2 == aux1).all(), f"the retried RGB-D frame differs from the un-overflowed one (fine {fine})"
+            got[fine] = (rgb1, aux1)
+    v = check_variants_against_oracle(drv, scene, cam, what="overflow -> grow -> retry")
+    assert (got[False][0] == v["img_bg"]).all() and (got[False][1] == v["aux"]).all()
+    assert (got[True][0] == v["fine"]["img_bg"]).all() and (got[True][1] == v["fine"]["aux"]).all()
 
 
 def case_depth_aux(drv, n=1500, res=(96, 80)):
@@ -573,7 +795,7 @@ def case_depth_aux(drv, n=1500, res=(96, 80)):
     cam = onp.Camera(w, h, 0.8 * w, 0.8 * w, w / 2.0, h / 2.0, np.eye(4, dtype=np.float32))
     drv.upload(*scene)
     rgb0, _ = drv.render(cam, stats=False)
-    rgb, aux = drv.render_aux(cam)
+    rgb, aux, _ = drv.render_aux(cam)
     assert (rgb == rgb0).all()
     ref, o = oracle_c.render(*scene, cam)
     safe = o["margin"] >= 1e-4
@@ -629,6 +851,14 @@ def case_batch_shares_scene_reads(drv, n=4000, res=(160, 112), quick=False):
                 batch = drv.render_batch(cams, fine=fine)
             for i, a in enumerate(alone):
                 assert (batch[i] == a).all(), f"frame {i} of a batch of {len(cams)} differs from the frame rendered alone (fine {fine})"
+            if cams is mixed:        # ... and over a background: the batch launches the TF instantiation with one frame per blockIdx.y
+                cfg_bg = with_background(None, BG)
+                with forced_fine(drv):
+                    alone_bg = [drv.render(c, cfg_bg, stats=False, fine=fine)[0] for c in cams]
+                    batch_bg = drv.render_batch(cams, fine=fine, cfg=cfg_bg)
+                for i, a in enumerate(alone_bg):
+                    assert (batch_bg[i] == a).all(), f"frame {i} of a batch over a background differs from the frame rendered alone (fine {fine})"
+                assert any((a != b).any() for a, b in zip(alone_bg, alone)), "the background shows in no frame"
     assert any(a.max() > 0.05 for a in alone)
 
 

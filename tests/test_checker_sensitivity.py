@@ -36,7 +36,44 @@ MUTANTS = {
     # background: the final transmittance rounded to fp16 precision before T * bg
     "bg_T_fp16": [("o[0] = C0 + Tf * P.bg[0]; o[1] = C1 + Tf * P.bg[1]; o[2] = C2 + Tf * P.bg[2];",
                    "o[0] = C0 + SGS_MUT_R11(Tf) * P.bg[0]; o[1] = C1 + SGS_MUT_R11(Tf) * P.bg[1]; o[2] = C2 + SGS_MUT_R11(Tf) * P.bg[2];")],
+    # the final transmittance of a STOPPED pixel (1 - the sum of its weights) dropped: such a pixel loses T_final bg, between t_min and
+    # t_min / (1 - alpha) of the background for the alpha it stopped on — 1.0e-4 to 1.012e-4 in a queue of faint splats (alpha <= 0.012)
+    "tf_stopped_zero": [("const float Tf = Tm > 0.0f ? Tm / amax : fmaxf(1.0f - Wsum, 0.0f);", "const float Tf = Tm > 0.0f ? Tm / amax : 0.0f;")],
+    # SGS_APPLY: the weights summed into 1 - T_final at fp16 precision.  Caught where pixels stop on a few LARGE weights (the deep-tile
+    # scene's opaque layers: a weight of 0.99 rounded to 11 bits is off by up to 2.4e-4, the budget there is A = 1.5e-5).  NOT caught on
+    # the big-depth-bucket scene, measured under the emulator: ~1100 weights of <= 0.012 rounded to 11 bits move coverage by 4.9e-5,
+    # and the budget at n_px = 1100 is A + B n_px = 8.1e-5 — B grants every record one whole rounding of a sum of 1, a faint record's
+    # fp16 rounding (w 2^-12 <= 3e-6 each, signs random) stays below that.  The budget is a bound on fp32 arithmetic, not a detector of
+    # every lower precision: in a queue of faint records it cannot tell fp16 weights from fp32 ones.
+    "tf_wsum_fp16": [("if (TF) Wsum += wgt;", "if (TF) Wsum += SGS_MUT_R11(wgt);")],
 }
+# No mutant sits in the deep-tile branch of render_tile (`!STATS && deep_ok && ...`) alone: that branch culls a window's records against the
+# live pixels and compacts the survivors' keys — it holds no line that touches Wsum or Dz; the survivors are staged and blended by the code
+# every tile runs (SGS_APPLY, mutated above).  A record it dropped or repeated would show in the colours as well, which case_deep_tile
+# holds against the ordinary path bit for bit; check_variants_against_oracle proves that the branch RAN in the TF and AUX kernels.
+
+
+def _variants(scene_cam, bg=pc.BG, what=""):
+    def case(drv):
+        scene, cam = scene_cam
+        drv.upload(*scene)
+        pc.check_variants_against_oracle(drv, scene, cam, bg=bg, what=what, switches=False)
+    return case
+
+
+def _tf_over_white(drv):
+    """The TF frame alone (cfg.bg = 1) of the big-depth-bucket scene: every pixel stops, on a faint splat, thousands of records in."""
+    import oracle_c
+    scene, cam = pc.big_depth_bucket_scene(1500)
+    cfg = pc.with_background(None, (1.0, 1.0, 1.0))
+    drv.upload(*scene)
+    ref, o = oracle_c.render(*scene, cam, cfg, want="image")
+    assert float((o["final_T"] < 1.02e-4).mean()) > 0.9, "the pixels of this case are meant to stop"
+    for kw in (dict(fine=False), dict()):
+        with pc.forced_fine(drv):
+            img, _ = drv.render(cam, cfg, stats=False, **kw)
+        conftest.assert_frame_close(img, ref, o["margin"], o["recheck"], what=f"big depth bucket over white {kw}")
+        pc.assert_frame_tight(img, ref, o, what=f"big depth bucket over white {kw}")
 
 
 def _fuzz(seeds):
@@ -56,6 +93,8 @@ CASES = {
     "fine_centre_2^-10px": _fuzz([1]),
     "t_min_x1.05": _config1,
     "bg_T_fp16": _fuzz([1]),
+    "tf_stopped_zero": _tf_over_white,
+    "tf_wsum_fp16": _variants(pc.deep_tile_scene(2000), what="deep tile"),
 }
 
 
@@ -102,9 +141,10 @@ def _run(lib_path, case, tight, monkeypatch):
             d = np.abs(out_aux[..., 0] - o["depth_image"]) / max(1.0, float(o["depth_image"].max()))
             c = np.abs(out_aux[..., 1] - (1.0 - o["final_T"]))
             seen["aux"] = max(seen["aux"], float(d[safe].max(initial=0.0)), float(c[safe].max(initial=0.0)))
-            return 0.0
+            return 0.0, 1.0 - float(safe.mean())
         monkeypatch.setattr(pc, "assert_frame_tight", no_tight)
         monkeypatch.setattr(pc, "assert_depth_coverage_tight", aux_seen)
+        monkeypatch.setattr(pc, "assert_aux_tilings_agree", no_tight)
     n0 = len(conftest.PARITY_LOG)
     drv = emu_harness.EmuRenderer(record_capacity=1 << 20, lib_path=lib_path)
     try:

@@ -9,6 +9,9 @@ import oracle_np as onp
 import parity_cases as pc
 
 
+FUZZ_VARIANT_SEEDS = tuple(range(9100, 9112))      # case_fuzz_variants: every seed with thresholds, background, aux and (3+ tile rows) bands
+
+
 @pytest.fixture(scope="module")
 def drv():
     d = emu_harness.EmuRenderer(record_capacity=1 << 21)
@@ -36,6 +39,10 @@ def test_seeded_random_frames_with_needles_and_specks(drv):
     """Splats from far below a pixel to needles and pancakes the size of the scene (aspect ratios up to 1e4): what the
     completed-square form of q2 is for (seeds 8019 and 8036 failed the three-term form by 1.6e-3)."""
     pc.case_fuzz(drv, range(7000, 7020), 400, (200, 120), wild=True)
+
+
+def test_seeded_random_frames_over_a_background_with_depth_and_coverage(drv):
+    pc.case_fuzz_variants(drv, FUZZ_VARIANT_SEEDS)
 
 
 def test_non_finite_gaussians_are_invisible_and_harmless(drv):
@@ -73,7 +80,7 @@ def test_big_depth_bucket(drv):
 
 
 def test_sort_classes(drv):
-    pc.case_sort_classes(drv, sizes=(700, 2500, 9500))
+    pc.case_sort_classes(drv, sizes=(700, 2500, 6000, 9500), variant_switches=False)
 
 
 def test_sparse_lists(drv):
@@ -85,7 +92,7 @@ def test_deep_tile(drv):
 
 
 def test_full_grid_splat(drv):
-    pc.case_full_grid_splat(drv, res=(640, 368))
+    pc.case_full_grid_splat(drv, res=(640, 368), variants=True)
 
 
 def test_wide_band_of_tiles(drv):
@@ -178,6 +185,17 @@ def test_pipelined_frames_and_batch_rotate_over_lanes(drv):
     assert (plain == seq[2]).all()
     for a, b in zip(seq, outs):
         assert (a == b).all()
+    # RGB-D frames in flight: each with its own out / out_aux, every other one over a background; after one sgs_frame_sync every
+    # RGB and every depth / coverage buffer is the synchronous render's, bit for bit
+    cfg_of = lambda i: pc.with_background(None, pc.BG) if i % 2 else None
+    want = [drv.render_aux(c, cfg_of(i))[:2] for i, c in enumerate(cams)]
+    bufs = [(np.full((80, 96, 3), pc.SENTINEL, np.float32), np.full((80, 96, 2), pc.SENTINEL, np.float32)) for _ in cams]
+    for i, (c, (o, oa)) in enumerate(zip(cams, bufs)):
+        drv.render_aux(c, cfg_of(i), out=o, out_aux=oa, flags=_capi.FLAG_ASYNC | _capi.FLAG_PIPELINED)
+    drv.sync()
+    for i, ((o, oa), (w_rgb, w_aux)) in enumerate(zip(bufs, want)):
+        assert (o == w_rgb).all() and (oa == w_aux).all(), f"pipelined RGB-D frame {i} differs from the synchronous one"
+    assert (want[1][0] != want[0][0]).any() and want[0][1].max() > 0.5
     # the batch entry point (always pipelined)
     arr = (_capi.SgsCamera * len(cams))(*[_capi.make_camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy,
                                                             np.asarray(c.view, np.float32).reshape(4, 4).tolist()) for c in cams])
@@ -267,6 +285,13 @@ def test_argument_errors_are_reported_not_swallowed(drv):
     expect_invalid(call(cfg=bad), "tile_row_phase")
     bad.tile_row_phase = -1
     expect_invalid(call(cfg=bad), "tile_row_phase")
+    # depth / coverage have no compact form (sage_gs.h): interleaved rows through sgs_render_rgbd are refused, nothing is written
+    aux_buf = np.full((32, 32, 2), -7.0, np.float32); rgb_buf = np.full((32, 32, 3), -7.0, np.float32)
+    for stride in (2, 3):
+        bad = lib.default_config(); bad.tile_row_stride, bad.tile_row_phase = stride, 1
+        expect_invalid(lib.sgs_render_rgbd(ctx, drv.scene, C.byref(good), C.byref(bad), 0, -1, rgb_buf.ctypes.data, aux_buf.ctypes.data, None, None), "out_aux")
+        assert call(cfg=bad) == 0                              # (the same rows without out_aux: rendered)
+    assert (aux_buf == -7.0).all() and (rgb_buf == -7.0).all()
     # what the kernels assume of the constants and of the view (round-1 advisor finding: near_z <= 0 breaks the depth-key order)
     for field, value, word in (("near_z", 0.0, "near_z"), ("near_z", -1.0, "near_z"), ("far_z", 0.1, "near_z"),
                                ("alpha_min", 0.0, "alpha_min"), ("alpha_min", float("nan"), "alpha_min"),

@@ -35,10 +35,9 @@ class GpuDriver:
 
     def render(self, cam, cfg=None, rows=(0, -1), out=None, full_sort=False, loose_cull=False, interleave=None,
                chunk_cull=True, stats=True, deep=True, fine=True):
-        from sage_gs import Camera, RenderConfig
+        from sage_gs import Camera
         c = Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, np.asarray(cam.view, np.float64))
-        k = None if cfg is None else RenderConfig(cfg.near, cfg.far, cfg.dilation, cfg.clamp, cfg.alpha_min,
-                                                  cfg.alpha_max, cfg.t_min, cfg.background, cfg.sh_degree)
+        k = self._config(cfg)
         if interleave is not None:         # (stride, phase): compact image of the owned tile rows
             owned = len(range(interleave[1], (cam.height + 15) // 16, interleave[0]))
             band = self.torch.full((16 * owned, cam.width, 3), -1.0, dtype=self.torch.float32, device="cuda:0")
@@ -51,16 +50,26 @@ class GpuDriver:
                             full_sort=full_sort, loose_cull=loose_cull, chunk_cull=chunk_cull, stats=stats, deep_cull=deep, fine_tiles=fine)
         return img.cpu().numpy(), self.r.last_stats
 
-    def render_batch(self, cams, fine=True):
+    def _config(self, cfg):
+        from sage_gs import RenderConfig
+        return None if cfg is None else RenderConfig(cfg.near, cfg.far, cfg.dilation, cfg.clamp, cfg.alpha_min,
+                                                     cfg.alpha_max, cfg.t_min, cfg.background, cfg.sh_degree)
+
+    def render_batch(self, cams, fine=True, cfg=None):
         from sage_gs import Camera
         cl = [Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, np.asarray(c.view, np.float64)) for c in cams]
-        return self.r.render_batch(cl, self.scene, fine_tiles=fine).cpu().numpy()
+        return self.r.render_batch(cl, self.scene, config=self._config(cfg), fine_tiles=fine).cpu().numpy()
 
-    def render_aux(self, cam, cfg=None, fine=True):
+    def render_aux(self, cam, cfg=None, rows=(0, -1), fine=True, deep=True, stats=False, out=None, out_aux=None):
+        """Renderer.render(return_aux / out_aux): (rgb [H, W, 3], aux [H, W, 2] = expected depth and coverage, stats).  `out` / `out_aux`:
+        pre-filled host arrays, copied to the device, rendered into and copied back (a band leaves the other rows alone)."""
         from sage_gs import Camera
         c = Camera(cam.width, cam.height, cam.fx, cam.fy, cam.cx, cam.cy, np.asarray(cam.view, np.float64))
-        img, aux = self.r.render(c, self.scene, return_aux=True, fine_tiles=fine)
-        return img.cpu().numpy(), aux.cpu().numpy()
+        o = None if out is None else self.torch.from_numpy(np.ascontiguousarray(out, np.float32)).to("cuda:0")
+        oa = None if out_aux is None else self.torch.from_numpy(np.ascontiguousarray(out_aux, np.float32)).to("cuda:0")
+        img, aux = self.r.render(c, self.scene, config=self._config(cfg), out=o, out_aux=oa, return_aux=True,
+                                 tile_rows=None if rows == (0, -1) else rows, deep_cull=deep, stats=stats, fine_tiles=fine)
+        return img.cpu().numpy(), aux.cpu().numpy(), self.r.last_stats
 
     def intermediates(self):
         return self.r.intermediates()
@@ -136,6 +145,10 @@ def test_needle_extents_follow_the_rounded_conic(drv):
     pc.case_fuzz(drv, range(3003, 3010), 3000, (2400, 1400), wild=True)
 
 
+def test_seeded_random_frames_over_a_background_with_depth_and_coverage(drv):
+    pc.case_fuzz_variants(drv, range(9100, 9112))
+
+
 def test_non_finite_gaussians_are_invisible_and_harmless(drv):
     pc.case_non_finite_gaussians(drv)
     pc.case_non_finite_gaussians(drv, n=700, res=(96, 64), seed=4)
@@ -183,7 +196,7 @@ def test_deep_tile(drv):
 
 
 def test_full_grid_splat(drv):
-    pc.case_full_grid_splat(drv, res=(1920, 1080))
+    pc.case_full_grid_splat(drv, res=(1920, 1080), variants=True)
     pc.case_full_grid_splat(drv, res=(3840, 2160))
 
 
@@ -701,6 +714,94 @@ def test_pipelined_frames_equal_sequential_frames(drv):
         for k in range(4):
             assert (outs[k] == seq[k]).all()
     scene.free()
+
+
+def test_asynchronous_rgbd_frames_equal_synchronous_frames(drv):
+    """sgs_render_rgbd with SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED: eight cameras in flight on the library's lanes, each with its own `out`
+    and `out_aux` (pre-filled), every other one over a background — after ONE sync() every RGB and every depth / coverage buffer equals
+    the synchronous render bit for bit (nothing written late, nothing written into another lane's frame), twice (warm lanes)."""
+    import torch
+    from sage_gs import RenderConfig, scenes
+    sc = scenes.make_room(150_000, seed=6)
+    cams = scenes.room_cameras(sc, 800, 608, n_positions=2, n_yaw=4, seed=6)
+    assert len(cams) == 8
+    scene = drv.r.upload(scenes.to_gaussians(sc, "cuda:0"))
+    cfg_of = lambda i: RenderConfig(background=pc.BG) if i % 2 else None
+    want = []
+    for i, c in enumerate(cams):
+        rgb, aux = drv.r.render(c, scene, config=cfg_of(i), return_aux=True)
+        want.append((rgb.clone(), aux.clone()))
+        assert (drv.r.render(c, scene, config=cfg_of(i)) == rgb).all(), "the AUX instantiation changed the colours"
+    for rep in range(2):
+        outs = [(torch.full((608, 800, 3), pc.SENTINEL, device="cuda:0"), torch.full((608, 800, 2), pc.SENTINEL, device="cuda:0")) for _ in cams]
+        for i, (c, (o, oa)) in enumerate(zip(cams, outs)):
+            drv.r.render(c, scene, config=cfg_of(i), out=o, out_aux=oa, sync=False, pipelined=True)
+        st = drv.r.sync()
+        assert st["d_total"] > 0
+        for i, ((o, oa), (w_rgb, w_aux)) in enumerate(zip(outs, want)):
+            assert (o == w_rgb).all() and (oa == w_aux).all(), f"round {rep}: pipelined RGB-D frame {i} differs from the synchronous one"
+    assert (want[0][1][..., 1] > 0.5).any() and (want[1][0] != drv.r.render(cams[1], scene)).any()
+    # ... and render_batch over a background (the TF instantiation with one frame per blockIdx.y) equals the frames rendered alone
+    batch = drv.r.render_batch(cams, scene, config=RenderConfig(background=pc.BG))
+    for i, c in enumerate(cams):
+        assert (batch[i] == drv.r.render(c, scene, config=RenderConfig(background=pc.BG))).all(), f"frame {i} of a batch over a background differs from the frame alone"
+    scene.free()
+
+
+# ---- the TF and AUX instantiations at scale ----------------------------------------------------------------------------------------
+def _variants_at_scale(drv, sc, ocam, what, fine=False):
+    """check_variants_against_oracle on a frame of a full-size scene uploaded in `drv`: the black-background frame is first held to the
+    oracle (image and counts), as the shared check presumes."""
+    img, st = drv.render(ocam, stats=False, fine=False)
+    ref, aux = oracle_c.render(*sc.as_tuple(), ocam, want="image")
+    assert st["n_visible"] == aux["n_visible"]
+    assert_frame_close(img, ref, aux["margin"], aux["recheck"], what=what)
+    assert_frame_tight(img, ref, aux, what=what)
+    aux["recheck"].close()
+    v = pc.check_variants_against_oracle(drv, sc.as_tuple(), ocam, what=what, fine=fine)
+    assert (v["img0"] == img).all()
+    return v
+
+
+def test_3m_scene_background_and_rgbd_vs_oracle(drv, big_scene):
+    """BASELINE configs[2] (make_room(3 000 000, seed 2), SH degree 3): the TF and AUX instantiations of the composite — a background of
+    (0.25, 0.5, 0.75), the depth / coverage outputs — against the oracle rendered with the same config, whole frames: 1920x1080 at two
+    poses of the bench's sweep (129, the slowest, and 77), 640x480 (through 16x16-pixel tiles and through the fine tiles, forced; and the
+    tiling the library picks there by itself is one of the two, bit for bit) and 3840x2160 (one pose of the yaw sweep)."""
+    from sage_gs import scenes
+    sc, _ = big_scene
+    drv.upload(*sc.as_tuple())
+    cams = scenes.room_cameras(sc, 1920, 1080, n_positions=4, n_yaw=64, seed=2)
+    for pid in (129, 77):
+        _variants_at_scale(drv, sc, _ocam(cams[pid], sc), f"3M @1080p bench pose {pid} (TF / AUX)")
+    ocam = _ocam(scenes.room_cameras(sc, 640, 480, n_positions=4, n_yaw=64, seed=2)[129], sc)
+    v = _variants_at_scale(drv, sc, ocam, "3M @640x480 pose 129 (TF / AUX)", fine=True)
+    assert "fine" in v and v["st_aux"]["max_tile_len"] > 4096
+    rgb_d, aux_d, st_d = drv.render_aux(ocam, pc.with_background(None, pc.BG))          # the library's own choice of tiling
+    pick = v if st_d["n_tiles"] == v["st_aux"]["n_tiles"] else v["fine"] if st_d["n_tiles"] == v["fine"]["st_aux"]["n_tiles"] else None
+    assert pick is None or ((rgb_d == pick["img_bg"]).all() and (aux_d == pick["aux"]).all()), "the default tiling's RGB-D frame is not that tiling's frame"
+    cam4k = scenes.sweep_cameras(sc, 3840, 2160, n=360, seed=2)[77]
+    _variants_at_scale(drv, sc, _ocam(cam4k, sc), "3M @3840x2160 sweep pose 77 (TF / AUX)")
+
+
+def test_trained_like_3m_background_and_rgbd_vs_oracle(drv):
+    """The trained-like 3 M scene (D = 28 M records at 1080p) at pose 129 of the bench's sweep through the TF and AUX instantiations."""
+    from sage_gs import scenes
+    sc = scenes.make_trained_like(3_000_000, seed=2)
+    cams = scenes.room_cameras(sc, 1920, 1080, n_positions=4, n_yaw=64, seed=2)
+    drv.set_record_capacity(96 << 20)
+    drv.upload(*sc.as_tuple())
+    v = _variants_at_scale(drv, sc, _ocam(cams[129], sc), "trained-like 3M @1080p pose 129 (TF / AUX)")
+    assert v["st_aux"]["d_total"] > 10_000_000
+
+
+def test_room_500k_background_and_rgbd_vs_oracle(drv):
+    """BASELINE configs[1] (make_room(500 000, seed 1), 1920x1080): one pose through the TF and AUX instantiations."""
+    from sage_gs import scenes
+    sc = scenes.make_room(500_000, seed=1)
+    cams = scenes.room_cameras(sc, 1920, 1080, n_positions=2, n_yaw=8, seed=1)
+    drv.upload(*sc.as_tuple())
+    _variants_at_scale(drv, sc, _ocam(cams[2], sc), "config2 500k cam 2 (TF / AUX)")
 
 
 def test_pack_rgba8(drv):
