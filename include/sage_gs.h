@@ -346,6 +346,51 @@ int sgs_render_mesh_depth(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* 
 int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams,
                                 const sgs_config* cfg, float* out_depth, sgs_stats* stats, void* hip_stream);
 
+/* ---- Baseline JPEG encoding of rendered frames — replaces Image.fromarray(rgb).save(path) of the data-generation loop
+ * (generate_images.py:431-432) and the JPEG encoding of every observation the VLM client sends (vlm_client_modular.py:346-351): the file
+ * is made on the device from the fp32 frame sgs_render* left there, and only its bytes cross the link.  No new version: no existing
+ * struct changes.
+ *
+ *   Picture  each channel becomes the 8-bit level sgs_pack_rgba8 would write (clamp to [0,1], (unsigned)(x * 255 + 0.5)); YCbCr by the
+ *            JFIF full-range BT.601 matrix and the level shift in fp32, never rounded to 8 bits in between; 4:2:0 chroma is the plain
+ *            mean of 2x2 pixels; pixels beyond the right / bottom edge of a partial MCU repeat the last column / row; 8x8 DCT-II in fp32;
+ *            the Annex K tables of ITU-T T.81 scaled by `quality` with the IJG rule (what libjpeg and PIL write for the same quality);
+ *            one rounding per coefficient, F / Q to nearest, halves away from zero; the four Annex K Huffman tables.
+ *   File     SOI, JFIF APP0, DQT x 2, SOF0, DHT x 4, DRI, SOS, entropy-coded data with 0xFF stuffing and RSTn markers, EOI: 629 header
+ *            bytes.  The restart interval is 48 blocks (8 MCUs of 4:2:0, 16 of 4:4:4): every interval is coded by its own wave.
+ *   Exact    the bytes of a frame depend on its pixels and the parameters alone — not on the batch it is issued in or its place there. */
+enum { SGS_JPEG_420 = 0, SGS_JPEG_444 = 1 };       /* sgs_jpeg_params.subsampling */
+typedef struct sgs_jpeg_params {
+    int32_t quality;       /* 1..100 */
+    int32_t subsampling;   /* SGS_JPEG_420 (what PIL's save() does by default, hence what the reference's files are) or SGS_JPEG_444 */
+    uint32_t flags;        /* none defined: 0 */
+    int32_t reserved_;     /* 0 */
+} sgs_jpeg_params;
+/* quality 95, 4:2:0: what the sweep asks PIL for. */
+void sgs_jpeg_params_default(sgs_jpeg_params* params);
+/* The most bytes one frame's file can take, or SGS_ERR_INVALID.  Derivation: 629 header bytes + per restart interval of 48 blocks
+ * 2 x ceil(48 x 1658 / 8) + 2, where 1658 bits is the longest a block can be coded (DC: 9-bit code + 11 amplitude bits; each of the 63
+ * AC coefficients: 16-bit code + 10 amplitude bits), the factor 2 is every byte being 0xFF and stuffed, and + 2 is the RSTn / EOI
+ * marker.  No picture comes near it (it is ~2.5x the fp32 frame's third); buffers of this size per frame never overflow. */
+int64_t sgs_jpeg_bound(int width, int height, const sgs_jpeg_params* params);
+/* Encodes n_frames frames: rgb is a DEVICE buffer, frame i at rgb + i * rgb_frame_stride (floats), height*width*3 floats each as
+ * sgs_render* writes them.  The files are laid end to end in `out`: file i is out[out_offsets[i] .. + out_sizes[i]).  out, out_offsets
+ * and out_sizes (n_frames entries each) are device buffers or pinned host memory the device can address, as for sgs_pack_rgba8.
+ * Stream-ordered and asynchronous: the call does not synchronise (it may, once, when it first sees a parameter set or grows its
+ * scratch), so the encode of one chunk runs beside the render of the next; one encode stream at a time per context.
+ * Nothing is ever written at or beyond out + out_capacity: a frame whose file would end beyond it is not written at all, offsets and
+ * sizes are reported all the same (what a buffer that fits needs), and sgs_jpeg_status says so after the stream has been
+ * synchronised; the caller retries with a larger buffer.  The library owns 12 bytes of scratch per restart interval (grown
+ * geometrically) and one small table per parameter set, freed by sgs_destroy.
+ * SGS_ERR_INVALID: quality outside 1..100, an unknown subsampling, width or height < 1 or > 65535, n_frames < 0, a null buffer, a
+ * negative capacity, frames closer together than their size. */
+int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
+                    const sgs_jpeg_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
+                    void* hip_stream);
+/* After the stream of the most recent sgs_encode_jpeg has been synchronised: SGS_OK, or SGS_ERR_OVERFLOW when its files did not fit;
+ * bytes_needed (nullable) receives the bytes they take end to end. */
+int sgs_jpeg_status(sgs_ctx* ctx, int64_t* bytes_needed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 #include "../../include/sage_gs.h"
 #include "sgs_kernels.h"
 #include "sgs_mesh.h"
+#include "sgs_jpeg.h"
 
 namespace {
 
@@ -111,6 +112,17 @@ struct MeshScratch {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+// The JPEG encoder's scratch (sgs_encode_jpeg): per-interval lengths and offsets, the tables of the parameter sets seen so far (a
+// table is never rewritten: an encode still in flight on another stream keeps reading its own) and the pinned status words.
+struct JpegScratch {
+    struct Entry { int width, height, quality, s420; sgs::JpegTables* dev; };
+    std::vector<Entry> tables;
+    int64_t cap = 0;                         // intervals the two arrays hold
+    unsigned* sizes = nullptr;
+    long long* offs = nullptr;
+    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
+};
+
 struct sgs_mesh {
     int64_t n_verts = 0, n_tris = 0;
     float* verts = nullptr;
@@ -120,6 +132,7 @@ struct sgs_mesh {
 struct sgs_ctx {
     int device = 0;
     MeshScratch mesh;
+    JpegScratch jpeg;
     std::string err;
     Lane lanes[kMaxLanes];
     int n_lanes = 3, next_lane = 0;          // sgs_tuning.lanes: lanes that SGS_FLAG_PIPELINED single frames rotate over
@@ -757,6 +770,13 @@ int sgs_destroy(sgs_ctx* ctx) {
         for (void* b : bufs) if (b) (void)hipFree(b);
         if (M.h_st) (void)hipHostFree(M.h_st);
         for (hipEvent_t e : M.ev) if (e) (void)hipEventDestroy(e);
+    }
+    {
+        JpegScratch& Z = ctx->jpeg;
+        for (JpegScratch::Entry& e : Z.tables) if (e.dev) (void)hipFree(e.dev);
+        if (Z.sizes) (void)hipFree(Z.sizes);
+        if (Z.offs) (void)hipFree(Z.offs);
+        if (Z.h_status) (void)hipHostFree(Z.h_status);
     }
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->row_acc) (void)hipFree(ctx->row_acc);
@@ -1665,6 +1685,122 @@ int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_ca
     if (!ctx) return SGS_ERR_INVALID;
     if (!cams || n_cams < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "no cameras");
     return mesh_frames(ctx, mesh, cams, n_cams, cfg, 0, -1, out_depth, (int64_t)cams[0].width * cams[0].height, stats, hip_stream);
+}
+
+}  // extern "C"
+
+// ---- JPEG encoder (csrc/sgs_jpeg.h) ------------------------------------------------------------------------------------------------
+namespace {
+
+struct JpegGeom { int s420, mcus_x, mcus_y, n_mcu, ri, n_int; };
+
+bool jpeg_geom(int width, int height, const sgs_jpeg_params* p, JpegGeom& g) {
+    if (!p || p->quality < 1 || p->quality > 100 || (p->subsampling != SGS_JPEG_420 && p->subsampling != SGS_JPEG_444) ||
+        width < 1 || height < 1 || width > 65535 || height > 65535)
+        return false;
+    g.s420 = p->subsampling == SGS_JPEG_420;
+    const int mcu = g.s420 ? 16 : 8;
+    g.mcus_x = (width + mcu - 1) / mcu; g.mcus_y = (height + mcu - 1) / mcu;
+    g.n_mcu = g.mcus_x * g.mcus_y;
+    g.ri = SGS_JPEG_BLOCKS / (g.s420 ? 6 : 3);
+    g.n_int = (g.n_mcu + g.ri - 1) / g.ri;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sgs_jpeg_params_default(sgs_jpeg_params* p) {
+    if (!p) return;
+    p->quality = 95; p->subsampling = SGS_JPEG_420; p->flags = 0; p->reserved_ = 0;
+}
+
+int64_t sgs_jpeg_bound(int width, int height, const sgs_jpeg_params* params) {
+    JpegGeom g;
+    if (!jpeg_geom(width, height, params, g)) return SGS_ERR_INVALID;
+    return SGS_JPEG_HEADER + (int64_t)g.n_int * (2 * SGS_JPEG_INT_BYTES + 2);
+}
+
+int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
+                    const sgs_jpeg_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
+                    void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (!params) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: params is NULL");
+    if (params->quality < 1 || params->quality > 100) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: quality %d is outside 1..100", params->quality);
+    if (params->subsampling != SGS_JPEG_420 && params->subsampling != SGS_JPEG_444)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: subsampling %d is neither SGS_JPEG_420 nor SGS_JPEG_444", params->subsampling);
+    if (width < 1 || height < 1 || width > 65535 || height > 65535)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: %d x %d is outside 1..65535", width, height);
+    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: n_frames = %d", n_frames);
+    if (!rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null rgb");
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out");
+    if (!out_offsets) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out_offsets");
+    if (!out_sizes) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out_sizes");
+    if (out_capacity < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: out_capacity %lld is negative", (long long)out_capacity);
+    if (n_frames > 1 && rgb_frame_stride < (int64_t)width * height * 3)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: frames overlap (stride %lld floats)", (long long)rgb_frame_stride);
+    JpegGeom g;
+    jpeg_geom(width, height, params, g);
+    const int64_t n = (int64_t)n_frames * g.n_int;
+    if (n > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: %lld restart intervals in one call (at most 2^31 - 1)", (long long)n);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    JpegScratch& Z = ctx->jpeg;
+    if (!Z.h_status) {
+        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&Z.h_status), 2 * sizeof(long long), 0));
+        Z.h_status[0] = Z.h_status[1] = 0;
+    }
+    if (n_frames == 0) {                                   // nothing to encode: the status is this call's, not the previous one's
+        Z.h_status[0] = 0; Z.h_status[1] = out_capacity;
+        return SGS_OK;
+    }
+    sgs::JpegTables* tab = nullptr;
+    for (const JpegScratch::Entry& e : Z.tables)
+        if (e.width == width && e.height == height && e.quality == params->quality && e.s420 == g.s420) tab = e.dev;
+    if (!tab) {
+        sgs::JpegTables T;
+        memset(&T, 0, sizeof T);
+        sgs::jpeg::build_tables(T, width, height, params->quality, g.s420 != 0, g.ri);
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&tab), sizeof T));
+        const hipError_t e = hipMemcpy(tab, &T, sizeof T, hipMemcpyHostToDevice);      // (synchronous: T is on this stack)
+        if (e != hipSuccess) {
+            (void)hipFree(tab);
+            SGS_FAIL(ctx, SGS_ERR_HIP, "sgs_encode_jpeg: copying the tables: %s", hipGetErrorString(e));
+        }
+        // only a filled table is remembered.  The list is never trimmed: 4.3 KB of device memory per distinct (width, height, quality,
+        // subsampling) a context has encoded, until sgs_destroy — a handful in any real caller
+        Z.tables.push_back({width, height, params->quality, g.s420, tab});
+    }
+    if (n + 1 > Z.cap) {                                   // grows geometrically; hipFree waits for the encodes that still use the old arrays
+        const int64_t c = std::max<int64_t>(n + 1, 2 * Z.cap);
+        if (Z.sizes) { (void)hipFree(Z.sizes); Z.sizes = nullptr; }
+        if (Z.offs) { (void)hipFree(Z.offs); Z.offs = nullptr; }
+        Z.cap = 0;
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.sizes), (size_t)c * sizeof(unsigned)));
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.offs), (size_t)c * sizeof(long long)));
+        Z.cap = c;
+    }
+    sgs::JpegJob J;
+    J.rgb = rgb; J.frame_stride = rgb_frame_stride; J.width = width; J.height = height; J.s420 = g.s420;
+    J.mcus_x = g.mcus_x; J.n_mcu = g.n_mcu; J.ri = g.ri; J.n_int = g.n_int; J.n_frames = n_frames;
+    J.tab = tab; J.sizes = Z.sizes; J.offs = Z.offs; J.out = out; J.cap = out_capacity;
+    J.out_offsets = reinterpret_cast<long long*>(out_offsets); J.out_sizes = reinterpret_cast<long long*>(out_sizes);
+    J.status = Z.h_status;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(sgs::k_jpeg_intervals<false>, dim3((unsigned)n), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(sgs::k_jpeg_scan, dim3(1), dim3(SGS_JPEG_SCAN_THREADS), 0, st, J);
+    hipLaunchKernelGGL(sgs::k_jpeg_intervals<true>, dim3((unsigned)n), dim3(64), 0, st, J);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+int sgs_jpeg_status(sgs_ctx* ctx, int64_t* bytes_needed) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const JpegScratch& Z = ctx->jpeg;
+    const long long need = Z.h_status ? Z.h_status[0] : 0, cap = Z.h_status ? Z.h_status[1] : 0;
+    if (bytes_needed) *bytes_needed = need;
+    if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "sgs_encode_jpeg: the files take %lld bytes, out_capacity was %lld", need, cap);
+    return SGS_OK;
 }
 
 }  // extern "C"

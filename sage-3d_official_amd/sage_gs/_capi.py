@@ -31,7 +31,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_set_record_capacity", "sgs_scene_upload", "sgs_scene_upload_compressed", "sgs_scene_free", "sgs_render",
            "sgs_render_rgbd", "sgs_render_batch", "sgs_render_batch_strided", "sgs_frame_sync", "sgs_row_records", "sgs_pack_rgba8", "sgs_debug_read",
            "sgs_tuning_default", "sgs_set_tuning", "sgs_get_tuning",
-           "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch")
+           "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch",
+           "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status")
 
 
 class SgsError(RuntimeError):
@@ -61,6 +62,24 @@ class SgsTuning(C.Structure):
     """include/sage_gs.h sgs_tuning: the library's whole tuning surface (it reads nothing from the environment)."""
     _fields_ = [("lanes", C.c_int32), ("group", C.c_int32), ("group_lanes", C.c_int32), ("morton", C.c_int32),
                 ("record_capacity", C.c_int64), ("fine_tile_pixels", C.c_int64), ("fine_tile_growth", C.c_double)]
+
+
+JPEG_420, JPEG_444 = 0, 1
+JPEG_SUBSAMPLING = {"4:2:0": JPEG_420, "4:4:4": JPEG_444}
+
+
+class SgsJpegParams(C.Structure):
+    """include/sage_gs.h sgs_jpeg_params."""
+    _fields_ = [("quality", C.c_int32), ("subsampling", C.c_int32), ("flags", C.c_uint32), ("reserved_", C.c_int32)]
+
+
+def jpeg_params(quality=95, subsampling="4:2:0"):
+    """sgs_jpeg_params of a quality and a subsampling given as "4:2:0" / "4:4:4" (or SGS_JPEG_* itself)."""
+    if isinstance(subsampling, str):
+        if subsampling not in JPEG_SUBSAMPLING:
+            raise ValueError("subsampling must be '4:2:0' or '4:4:4'")
+        subsampling = JPEG_SUBSAMPLING[subsampling]
+    return SgsJpegParams(int(quality), int(subsampling), 0, 0)
 
 
 class SgsStats(C.Structure):
@@ -135,6 +154,10 @@ class Lib:
         lib.sgs_mesh_set_record_capacity.argtypes = [vp, i64]
         lib.sgs_render_mesh_depth.argtypes = [vp, vp, C.POINTER(SgsCamera), C.POINTER(SgsConfig), i32, i32, vp, C.POINTER(SgsStats), vp]
         lib.sgs_render_mesh_depth_batch.argtypes = [vp, vp, vp, i32, C.POINTER(SgsConfig), vp, vp, vp]
+        lib.sgs_jpeg_params_default.argtypes = [C.POINTER(SgsJpegParams)]; lib.sgs_jpeg_params_default.restype = None
+        lib.sgs_jpeg_bound.argtypes = [i32, i32, C.POINTER(SgsJpegParams)]; lib.sgs_jpeg_bound.restype = i64
+        lib.sgs_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsJpegParams), vp, i64, vp, vp, vp]
+        lib.sgs_jpeg_status.argtypes = [vp, C.POINTER(i64)]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -78,6 +78,12 @@ class GsCamera:
         img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config)
         return img.copy() if copy else img
 
+    def get_jpeg(self, quality: int = 75) -> bytes:
+        """The current view as the bytes of a baseline JPEG file — the picture get_rgba() returns, encoded on the GPU
+        (Renderer.encode_jpeg): for callers shaped like the VLM client, which JPEG-encodes every observation before it leaves the
+        process (vlm_client_modular.py:346-351)."""
+        return self._r.encode_jpeg(self.get_rgb_tensor(), quality=quality)[0]
+
     def _mesh_depth(self):
         """depth [H,W] float32 on the GPU: distance to the image plane of the nearest collision-mesh triangle, +inf where none."""
         return self._r.render_mesh_depth(self._camera(), self._mesh, config=self._mesh_config)

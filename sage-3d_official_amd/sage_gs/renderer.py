@@ -561,6 +561,55 @@ class Renderer:
             h = ring.submit(rgb, tonemap=tonemap, direct=True)
         return h.wait()
 
+    # -- JPEG files made on the device (include/sage_gs.h sgs_encode_jpeg) ------------------------------------------------------
+    def _jpeg_frames_of(self, rgb: torch.Tensor) -> torch.Tensor:
+        if rgb.dim() == 3:
+            rgb = rgb.unsqueeze(0)
+        if (rgb.device != self.device or rgb.dtype != torch.float32 or rgb.dim() != 4 or rgb.shape[-1] != 3
+                or (rgb.shape[0] > 0 and not rgb[0].is_contiguous())):
+            raise ValueError("rgb must be float32 [H,W,3] or [B,H,W,3] on the renderer's device with contiguous frames")
+        return rgb
+
+    def _encode_jpeg_into(self, rgb: torch.Tensor, n: int, params, out: torch.Tensor, meta: torch.Tensor):
+        """sgs_encode_jpeg of the first n frames of rgb [B,H,W,3] on the current stream: files into `out` (uint8, device), offsets and
+        sizes into the pinned int64 [2, >= n] `meta`.  Does not synchronise."""
+        h, w = int(rgb.shape[1]), int(rgb.shape[2])
+        self._lib.check(self._lib.sgs_encode_jpeg(self._ctx, rgb.data_ptr(), w, h, int(n), int(rgb.stride(0)) if rgb.shape[0] > 1 else h * w * 3,
+                                                  C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
+                                                  self._stream()), self._ctx)
+
+    def encode_jpeg(self, rgb: torch.Tensor, quality: int = 95, subsampling: str = "4:2:0") -> list:
+        """Baseline JPEG files (bytes, one per frame) of float32 [H,W,3] or [B,H,W,3] frames on the device, encoded there: what
+        Image.fromarray(get_rgba()[:, :, :3]).save(f, quality=quality) writes for the same picture, same tables, same default
+        subsampling (generate_images.py:431-432; vlm_client_modular.py:346-351).  Synchronous: the simple form; jpeg_frames() is the
+        pipelined one.  A frame's bytes do not depend on the batch it is encoded in."""
+        rgb = self._jpeg_frames_of(rgb)
+        n = int(rgb.shape[0])
+        if n == 0:
+            return []
+        params = _capi.jpeg_params(quality, subsampling)
+        cap = n * max(1 << 16, int(rgb.shape[1]) * int(rgb.shape[2]))         # a byte a pixel: several times a photographic frame at q95
+        meta = torch.zeros((2, n), dtype=torch.int64, pin_memory=True)
+        while True:
+            out = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+            self._encode_jpeg_into(rgb, n, params, out, meta)
+            torch.cuda.current_stream(self.device).synchronize()
+            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
+            if total <= cap:
+                break
+            cap = total                                                       # did not fit: the sizes say what does
+        host = out[:total].cpu().numpy()
+        return [host[int(o):int(o) + int(z)].tobytes() for o, z in zip(meta[0].tolist(), meta[1].tolist())]
+
+    def jpeg_frames(self, shape, quality: int = 95, subsampling: str = "4:2:0", depth: int = 3) -> "JpegFrames":
+        """A ring of `depth` pinned byte buffers (+ device twins, a copy stream, events) for chunks of up to shape[0] frames of
+        shape[1] x shape[2] pixels — JPEG's counterpart of host_frames().  Cached per argument set."""
+        key = (tuple(int(v) for v in shape[:3]), int(quality), str(subsampling), int(depth))
+        rings = self.__dict__.setdefault("_jpeg_rings", {})
+        if key not in rings:
+            rings[key] = JpegFrames(self, key[0], key[1], key[2], key[3])
+        return rings[key]
+
     # -- test hooks -------------------------------------------------------------------------------
     def debug_buffer(self, what, dtype):
         have = self._lib.sgs_debug_read(self._ctx, what, None, 0)
@@ -735,6 +784,71 @@ class HostFrames:
             self._host[k].copy_(self._dev[k], non_blocking=True)
             self._done[k].record(self._copy_stream)
         return HostFrames.Handle(self, k, n)
+
+
+class JpegFrames:
+    """`depth` slots of (device byte buffer, pinned byte buffer, pinned offsets / sizes), a copy stream and events.
+    submit(rgb, n) encodes the first n frames on the CURRENT stream (sgs_encode_jpeg, asynchronous) and returns a handle; wait() on it
+    blocks the host until THAT encode is done, copies only the bytes the files take into the slot's pinned buffer on the copy stream,
+    waits for the copy and returns one memoryview per frame, valid until the slot comes round again (depth submits later).  The copy
+    overlaps only GPU work that was enqueued BEFORE wait() was called: a caller that wants the pipeline enqueues the next chunk's
+    rendering first and waits for this chunk afterwards, as sweep.run does.  rgb must stay as it is until wait() has returned: should the files not fit the
+    slot (it starts at a byte a pixel), wait() grows it and encodes them again."""
+
+    class Handle:
+        def __init__(self, ring, k, rgb, n):
+            self._ring, self._k, self._rgb, self._n = ring, k, rgb, n
+
+        def wait(self, copy: bool = False) -> list:
+            ring, k, n = self._ring, self._k, self._n
+            if n == 0:
+                return []
+            ring._encoded[k].synchronize()
+            meta = ring._meta[k]
+            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
+            if total > ring._dev[k].numel():                                  # rare: the chunk is encoded again into a slot that fits
+                ring._grow(k, total)
+                ring._r._encode_jpeg_into(self._rgb, n, ring._params, ring._dev[k], meta)
+                ring._encoded[k].record(torch.cuda.current_stream(ring._r.device))
+                ring._encoded[k].synchronize()
+            with torch.cuda.stream(ring._copy_stream):
+                ring._host[k][:total].copy_(ring._dev[k][:total], non_blocking=True)
+            ring._copy_stream.synchronize()
+            self._rgb = None
+            view = memoryview(ring._host_np[k])
+            files = [view[int(o):int(o) + int(z)] for o, z in zip(meta[0, :n].tolist(), meta[1, :n].tolist())]
+            return [bytes(f) for f in files] if copy else files
+
+    def __init__(self, renderer: "Renderer", shape, quality: int, subsampling: str, depth: int):
+        self._r, self.shape, self.depth = renderer, tuple(shape), int(depth)
+        self._params = _capi.jpeg_params(quality, subsampling)
+        if not 1 <= self._params.quality <= 100:
+            raise ValueError("quality must be in 1..100")
+        cap = self.shape[0] * max(1 << 16, self.shape[1] * self.shape[2])
+        self._dev, self._host, self._host_np = [None] * self.depth, [None] * self.depth, [None] * self.depth
+        for k in range(self.depth):
+            self._grow(k, cap)
+        self._meta = [torch.zeros((2, self.shape[0]), dtype=torch.int64, pin_memory=True) for _ in range(self.depth)]
+        self._encoded = [torch.cuda.Event() for _ in range(self.depth)]
+        self._copy_stream = torch.cuda.Stream(device=renderer.device)
+        self._turn = 0
+
+    def _grow(self, k, cap):
+        self._dev[k] = torch.empty((int(cap),), dtype=torch.uint8, device=self._r.device)
+        self._host[k] = torch.empty((int(cap),), dtype=torch.uint8, pin_memory=True)
+        self._host_np[k] = self._host[k].numpy()
+
+    def submit(self, rgb: torch.Tensor, n: Optional[int] = None) -> "JpegFrames.Handle":
+        rgb = self._r._jpeg_frames_of(rgb)
+        n = int(rgb.shape[0]) if n is None else int(n)
+        if not 0 <= n <= min(int(rgb.shape[0]), self.shape[0]) or tuple(rgb.shape[1:3]) != self.shape[1:3]:
+            raise ValueError(f"the ring holds up to {self.shape[0]} frames of {self.shape[1]} x {self.shape[2]} pixels")
+        k = self._turn
+        self._turn = (k + 1) % self.depth
+        if n:
+            self._r._encode_jpeg_into(rgb, n, self._params, self._dev[k], self._meta[k])
+            self._encoded[k].record(torch.cuda.current_stream(self._r.device))
+        return JpegFrames.Handle(self, k, rgb, n)
 
 
 _default = {}

@@ -96,7 +96,7 @@ def cameras_for(points, resolution=CAMERA_RESOLUTION):
 
 
 def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESOLUTION, force=False, quality=95,
-        chunk=64, on_frame=None, write=True, encode_workers=8):
+        chunk=64, on_frame=None, write=True, encode_workers=8, encoder="pil"):
     """Renders every trajectory (one GPU batch per `chunk` poses) and writes the reference's output layout.
     on_frame(trajectory_id, index, rgb uint8 [H,W,3]) — optional — sees each frame as it is handed to the JPEG encoder
     (the array `cam.get_rgba()[:, :, :3]` would be in generate_images.py:428-432).  The array is a VIEW of a pinned ring buffer that
@@ -108,8 +108,15 @@ def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESO
     (generate_images.py:408-436).  write=False skips the encoder (throughput of the render + readback path alone).
     Back-pressure: at most 4 x encode_workers frames wait for (or are in) the encoder — the GPU produces several thousand frames/s, eight
     PIL threads encode 1-1.5 k/s, and every queued frame holds its own 2.4 MB (1024x768) copy: unbounded, a scene of a few thousand
-    waypoints held gigabytes per process.  The pool is shut down on every exit path."""
+    waypoints held gigabytes per process.  The pool is shut down on every exit path.
+    encoder="gpu": the files are made on the GPU from the fp32 frames (Renderer.jpeg_frames: same tables, same 4:2:0 as PIL's save at
+    this quality); only their bytes cross the link and the worker threads just write them.  The uint8 RGBA copy is then made only when
+    on_frame is given."""
     from concurrent.futures import ThreadPoolExecutor
+    if encoder not in ("pil", "gpu"):
+        raise ValueError("encoder must be 'pil' or 'gpu'")
+    gpu = encoder == "gpu" and write
+    want_rgba = not gpu or on_frame is not None
     os.makedirs(out_dir, exist_ok=True)
     w, h = int(resolution[0]), int(resolution[1])
     sequences, total = [], 0
@@ -122,18 +129,24 @@ def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESO
         from PIL import Image
         Image.fromarray(rgb).save(path, quality=quality)
 
+    def store(data, path):
+        with open(path, "wb") as f:
+            f.write(data)
+
     def drain(keep):
         while len(pending) > keep:
-            hnd, items = pending.pop(0)
-            host = hnd.wait()                                     # [chunk,H,W,4] pinned; valid until the ring comes round again
+            hnd, jhnd, items, seq = pending.pop(0)
+            host = hnd.wait() if hnd is not None else None        # [chunk,H,W,4] pinned; valid until the ring comes round again
+            files = jhnd.wait() if jhnd is not None else None     # views of the pinned bytes of this chunk's files: valid as long
             for k, (tid, idx, path) in enumerate(items):
-                rgb = host[k, :, :, :3]
+                rgb = host[k, :, :, :3] if host is not None else None
                 if on_frame is not None:
                     on_frame(tid, idx, rgb)
                 if pool is not None:
                     while len(jobs) >= max_jobs:
-                        jobs.pop(0).result()                      # the encoders are behind: wait for the oldest frame (its error surfaces here)
-                    jobs.append(pool.submit(encode, np.ascontiguousarray(rgb), path))
+                        jobs.pop(0)[1].result()                   # the encoders are behind: wait for the oldest frame (its error surfaces here)
+                    jobs.append((seq, pool.submit(store, files[k], path) if files is not None else
+                                 pool.submit(encode, np.ascontiguousarray(rgb), path)))
 
     try:
         # The scene's waypoints are ONE work list cut into chunks, whatever trajectory they belong to: a trajectory holds a dozen or two
@@ -159,18 +172,28 @@ def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESO
                               "sampling_info": {"sampled_points_count": len(names), "generated_images_count": len(names),
                                                 "data_source": "sage_gs.sweep"}})
         if work:
-            ring = renderer.host_frames((chunk, h, w, 4), depth=2)
-            frames = None
-            for c0 in range(0, len(work), chunk):
+            ring = renderer.host_frames((chunk, h, w, 4), depth=2) if want_rgba else None
+            jring = renderer.jpeg_frames((chunk, h, w), quality=quality, depth=3) if gpu else None
+            # the GPU encoder reads a chunk's fp32 frames until its handle has been waited for (one chunk later): two buffers take turns
+            fbufs = [None, None] if gpu else [None]
+            for seq, c0 in enumerate(range(0, len(work), chunk)):
                 part = work[c0:c0 + chunk]
                 drain(1)                                              # at most one copy in flight beside the batch being rendered
+                frames = fbufs[seq % len(fbufs)]
                 # [B,H,W,3] on the GPU; ONE pack and ONE device-to-host copy per chunk (B stacked images are one tall image)
-                frames = renderer.render_batch([it[2] for it in part], scene,
-                                               out=frames if frames is not None and frames.shape[0] >= len(part) else None)
-                buf = frames if frames.shape[0] == chunk else torch_pad(frames, chunk)
-                pending.append((ring.submit(buf, n=len(part)), [(it[0], it[1], it[3]) for it in part]))
+                frames = fbufs[seq % len(fbufs)] = renderer.render_batch(
+                    [it[2] for it in part], scene, out=frames if frames is not None and frames.shape[0] >= len(part) else None)
+                hnd = jhnd = None
+                if ring is not None:
+                    buf = frames if frames.shape[0] == chunk else torch_pad(frames, chunk)
+                    hnd = ring.submit(buf, n=len(part))
+                if jring is not None:
+                    while jobs and jobs[0][0] <= seq - jring.depth:   # the slot's previous files have been written before it is reused
+                        jobs.pop(0)[1].result()
+                    jhnd = jring.submit(frames, n=len(part))
+                pending.append((hnd, jhnd, [(it[0], it[1], it[3]) for it in part], seq))
         drain(0)
-        for j in jobs:
+        for _, j in jobs:
             j.result()                                            # (an encoder error surfaces here)
     finally:
         if pool is not None:
@@ -206,12 +229,17 @@ def main(argv=None):
     ap.add_argument("--width", type=int, default=CAMERA_RESOLUTION[0])
     ap.add_argument("--height", type=int, default=CAMERA_RESOLUTION[1])
     ap.add_argument("--force", action="store_true")
+    ap.add_argument("--encoder", choices=("pil", "gpu"), default="pil",
+                    help="who makes the .jpg files: PIL threads on the host (default), or the GPU (sgs_encode_jpeg)")
+    ap.add_argument("--quality", type=int, default=95, help="JPEG quality, 1..100 (generate_images.py writes PIL's default subsampling)")
     a = ap.parse_args(argv)
     if not 0 <= a.instance_id < a.total_instances:
         ap.error(f"instance_id({a.instance_id}) must be in range [0, {a.total_instances})")
     many = a.action_root is not None
     if many == (a.scene is not None) or (many and not a.scene_root) or (not many and not (a.actions and a.scene_id)):
         ap.error("give either --scene/--actions/--scene-id (one scene) or --action-root/--scene-root (many)")
+    if not 1 <= a.quality <= 100:
+        ap.error("--quality must be in 1..100")
     from . import ply, scenes
     from .renderer import Renderer
     import torch
@@ -231,7 +259,7 @@ def main(argv=None):
     for sid, path, comp, actions, out_dir in jobs:
         arrays = (ply.load_compressed_ply if comp else ply.load_ply)(path)
         scene = r.upload(ply.to_gaussians(arrays, dev, scenes.MODEL_TO_WORLD))      # template.usda:120
-        n = run(r, scene, load_trajectories(actions), sid, out_dir, (a.width, a.height), a.force)
+        n = run(r, scene, load_trajectories(actions), sid, out_dir, (a.width, a.height), a.force, quality=a.quality, encoder=a.encoder)
         scene.free()
         total += n
         print(f"[sage_gs.sweep] instance {a.instance_id + 1}/{a.total_instances}: scene {sid}: {n} frames -> {out_dir}")
