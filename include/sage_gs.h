@@ -391,6 +391,52 @@ int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n
  * bytes_needed (nullable) receives the bytes they take end to end. */
 int sgs_jpeg_status(sgs_ctx* ctx, int64_t* bytes_needed);
 
+/* ---- PNG encoding of depth and colour frames — replaces the 16-bit grey PNG the VLM client makes of every depth observation
+ * (vlm_client_modular.py:354-365: np.clip(depth, 0, 6.5) * 10000 -> uint16 -> PNG) and the frame_%05d.png sequence of an episode
+ * (simple_env.py:2757-2759): the file is made on the device from the fp32 frame, and only its bytes cross the link.  No new version: no
+ * existing struct changes.
+ *
+ *   Samples  SGS_PNG_RGB8: each channel becomes the 8-bit level sgs_pack_rgba8 would write: clamp to [0,1], (unsigned)(x * 255 + 0.5).
+ *            SGS_PNG_DEPTH16: v = (uint16) trunc(min(max(d, 0), depth_max) * depth_scale) — one fp32 multiply and a truncation, NumPy's
+ *            clip(d, 0, depth_max) * depth_scale -> astype(uint16); +inf (no triangle hit) becomes depth_max, -inf and NaN become 0;
+ *            stored big-endian.
+ *   File     signature, IHDR (bit depth 8 / colour type 2, or 16 / 0; no interlace), IDAT chunks, IEND, nothing else.  The image is
+ *            cut into strips of as many whole rows as fit 16 384 filtered bytes (at least one), one IDAT chunk per strip.  Every row
+ *            takes the filter (None, Sub, Up, Average, Paeth) with the least sum of its bytes' absolute values read as signed, ties to
+ *            the lowest type; the row above the image is zeros.  A strip is one deflate block — dynamic Huffman codes over literals and
+ *            run matches (distance 1, 3..258 bytes), or stored when that is no shorter — followed by an empty stored block, so every
+ *            strip ends byte-aligned and matches nothing before itself.  The first chunk carries the zlib header 78 01, the last the
+ *            final empty block and the Adler-32.
+ *   Exact    the bytes of a frame depend on its samples and the parameters alone — not on the batch it is issued in or its place there. */
+enum { SGS_PNG_RGB8 = 0, SGS_PNG_DEPTH16 = 1 };    /* sgs_png_params.format */
+typedef struct sgs_png_params {
+    int32_t format;        /* SGS_PNG_RGB8: src is fp32 [H,W,3]; SGS_PNG_DEPTH16: src is fp32 [H,W] (metres) */
+    float   depth_scale;   /* 10000 (vlm_client_modular.py:356) */
+    float   depth_max;     /* 6.5   (vlm_client_modular.py:355) */
+    int32_t reserved;      /* 0 */
+} sgs_png_params;
+/* SGS_PNG_RGB8, 10000, 6.5. */
+void sgs_png_params_default(sgs_png_params* params);
+/* The most bytes one frame's file can take, or SGS_ERR_INVALID.  Derivation, every strip stored: signature 8 + IHDR 25 + IEND 12 + zlib
+ * header 2 + final block 5 + Adler-32 4 = 56, plus per strip 12 bytes of chunk framing, 5 of the stored block's header and 5 of the empty
+ * block, plus the filtered bytes, height x (1 + width x bytes per pixel).  A strip that would code longer than stored is stored. */
+int64_t sgs_png_bound(int width, int height, const sgs_png_params* params);
+/* Encodes n_frames frames: src is a DEVICE buffer, frame i at src + i * src_frame_stride (floats), height*width*3 (RGB8) or height*width
+ * (DEPTH16) floats each.  Everything else is as for sgs_encode_jpeg: the files lie end to end in `out`, file i is
+ * out[out_offsets[i] .. + out_sizes[i]); out, out_offsets and out_sizes are device buffers or pinned host memory; the call is
+ * stream-ordered and does not synchronise (it may, when it grows its scratch); a frame whose file would end beyond out_capacity is not
+ * written at all, offsets and sizes are reported all the same, and sgs_png_status says so after the stream has been synchronised.  The
+ * library owns one slot of (strip + 16) bytes and 24 bytes per strip, grown geometrically and freed by sgs_destroy.
+ * SGS_ERR_INVALID: an unknown format, reserved != 0, a null buffer, n_frames < 0, a negative capacity, width or height < 1, height
+ * > 65535, a filtered row longer than 16 384 bytes (width > 5461 for RGB8, > 8191 for DEPTH16), for DEPTH16 depth_scale <= 0, depth_max
+ * <= 0 or depth_max * depth_scale > 65535 (in fp32), frames closer together than their size. */
+int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
+                   const sgs_png_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
+                   void* hip_stream);
+/* After the stream of the most recent sgs_encode_png has been synchronised: SGS_OK, or SGS_ERR_OVERFLOW when its files did not fit;
+ * bytes_needed (nullable) receives the bytes they take end to end. */
+int sgs_png_status(sgs_ctx* ctx, int64_t* bytes_needed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,7 @@
 #include "sgs_kernels.h"
 #include "sgs_mesh.h"
 #include "sgs_jpeg.h"
+#include "sgs_png.h"
 
 namespace {
 
@@ -123,6 +124,19 @@ struct JpegScratch {
     long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
 };
 
+// The PNG encoder's scratch (sgs_encode_png): a stored-size slot, a record and an offset per strip, an Adler-32 per frame, the pinned
+// status words.
+struct PngScratch {
+    int64_t cap = 0;                         // strips the record and offset arrays hold
+    sgs::PngStripRec* rec = nullptr;
+    long long* offs = nullptr;
+    int64_t slot_bytes = 0;
+    unsigned char* slots = nullptr;
+    int64_t frame_cap = 0;
+    unsigned* adler = nullptr;
+    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
+};
+
 struct sgs_mesh {
     int64_t n_verts = 0, n_tris = 0;
     float* verts = nullptr;
@@ -133,6 +147,7 @@ struct sgs_ctx {
     int device = 0;
     MeshScratch mesh;
     JpegScratch jpeg;
+    PngScratch png;
     std::string err;
     Lane lanes[kMaxLanes];
     int n_lanes = 3, next_lane = 0;          // sgs_tuning.lanes: lanes that SGS_FLAG_PIPELINED single frames rotate over
@@ -776,6 +791,12 @@ int sgs_destroy(sgs_ctx* ctx) {
         for (JpegScratch::Entry& e : Z.tables) if (e.dev) (void)hipFree(e.dev);
         if (Z.sizes) (void)hipFree(Z.sizes);
         if (Z.offs) (void)hipFree(Z.offs);
+        if (Z.h_status) (void)hipHostFree(Z.h_status);
+    }
+    {
+        PngScratch& Z = ctx->png;
+        void* bufs[] = {Z.rec, Z.offs, Z.slots, Z.adler};
+        for (void* b : bufs) if (b) (void)hipFree(b);
         if (Z.h_status) (void)hipHostFree(Z.h_status);
     }
     if (ctx->d_status) (void)hipFree(ctx->d_status);
@@ -1800,6 +1821,136 @@ int sgs_jpeg_status(sgs_ctx* ctx, int64_t* bytes_needed) {
     const long long need = Z.h_status ? Z.h_status[0] : 0, cap = Z.h_status ? Z.h_status[1] : 0;
     if (bytes_needed) *bytes_needed = need;
     if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "sgs_encode_jpeg: the files take %lld bytes, out_capacity was %lld", need, cap);
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- PNG encoder (csrc/sgs_png.h) -------------------------------------------------------------------------------------------------
+namespace {
+
+struct PngGeom { int depth16, bpp, row_bytes, rows_per_strip, n_strips; };
+
+// nullptr when the arguments describe a picture the encoder takes, else what is wrong with them.
+const char* png_geom(int width, int height, const sgs_png_params* p, PngGeom& g, char* why, size_t n_why) {
+    if (!p) { snprintf(why, n_why, "params is NULL"); return why; }
+    if (p->format != SGS_PNG_RGB8 && p->format != SGS_PNG_DEPTH16) {
+        snprintf(why, n_why, "format %d is neither SGS_PNG_RGB8 nor SGS_PNG_DEPTH16", p->format); return why;
+    }
+    if (p->reserved != 0) { snprintf(why, n_why, "reserved = %d, must be 0", p->reserved); return why; }
+    if (width < 1 || height < 1 || height > 65535) { snprintf(why, n_why, "%d x %d: width < 1 or height outside 1..65535", width, height); return why; }
+    g.depth16 = p->format == SGS_PNG_DEPTH16;
+    g.bpp = g.depth16 ? 2 : 3;
+    if ((int64_t)width * g.bpp + 1 > SGS_PNG_STRIP) {
+        snprintf(why, n_why, "width %d: a filtered row of %lld bytes is longer than %d", width, (long long)width * g.bpp + 1, SGS_PNG_STRIP); return why;
+    }
+    if (g.depth16) {
+        if (!(p->depth_scale > 0.f)) { snprintf(why, n_why, "depth_scale %g is not positive", (double)p->depth_scale); return why; }
+        if (!(p->depth_max > 0.f)) { snprintf(why, n_why, "depth_max %g is not positive", (double)p->depth_max); return why; }
+        const volatile float top = p->depth_max * p->depth_scale;              // the kernel's own fp32 product of the largest clamped depth
+        if (!(top <= 65535.0f)) {
+            snprintf(why, n_why, "depth_max * depth_scale = %.9g does not fit 16 bits", (double)top); return why;
+        }
+    }
+    g.row_bytes = width * g.bpp;
+    g.rows_per_strip = std::max(1, SGS_PNG_STRIP / (g.row_bytes + 1));
+    g.n_strips = (height + g.rows_per_strip - 1) / g.rows_per_strip;
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+void sgs_png_params_default(sgs_png_params* p) {
+    if (!p) return;
+    p->format = SGS_PNG_RGB8; p->depth_scale = 10000.0f; p->depth_max = 6.5f; p->reserved = 0;
+}
+
+int64_t sgs_png_bound(int width, int height, const sgs_png_params* params) {
+    PngGeom g;
+    char why[256];
+    if (png_geom(width, height, params, g, why, sizeof why)) return SGS_ERR_INVALID;
+    return 56 + (int64_t)g.n_strips * 22 + (int64_t)height * (g.row_bytes + 1);
+}
+
+int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
+                   const sgs_png_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
+                   void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    PngGeom g;
+    char why[256];
+    if (png_geom(width, height, params, g, why, sizeof why)) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: %s", why);
+    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: n_frames = %d", n_frames);
+    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null src");
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out");
+    if (!out_offsets) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out_offsets");
+    if (!out_sizes) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out_sizes");
+    if (out_capacity < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: out_capacity %lld is negative", (long long)out_capacity);
+    const int64_t frame_floats = (int64_t)width * height * (g.depth16 ? 1 : 3);
+    if (n_frames > 1 && src_frame_stride < frame_floats)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: frames overlap (stride %lld floats, a frame has %lld)", (long long)src_frame_stride,
+                 (long long)frame_floats);
+    const int64_t n = (int64_t)n_frames * g.n_strips;
+    if (n > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: %lld strips in one call (at most 2^31 - 1)", (long long)n);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    PngScratch& Z = ctx->png;
+    if (!Z.h_status) {
+        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&Z.h_status), 2 * sizeof(long long), 0));
+        Z.h_status[0] = Z.h_status[1] = 0;
+    }
+    if (n_frames == 0) {                                   // nothing to encode: the status is this call's, not the previous one's
+        Z.h_status[0] = 0; Z.h_status[1] = out_capacity;
+        return SGS_OK;
+    }
+    // scratch grows geometrically; hipFree waits for the encodes that still use the old arrays
+    if (n + 1 > Z.cap) {
+        const int64_t c = std::max<int64_t>(n + 1, 2 * Z.cap);
+        if (Z.rec) { (void)hipFree(Z.rec); Z.rec = nullptr; }
+        if (Z.offs) { (void)hipFree(Z.offs); Z.offs = nullptr; }
+        Z.cap = 0;
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.rec), (size_t)c * sizeof(sgs::PngStripRec)));
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.offs), (size_t)c * sizeof(long long)));
+        Z.cap = c;
+    }
+    const int64_t slot = (((int64_t)std::min(g.rows_per_strip, height) * (g.row_bytes + 1) + 16) + 15) & ~(int64_t)15;
+    if (n * slot > Z.slot_bytes) {
+        const int64_t c = std::max<int64_t>(n * slot, 2 * Z.slot_bytes);
+        if (Z.slots) { (void)hipFree(Z.slots); Z.slots = nullptr; }
+        Z.slot_bytes = 0;
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.slots), (size_t)c));
+        Z.slot_bytes = c;
+    }
+    if (n_frames > Z.frame_cap) {
+        const int64_t c = std::max<int64_t>(n_frames, 2 * Z.frame_cap);
+        if (Z.adler) { (void)hipFree(Z.adler); Z.adler = nullptr; }
+        Z.frame_cap = 0;
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.adler), (size_t)c * sizeof(unsigned)));
+        Z.frame_cap = c;
+    }
+    sgs::PngJob J;
+    memset(&J, 0, sizeof J);
+    J.src = src; J.frame_stride = src_frame_stride; J.width = width; J.height = height; J.depth16 = g.depth16;
+    J.scale = params->depth_scale; J.dmax = params->depth_max; J.bpp = g.bpp; J.row_bytes = g.row_bytes;
+    J.rows_per_strip = g.rows_per_strip; J.n_strips = g.n_strips; J.n_frames = n_frames;
+    J.slot = slot; J.slots = Z.slots; J.rec = Z.rec; J.offs = Z.offs; J.adler = Z.adler; J.out = out; J.cap = out_capacity;
+    J.out_offsets = reinterpret_cast<long long*>(out_offsets); J.out_sizes = reinterpret_cast<long long*>(out_sizes);
+    J.status = Z.h_status;
+    sgs::png::build_head(J.head, width, height, g.depth16 != 0);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    hipLaunchKernelGGL(sgs::k_png_strips, dim3((unsigned)n), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(sgs::k_png_scan, dim3(1), dim3(SGS_PNG_SCAN_THREADS), 0, st, J);
+    hipLaunchKernelGGL(sgs::k_png_gather, dim3((unsigned)n), dim3(SGS_PNG_GATHER_THREADS), 0, st, J);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+int sgs_png_status(sgs_ctx* ctx, int64_t* bytes_needed) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const PngScratch& Z = ctx->png;
+    const long long need = Z.h_status ? Z.h_status[0] : 0, cap = Z.h_status ? Z.h_status[1] : 0;
+    if (bytes_needed) *bytes_needed = need;
+    if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "sgs_encode_png: the files take %lld bytes, out_capacity was %lld", need, cap);
     return SGS_OK;
 }
 

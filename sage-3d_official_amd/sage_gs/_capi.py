@@ -32,7 +32,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_render_rgbd", "sgs_render_batch", "sgs_render_batch_strided", "sgs_frame_sync", "sgs_row_records", "sgs_pack_rgba8", "sgs_debug_read",
            "sgs_tuning_default", "sgs_set_tuning", "sgs_get_tuning",
            "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch",
-           "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status")
+           "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
+           "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status")
 
 
 class SgsError(RuntimeError):
@@ -80,6 +81,24 @@ def jpeg_params(quality=95, subsampling="4:2:0"):
             raise ValueError("subsampling must be '4:2:0' or '4:4:4'")
         subsampling = JPEG_SUBSAMPLING[subsampling]
     return SgsJpegParams(int(quality), int(subsampling), 0, 0)
+
+
+PNG_RGB8, PNG_DEPTH16 = 0, 1
+PNG_FORMAT = {"rgb8": PNG_RGB8, "depth16": PNG_DEPTH16}
+
+
+class SgsPngParams(C.Structure):
+    """include/sage_gs.h sgs_png_params."""
+    _fields_ = [("format", C.c_int32), ("depth_scale", C.c_float), ("depth_max", C.c_float), ("reserved", C.c_int32)]
+
+
+def png_params(format="rgb8", depth_scale=10000.0, depth_max=6.5):
+    """sgs_png_params of a format given as "rgb8" / "depth16" (or SGS_PNG_* itself)."""
+    if isinstance(format, str):
+        if format not in PNG_FORMAT:
+            raise ValueError("format must be 'rgb8' or 'depth16'")
+        format = PNG_FORMAT[format]
+    return SgsPngParams(int(format), float(depth_scale), float(depth_max), 0)
 
 
 class SgsStats(C.Structure):
@@ -158,6 +177,10 @@ class Lib:
         lib.sgs_jpeg_bound.argtypes = [i32, i32, C.POINTER(SgsJpegParams)]; lib.sgs_jpeg_bound.restype = i64
         lib.sgs_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsJpegParams), vp, i64, vp, vp, vp]
         lib.sgs_jpeg_status.argtypes = [vp, C.POINTER(i64)]
+        lib.sgs_png_params_default.argtypes = [C.POINTER(SgsPngParams)]; lib.sgs_png_params_default.restype = None
+        lib.sgs_png_bound.argtypes = [i32, i32, C.POINTER(SgsPngParams)]; lib.sgs_png_bound.restype = i64
+        lib.sgs_encode_png.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsPngParams), vp, i64, vp, vp, vp]
+        lib.sgs_png_status.argtypes = [vp, C.POINTER(i64)]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

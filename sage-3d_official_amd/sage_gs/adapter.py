@@ -84,6 +84,20 @@ class GsCamera:
         process (vlm_client_modular.py:346-351)."""
         return self._r.encode_jpeg(self.get_rgb_tensor(), quality=quality)[0]
 
+    def get_png(self) -> bytes:
+        """The current view as the bytes of an 8-bit RGB PNG file — exactly get_rgba()'s picture, encoded on the GPU
+        (Renderer.encode_png): a frame of the episode's frame_%05d.png sequence (simple_env.py:2757-2759)."""
+        return self._r.encode_png(self.get_rgb_tensor(), format="rgb8")[0]
+
+    def get_depth_png(self, clip=(0.1, 6.5)) -> bytes:
+        """The depth observation as the VLM client sends it (vlm_client_modular.py:355-365): a 16-bit grey PNG of
+        np.clip(get_depth(clip), 0, 6.5) * 10000 -> uint16, made on the GPU from the device depth — the fp32 frame does not cross the
+        link.  The lower clip bound is applied on the device before the encoder; its upper bound is the encoder's depth_max."""
+        import torch
+        depth = self._mesh_depth() if self._mesh is not None else self._rgb_depth()[1]
+        depth = torch.clamp(depth, min=float(clip[0])).contiguous()
+        return self._r.encode_png(depth, format="depth16", depth_scale=10000.0, depth_max=float(clip[1]))[0]
+
     def _mesh_depth(self):
         """depth [H,W] float32 on the GPU: distance to the image plane of the nearest collision-mesh triangle, +inf where none."""
         return self._r.render_mesh_depth(self._camera(), self._mesh, config=self._mesh_config)

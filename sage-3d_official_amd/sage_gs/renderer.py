@@ -610,6 +610,40 @@ class Renderer:
             rings[key] = JpegFrames(self, key[0], key[1], key[2], key[3])
         return rings[key]
 
+    # -- PNG files made on the device (include/sage_gs.h sgs_encode_png) --------------------------------------------------------
+    def encode_png(self, frames: torch.Tensor, format: str = "rgb8", depth_scale: float = 10000.0, depth_max: float = 6.5) -> list:
+        """PNG files (bytes, one per frame) of float32 frames on the device, encoded there.  format="rgb8": [H,W,3] or [n,H,W,3]
+        colour, the picture get_rgba() shows — what the episode's frame_%05d.png sequence holds (simple_env.py:2757-2759).
+        format="depth16": [H,W] or [n,H,W] metres as 16-bit grey, np.clip(d, 0, depth_max) * depth_scale -> uint16 — the depth.png
+        of the VLM client (vlm_client_modular.py:354-365).  Lossless; synchronous; a frame's bytes do not depend on the batch it is
+        encoded in."""
+        params = _capi.png_params(format, depth_scale, depth_max)
+        tail = 1 if params.format == _capi.PNG_RGB8 else 0
+        if frames.dim() == 2 + tail:
+            frames = frames.unsqueeze(0)
+        if (frames.device != self.device or frames.dtype != torch.float32 or frames.dim() != 3 + tail or (tail and frames.shape[-1] != 3)
+                or (frames.shape[0] > 0 and not frames[0].is_contiguous())):
+            raise ValueError("frames must be float32 [H,W,3] / [n,H,W,3] (rgb8) or [H,W] / [n,H,W] (depth16) on the renderer's device "
+                             "with contiguous frames")
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        if n == 0:
+            return []
+        frame_floats = h * w * (3 if tail else 1)
+        cap = n * max(1 << 12, frame_floats // 2)                             # half a byte a sample to begin with; the sizes say what fits
+        meta = torch.zeros((2, n), dtype=torch.int64, pin_memory=True)
+        while True:
+            out = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+            self._lib.check(self._lib.sgs_encode_png(self._ctx, frames.data_ptr(), w, h, n, int(frames.stride(0)) if n > 1 else frame_floats,
+                                                     C.byref(params), out.data_ptr(), cap, meta[0].data_ptr(), meta[1].data_ptr(),
+                                                     self._stream()), self._ctx)
+            torch.cuda.current_stream(self.device).synchronize()
+            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
+            if total <= cap:
+                break
+            cap = total                                                       # did not fit: SGS_ERR_OVERFLOW's figure
+        host = out[:total].cpu().numpy()
+        return [host[int(o):int(o) + int(z)].tobytes() for o, z in zip(meta[0].tolist(), meta[1].tolist())]
+
     # -- test hooks -------------------------------------------------------------------------------
     def debug_buffer(self, what, dtype):
         have = self._lib.sgs_debug_read(self._ctx, what, None, 0)
