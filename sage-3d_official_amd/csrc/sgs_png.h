@@ -168,17 +168,60 @@ __device__ inline void png_min_redundancy(unsigned* A, int n) {
     }
 }
 
+// How many codes of each length the optimal code within `limit` bits has (package-merge: Larmore & Hirschberg, "A fast algorithm for
+// optimal length-limited Huffman codes", 1990), for a small alphabet: F[0..n) the frequencies in ascending order, 2 <= n <= 32,
+// n <= 2^limit.  Level by level from the deepest, the items of a level are the leaves merged with the pairs of the level below (the
+// 2n - 2 cheapest are kept; a bit mask per level records which are leaves); going back from the top, a leaf among the items taken at a
+// level adds one bit to its symbol — always the rarest symbols first, so only the count per level is needed.  work: 256 words.
+__device__ inline void png_package_merge(const unsigned* F, int n, int limit, unsigned* num, unsigned* work) {
+    unsigned* prev = work, *cur = work + 64, *mask = work + 128, *len = work + 176;      // mask[2 lev], mask[2 lev + 1]
+    const int keep = 2 * n - 2;
+    int np = n;
+    for (int i = 0; i < n; ++i) { prev[i] = F[i]; len[i] = 0; }
+    mask[2 * limit] = n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; mask[2 * limit + 1] = 0;
+    for (int lev = limit - 1; lev >= 1; --lev) {
+        const int npk = np >> 1;
+        int a = 0, b = 0, t = 0;
+        unsigned m0 = 0, m1 = 0;
+        while (t < keep && (a < n || b < npk)) {
+            const unsigned pw = b < npk ? prev[2 * b] + prev[2 * b + 1] : 0xFFFFFFFFu;
+            if (a < n && F[a] <= pw) {
+                cur[t] = F[a++];
+                if (t < 32) m0 |= 1u << t; else m1 |= 1u << (t - 32);
+            } else { cur[t] = pw; ++b; }
+            ++t;
+        }
+        mask[2 * lev] = m0; mask[2 * lev + 1] = m1;
+        np = t;
+        unsigned* sw = prev; prev = cur; cur = sw;
+    }
+    int need = keep;
+    for (int lev = 1; lev <= limit && need > 0; ++lev) {
+        const unsigned lo = need >= 32 ? 0xFFFFFFFFu : (1u << need) - 1u, hi = need > 32 ? (need >= 64 ? 0xFFFFFFFFu : (1u << (need - 32)) - 1u) : 0u;
+        const int leaves = __popcll(((unsigned long long)(mask[2 * lev + 1] & hi) << 32) | (mask[2 * lev] & lo));
+        for (int i = 0; i < leaves && i < n; ++i) len[i]++;
+        need = 2 * (need - leaves);
+    }
+    for (int i = 0; i <= limit; ++i) num[i] = 0;
+    for (int i = 0; i < n; ++i) num[len[i]]++;
+}
+
 // Code lengths limited to `limit` bits and canonical codes for the n used symbols sym[0..n) whose frequencies A[0..n) are in ascending
 // order: lengths of the optimal code, lengths beyond the limit folded into it and the Kraft sum repaired by lengthening the deepest
-// shorter codes (the construction small deflaters use), the longest lengths to the rarest symbols.  tab[s] = reversed code | length << 16
-// for every symbol of the alphabet (0 for unused ones).  n >= 2.
-__device__ inline void png_build_code(unsigned* A, const unsigned short* sym, int n, int limit, unsigned* tab, int n_alphabet, unsigned* num) {
+// shorter codes (the construction small deflaters use), the longest lengths to the rarest symbols.  Given `work` (n <= 32, 320 words), an
+// optimal code deeper than the limit is replaced by the optimal code within it (png_package_merge) instead of being repaired.
+// tab[s] = reversed code | length << 16 for every symbol of the alphabet (0 for unused ones).  n >= 2.
+__device__ inline void png_build_code(unsigned* A, const unsigned short* sym, int n, int limit, unsigned* tab, int n_alphabet, unsigned* num,
+                                      unsigned* work = nullptr) {
     unsigned* nextc = num + 16;                            // num[0..16), nextc[0..16): the caller's (LDS, not a private array)
     for (int i = 0; i <= 15; ++i) num[i] = 0;
+    if (work) for (int i = 0; i < n; ++i) work[256 + i] = A[i];
     png_min_redundancy(A, n);
+    const bool too_deep = A[0] > (unsigned)limit;          // (the lengths are in descending order)
     for (int i = 0; i < n; ++i) num[A[i] < (unsigned)limit ? A[i] : (unsigned)limit]++;
     unsigned total = 0;
     for (int i = limit; i > 0; --i) total += num[i] << (limit - i);
+    if (work && too_deep) { png_package_merge(work + 256, n, limit, num, work); total = 1u << limit; }
     while (total > (1u << limit)) {
         num[limit]--;
         for (int i = limit - 1; i > 0; --i)
@@ -374,7 +417,7 @@ __global__ __launch_bounds__(64) void k_png_strips(PngJob J) {
             while (k > 0 && s_clA[k - 1] > fr) { s_clA[k] = s_clA[k - 1]; s_clsym[k] = s_clsym[k - 1]; --k; }
             s_clA[k] = fr; s_clsym[k] = (unsigned short)i;
         }
-        png_build_code(s_clA, s_clsym, ncl, 7, s_cltab, 19, s_num);
+        png_build_code(s_clA, s_clsym, ncl, 7, s_cltab, 19, s_num, s_key);      // (s_key is free: the literal / length code stands in s_tab)
         const unsigned char order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
         int hclen = 19;
         while (hclen > 4 && !(s_cltab[order[hclen - 1]] >> 16)) --hclen;

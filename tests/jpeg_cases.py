@@ -108,18 +108,21 @@ class AbiJpeg:
         p = self._capi.jpeg_params(quality, subsampling)
         return int(self.lib.sgs_jpeg_bound(int(w), int(h), C.byref(p)))
 
-    def encode(self, frames, quality, subsampling, capacity=None, slack=64):
+    def encode(self, frames, quality, subsampling, capacity=None, slack=64, stride=None):
         """frames fp32 [n,H,W,3].  Returns dict(files, offsets, sizes, buffer (capacity + slack bytes, SENTINEL-filled before the
-        call), capacity, rc (sgs_jpeg_status after synchronising), needed)."""
+        call), capacity, rc (sgs_jpeg_status after synchronising), needed).  stride: floats from one frame to the next (default: a
+        frame); the floats between frames are NaN and 1e30 in turn."""
         frames = np.asarray(frames, np.float32)
         n, h, w, _ = frames.shape
+        if stride is not None:
+            frames = strided(frames, stride)
         p = self._capi.jpeg_params(quality, subsampling)
         cap = n * self.bound(w, h, quality, subsampling) if capacity is None else int(capacity)
         keep_f, f_ptr = self._frames(frames)
         keep_o, o_ptr, o_get = self._bytes(cap + slack)
         keep_a, a_ptr, a_get = self._i64(n)
         keep_s, s_ptr, s_get = self._i64(n)
-        self.lib.check(self.lib.sgs_encode_jpeg(self.ctx, f_ptr, w, h, n, h * w * 3, C.byref(p), o_ptr, cap, a_ptr, s_ptr, None), self.ctx)
+        self.lib.check(self.lib.sgs_encode_jpeg(self.ctx, f_ptr, w, h, n, h * w * 3 if stride is None else int(stride), C.byref(p), o_ptr, cap, a_ptr, s_ptr, None), self.ctx)
         self._sync()
         need = C.c_int64(-1)
         rc = int(self.lib.sgs_jpeg_status(self.ctx, C.byref(need)))
@@ -132,6 +135,32 @@ class AbiJpeg:
         assert r["rc"] == 0, r["rc"]
         check_nothing_written_beyond(r)
         return r["files"][0]
+
+
+def strided(frames, stride):
+    """fp32 [n * stride]: frame i at i * stride, every float between and after the frames NaN or 1e30 in turn."""
+    n, size = frames.shape[0], int(np.prod(frames.shape[1:]))
+    assert stride >= size
+    buf = np.empty((n, int(stride)), np.float32)
+    buf[:, :size] = frames.reshape(n, size)
+    buf[:, size:] = np.where(np.arange(int(stride) - size) % 2 == 0, np.float32(np.nan), np.float32(1e30))
+    return buf.reshape(-1)
+
+
+def check_stride_and_long_scan(encode, frames, more_than, units_per_frame, **kw):
+    """A batch of more than `more_than` strips or intervals (the scan kernels then take several per thread): offsets, sizes and
+    nothing written beyond; the files of a batch whose frames lie a frame plus 37 floats apart are those of the packed batch byte for
+    byte; returns the packed batch."""
+    assert frames.shape[0] * units_per_frame > more_than, "the case proves too little: the scan takes one element per thread"
+    packed = encode(frames, **kw)
+    assert packed["rc"] == 0
+    check_nothing_written_beyond(packed)
+    padded = encode(frames, stride=int(np.prod(frames.shape[1:])) + 37, **kw)
+    assert padded["rc"] == 0
+    check_nothing_written_beyond(padded)
+    assert (padded["offsets"] == packed["offsets"]).all() and (padded["sizes"] == packed["sizes"]).all()
+    assert padded["files"] == packed["files"], "a padded frame stride changes the files"
+    return packed
 
 
 def check_nothing_written_beyond(r):

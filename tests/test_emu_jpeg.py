@@ -218,3 +218,17 @@ def test_jpeg_mutant_is_caught(mutant_libs, name):
 
 def test_the_unmutated_library_passes_the_mutants_checks(drv):
     _checks_1_and_2(drv)
+
+
+# ---- test 9: padded strides, long scans -----------------------------------------------------------------------------------------------
+def test_padded_stride_and_long_scan(drv):
+    """Frames a frame plus 37 floats apart (NaN and 1e30 between them) give the packed batch's files; a batch of 20 frames of 128x112
+    at 4:4:4 has 280 restart intervals, so that k_jpeg_scan's 256 threads take two each: offsets and sizes end to end, nothing written
+    beyond, every frame the bytes it gets alone."""
+    frames = np.stack([jc.gradient_noise(112, 128, seed=s) * (0.6 + 0.02 * s) for s in range(20)])
+    batch = jc.check_stride_and_long_scan(drv.encode, frames, 256, 14, quality=75, subsampling="4:4:4")
+    assert len(set(batch["files"])) == 20
+    for i in (0, 9, 10, 19):
+        assert drv.encode_one(frames[i], 75, "4:4:4") == batch["files"][i], f"frame {i} depends on the batch it is issued in"
+    jc.check_file(batch["files"][19], frames[19], 75, "4:4:4", label="long_scan_frame_19")
+    jc.check_stride_and_long_scan(drv.encode, frames[:3], 0, 4, quality=95, subsampling="4:2:0")

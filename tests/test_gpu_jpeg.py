@@ -245,3 +245,19 @@ def test_pipelined_ring_gives_the_synchronous_bytes(r):
     small._grow(0, 1000)
     assert [bytes(f) for f in small.submit(bufs[0][:2].clone()).wait()] == want[2][:2]          # (bufs[0] holds the third chunk)
     scene.free()
+
+
+def test_padded_stride_and_long_scan_on_the_gpu(r):
+    """test_emu_jpeg.py's test 9 through the GPU build, and its files against the emulator's (input on the levels)."""
+    from sage_gs import _capi
+    d = GpuJpeg(r)
+    frames = np.stack([jc.levels_of(jc.gradient_noise(112, 128, seed=s) * (0.6 + 0.02 * s)).astype(np.float32) / np.float32(255.0) for s in range(20)])
+    batch = jc.check_stride_and_long_scan(d.encode, frames, 256, 14, quality=75, subsampling="4:4:4")
+    for i in (0, 9, 10, 19):
+        assert d.encode_one(frames[i], 75, "4:4:4") == batch["files"][i], f"frame {i} depends on the batch it is issued in"
+    jc.check_stride_and_long_scan(d.encode, frames[:3], 0, 4, quality=95, subsampling="4:2:0")
+    emu = jc.AbiJpeg(_capi.Lib(jc.emu_library()))
+    try:
+        assert emu.encode(frames, 75, "4:4:4")["files"] == batch["files"], "the GPU's files are not the emulator's"
+    finally:
+        emu.close()

@@ -188,3 +188,43 @@ def test_camera_adapter(r):
     im2 = Image.open(io.BytesIO(cam2.get_depth_png())); im2.load()
     assert np.array_equal(np.asarray(im2), (np.clip(cam2.get_depth(), 0, 6.5) * 10000).astype(np.uint16))
     mesh.free(); scene.free()
+
+
+def test_coder_pictures_on_the_gpu(r):
+    """test_emu_png_coder.py's pictures (code lengths over 15 and 7 bits, few symbols, the run parse at every window edge, the stored /
+    dynamic decision and its neighbours): the property from the reference alone, checks 1-5 with the coder's own, and the emulator's
+    bytes.  The colour input is on the levels, so the reference's samples are the build's."""
+    from sage_gs import _capi
+    emu = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    d = GpuPng(r)
+    try:
+        for name, case in pc.coder_set().items():
+            want = pc.check_coder_case(name, case)          # before the library's output is looked at
+            frame, fmt = case["frame"], case["fmt"]
+            h, w = frame.shape[:2]
+            data = d.encode_one(frame, fmt)
+            samples = _packed(r, frame) if fmt == "rgb8" else png_ref.depth_samples(frame)
+            assert np.array_equal(samples, pc.samples_of(frame, fmt))
+            fig = pc.check_file(data, samples, d.bound(w, h, fmt), name)
+            want.pop("runs", None)
+            print(f"[png coder] {name}: reference {want}; file {fig['coding']}")
+            assert data == emu.encode_one(frame, fmt), f"{name}: the GPU's file is not the emulator's"
+    finally:
+        emu.close()
+
+
+def test_padded_stride_and_long_scan_on_the_gpu(r):
+    """test_emu_png_coder.py's test 15 through the GPU build, and its files against the emulator's (input on the levels)."""
+    from sage_gs import _capi
+    d = GpuPng(r)
+    frames = png_ref.rgb_samples(pc.long_scan_frames()).astype(np.float32) / np.float32(255.0)
+    batch = jpeg_cases.check_stride_and_long_scan(d.encode, frames, 256, 2, fmt="rgb8")
+    for i in (0, 1, 63, 64, 127, 128):
+        assert d.encode_one(frames[i], "rgb8") == batch["files"][i], f"frame {i} depends on the batch it is issued in"
+    depth = np.stack([pc.depth_levels(9, 5) * np.float32(1 + 0.01 * i) for i in range(257)])
+    dbatch = jpeg_cases.check_stride_and_long_scan(d.encode, depth, 256, 1, fmt="depth16")
+    emu = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    try:
+        assert emu.encode(frames, "rgb8")["files"] == batch["files"] and emu.encode(depth, "depth16")["files"] == dbatch["files"]
+    finally:
+        emu.close()
