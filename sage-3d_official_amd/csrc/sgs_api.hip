@@ -113,28 +113,32 @@ struct MeshScratch {
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
-// The JPEG encoder's scratch (sgs_encode_jpeg): per-interval lengths and offsets, the tables of the parameter sets seen so far (a
-// table is never rewritten: an encode still in flight on another stream keeps reading its own) and the pinned status words.
+// What every file encoder keeps for the placement of its files (csrc/sgs_encode.h): an offset per unit and the pinned status words.
+struct FileScratch {
+    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
+    int64_t offs_cap = 0;
+    long long* offs = nullptr;
+};
+
+// The JPEG encoder's scratch (sgs_encode_jpeg): per-interval lengths, the tables of the parameter sets seen so far (a table is never
+// rewritten: an encode still in flight on another stream keeps reading its own) and the files' placement.
 struct JpegScratch {
     struct Entry { int width, height, quality, s420; sgs::JpegTables* dev; };
     std::vector<Entry> tables;
-    int64_t cap = 0;                         // intervals the two arrays hold
+    int64_t sizes_cap = 0;
     unsigned* sizes = nullptr;
-    long long* offs = nullptr;
-    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
+    FileScratch files;
 };
 
-// The PNG encoder's scratch (sgs_encode_png): a stored-size slot, a record and an offset per strip, an Adler-32 per frame, the pinned
-// status words.
+// The PNG encoder's scratch (sgs_encode_png): a stored-size slot and a record per strip, an Adler-32 per frame, the files' placement.
 struct PngScratch {
-    int64_t cap = 0;                         // strips the record and offset arrays hold
+    int64_t rec_cap = 0;
     sgs::PngStripRec* rec = nullptr;
-    long long* offs = nullptr;
     int64_t slot_bytes = 0;
     unsigned char* slots = nullptr;
     int64_t frame_cap = 0;
     unsigned* adler = nullptr;
-    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
+    FileScratch files;
 };
 
 struct sgs_mesh {
@@ -210,6 +214,23 @@ int grow(sgs_ctx* ctx, T*& p, size_t count) {
     if (count == 0) count = 1;
     SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
     return SGS_OK;
+}
+
+// A scratch array of the file encoders, of at least `want` elements: grows geometrically; hipFree waits for the encodes that still use
+// the old array.  The capacity reads 0 while the array is being replaced, so a failed allocation leaves a state the next call recovers from.
+template <class T>
+int reserve(sgs_ctx* ctx, T*& p, int64_t& cap, int64_t want) {
+    if (want <= cap) return SGS_OK;
+    const int64_t c = std::max<int64_t>(want, 2 * cap);
+    cap = 0;
+    const int rc = grow(ctx, p, (size_t)c);
+    if (rc == SGS_OK) cap = c;
+    return rc;
+}
+
+void free_file_scratch(FileScratch& F) {
+    if (F.offs) (void)hipFree(F.offs);
+    if (F.h_status) (void)hipHostFree(F.h_status);
 }
 
 int ensure_splats(sgs_ctx* ctx, Lane& L, int64_t n) {
@@ -787,17 +808,11 @@ int sgs_destroy(sgs_ctx* ctx) {
         for (hipEvent_t e : M.ev) if (e) (void)hipEventDestroy(e);
     }
     {
-        JpegScratch& Z = ctx->jpeg;
-        for (JpegScratch::Entry& e : Z.tables) if (e.dev) (void)hipFree(e.dev);
-        if (Z.sizes) (void)hipFree(Z.sizes);
-        if (Z.offs) (void)hipFree(Z.offs);
-        if (Z.h_status) (void)hipHostFree(Z.h_status);
-    }
-    {
-        PngScratch& Z = ctx->png;
-        void* bufs[] = {Z.rec, Z.offs, Z.slots, Z.adler};
+        for (JpegScratch::Entry& e : ctx->jpeg.tables) if (e.dev) (void)hipFree(e.dev);
+        void* bufs[] = {ctx->jpeg.sizes, ctx->png.rec, ctx->png.slots, ctx->png.adler};
         for (void* b : bufs) if (b) (void)hipFree(b);
-        if (Z.h_status) (void)hipHostFree(Z.h_status);
+        free_file_scratch(ctx->jpeg.files);
+        free_file_scratch(ctx->png.files);
     }
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->row_acc) (void)hipFree(ctx->row_acc);
@@ -1710,22 +1725,75 @@ int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_ca
 
 }  // extern "C"
 
-// ---- JPEG encoder (csrc/sgs_jpeg.h) ------------------------------------------------------------------------------------------------
+// ---- the file encoders: what they share on the host (csrc/sgs_encode.h is the device side) ------------------------------------------
 namespace {
 
+// The checks every encoder makes of its arguments, after its own of the picture's parameters (bad_params: what is wrong with those, or
+// nullptr).  src_name: what the entry point calls its input; units: what a frame is cut into.
+int check_file_args(sgs_ctx* ctx, const char* who, const char* bad_params, int n_frames, const float* src, const char* src_name, int64_t frame_stride,
+                    int64_t frame_floats, const uint8_t* out, int64_t out_capacity, const int64_t* out_offsets, const int64_t* out_sizes,
+                    int units_per_frame, const char* units) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (bad_params) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s", who, bad_params);
+    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
+    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null %s", who, src_name);
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out", who);
+    if (!out_offsets) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_offsets", who);
+    if (!out_sizes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_sizes", who);
+    if (out_capacity < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_capacity %lld is negative", who, (long long)out_capacity);
+    if (n_frames > 1 && frame_stride < frame_floats)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (stride %lld floats, a frame has %lld)", who, (long long)frame_stride, (long long)frame_floats);
+    const int64_t n = (int64_t)n_frames * units_per_frame;
+    if (n > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %lld %s in one call (at most 2^31 - 1)", who, (long long)n, units);
+    return SGS_OK;
+}
+
+// Readies K for a call of n_units units: the pinned status words (made on first use) and the offsets array.  A call of no frames has
+// nothing to place: the status becomes this call's, not the previous one's, and K is left alone.
+int ready_file_sink(sgs_ctx* ctx, FileScratch& F, int64_t n_units, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
+                    sgs::FileSink& K) {
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    if (!F.h_status) {
+        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&F.h_status), 2 * sizeof(long long), 0));
+        F.h_status[0] = F.h_status[1] = 0;
+    }
+    if (n_units == 0) {
+        F.h_status[0] = 0; F.h_status[1] = out_capacity;
+        return SGS_OK;
+    }
+    const int rc = reserve(ctx, F.offs, F.offs_cap, n_units + 1);
+    if (rc != SGS_OK) return rc;
+    K = {F.offs, out, out_capacity, reinterpret_cast<long long*>(out_offsets), reinterpret_cast<long long*>(out_sizes), F.h_status};
+    return SGS_OK;
+}
+
+// sgs_jpeg_status / sgs_png_status: the status words of the encoder's most recent call (F: nullptr without a context).
+int file_status(sgs_ctx* ctx, const char* who, const FileScratch* F, int64_t* bytes_needed) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const long long need = F->h_status ? F->h_status[0] : 0, cap = F->h_status ? F->h_status[1] : 0;
+    if (bytes_needed) *bytes_needed = need;
+    if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "%s: the files take %lld bytes, out_capacity was %lld", who, need, cap);
+    return SGS_OK;
+}
+
+// ---- JPEG encoder (csrc/sgs_jpeg.h) ------------------------------------------------------------------------------------------------
 struct JpegGeom { int s420, mcus_x, mcus_y, n_mcu, ri, n_int; };
 
-bool jpeg_geom(int width, int height, const sgs_jpeg_params* p, JpegGeom& g) {
-    if (!p || p->quality < 1 || p->quality > 100 || (p->subsampling != SGS_JPEG_420 && p->subsampling != SGS_JPEG_444) ||
-        width < 1 || height < 1 || width > 65535 || height > 65535)
-        return false;
+// nullptr when the arguments describe a picture the encoder takes, else what is wrong with them.
+const char* jpeg_geom(int width, int height, const sgs_jpeg_params* p, JpegGeom& g, char* why, size_t n_why) {
+    if (!p) { snprintf(why, n_why, "params is NULL"); return why; }
+    if (p->quality < 1 || p->quality > 100) { snprintf(why, n_why, "quality %d is outside 1..100", p->quality); return why; }
+    if (p->subsampling != SGS_JPEG_420 && p->subsampling != SGS_JPEG_444) {
+        snprintf(why, n_why, "subsampling %d is neither SGS_JPEG_420 nor SGS_JPEG_444", p->subsampling); return why;
+    }
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) { snprintf(why, n_why, "%d x %d is outside 1..65535", width, height); return why; }
     g.s420 = p->subsampling == SGS_JPEG_420;
     const int mcu = g.s420 ? 16 : 8;
     g.mcus_x = (width + mcu - 1) / mcu; g.mcus_y = (height + mcu - 1) / mcu;
     g.n_mcu = g.mcus_x * g.mcus_y;
     g.ri = SGS_JPEG_BLOCKS / (g.s420 ? 6 : 3);
     g.n_int = (g.n_mcu + g.ri - 1) / g.ri;
-    return true;
+    return nullptr;
 }
 
 }  // namespace
@@ -1739,42 +1807,24 @@ void sgs_jpeg_params_default(sgs_jpeg_params* p) {
 
 int64_t sgs_jpeg_bound(int width, int height, const sgs_jpeg_params* params) {
     JpegGeom g;
-    if (!jpeg_geom(width, height, params, g)) return SGS_ERR_INVALID;
+    char why[256];
+    if (jpeg_geom(width, height, params, g, why, sizeof why)) return SGS_ERR_INVALID;
     return SGS_JPEG_HEADER + (int64_t)g.n_int * (2 * SGS_JPEG_INT_BYTES + 2);
 }
 
 int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
                     const sgs_jpeg_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
                     void* hip_stream) {
-    if (!ctx) return SGS_ERR_INVALID;
-    if (!params) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: params is NULL");
-    if (params->quality < 1 || params->quality > 100) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: quality %d is outside 1..100", params->quality);
-    if (params->subsampling != SGS_JPEG_420 && params->subsampling != SGS_JPEG_444)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: subsampling %d is neither SGS_JPEG_420 nor SGS_JPEG_444", params->subsampling);
-    if (width < 1 || height < 1 || width > 65535 || height > 65535)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: %d x %d is outside 1..65535", width, height);
-    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: n_frames = %d", n_frames);
-    if (!rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null rgb");
-    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out");
-    if (!out_offsets) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out_offsets");
-    if (!out_sizes) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: null out_sizes");
-    if (out_capacity < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: out_capacity %lld is negative", (long long)out_capacity);
-    if (n_frames > 1 && rgb_frame_stride < (int64_t)width * height * 3)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: frames overlap (stride %lld floats)", (long long)rgb_frame_stride);
-    JpegGeom g;
-    jpeg_geom(width, height, params, g);
+    JpegGeom g = {};
+    char why[256];
+    const char* bad = jpeg_geom(width, height, params, g, why, sizeof why);
+    int rc = check_file_args(ctx, "sgs_encode_jpeg", bad, n_frames, rgb, "rgb", rgb_frame_stride, (int64_t)width * height * 3, out, out_capacity,
+                             out_offsets, out_sizes, g.n_int, "restart intervals");
+    if (rc != SGS_OK) return rc;
     const int64_t n = (int64_t)n_frames * g.n_int;
-    if (n > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_jpeg: %lld restart intervals in one call (at most 2^31 - 1)", (long long)n);
-    SGS_HIP(ctx, hipSetDevice(ctx->device));
     JpegScratch& Z = ctx->jpeg;
-    if (!Z.h_status) {
-        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&Z.h_status), 2 * sizeof(long long), 0));
-        Z.h_status[0] = Z.h_status[1] = 0;
-    }
-    if (n_frames == 0) {                                   // nothing to encode: the status is this call's, not the previous one's
-        Z.h_status[0] = 0; Z.h_status[1] = out_capacity;
-        return SGS_OK;
-    }
+    sgs::JpegJob J;
+    if ((rc = ready_file_sink(ctx, Z.files, n, out, out_capacity, out_offsets, out_sizes, J.sink)) != SGS_OK || n == 0) return rc;
     sgs::JpegTables* tab = nullptr;
     for (const JpegScratch::Entry& e : Z.tables)
         if (e.width == width && e.height == height && e.quality == params->quality && e.s420 == g.s420) tab = e.dev;
@@ -1792,21 +1842,10 @@ int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n
         // subsampling) a context has encoded, until sgs_destroy — a handful in any real caller
         Z.tables.push_back({width, height, params->quality, g.s420, tab});
     }
-    if (n + 1 > Z.cap) {                                   // grows geometrically; hipFree waits for the encodes that still use the old arrays
-        const int64_t c = std::max<int64_t>(n + 1, 2 * Z.cap);
-        if (Z.sizes) { (void)hipFree(Z.sizes); Z.sizes = nullptr; }
-        if (Z.offs) { (void)hipFree(Z.offs); Z.offs = nullptr; }
-        Z.cap = 0;
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.sizes), (size_t)c * sizeof(unsigned)));
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.offs), (size_t)c * sizeof(long long)));
-        Z.cap = c;
-    }
-    sgs::JpegJob J;
+    if ((rc = reserve(ctx, Z.sizes, Z.sizes_cap, n)) != SGS_OK) return rc;
     J.rgb = rgb; J.frame_stride = rgb_frame_stride; J.width = width; J.height = height; J.s420 = g.s420;
     J.mcus_x = g.mcus_x; J.n_mcu = g.n_mcu; J.ri = g.ri; J.n_int = g.n_int; J.n_frames = n_frames;
-    J.tab = tab; J.sizes = Z.sizes; J.offs = Z.offs; J.out = out; J.cap = out_capacity;
-    J.out_offsets = reinterpret_cast<long long*>(out_offsets); J.out_sizes = reinterpret_cast<long long*>(out_sizes);
-    J.status = Z.h_status;
+    J.tab = tab; J.sizes = Z.sizes;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipLaunchKernelGGL(sgs::k_jpeg_intervals<false>, dim3((unsigned)n), dim3(64), 0, st, J);
     hipLaunchKernelGGL(sgs::k_jpeg_scan, dim3(1), dim3(SGS_JPEG_SCAN_THREADS), 0, st, J);
@@ -1816,12 +1855,7 @@ int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n
 }
 
 int sgs_jpeg_status(sgs_ctx* ctx, int64_t* bytes_needed) {
-    if (!ctx) return SGS_ERR_INVALID;
-    const JpegScratch& Z = ctx->jpeg;
-    const long long need = Z.h_status ? Z.h_status[0] : 0, cap = Z.h_status ? Z.h_status[1] : 0;
-    if (bytes_needed) *bytes_needed = need;
-    if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "sgs_encode_jpeg: the files take %lld bytes, out_capacity was %lld", need, cap);
-    return SGS_OK;
+    return file_status(ctx, "sgs_encode_jpeg", ctx ? &ctx->jpeg.files : nullptr, bytes_needed);
 }
 
 }  // extern "C"
@@ -1877,65 +1911,25 @@ int64_t sgs_png_bound(int width, int height, const sgs_png_params* params) {
 int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
                    const sgs_png_params* params, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
                    void* hip_stream) {
-    if (!ctx) return SGS_ERR_INVALID;
-    PngGeom g;
+    PngGeom g = {};
     char why[256];
-    if (png_geom(width, height, params, g, why, sizeof why)) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: %s", why);
-    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: n_frames = %d", n_frames);
-    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null src");
-    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out");
-    if (!out_offsets) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out_offsets");
-    if (!out_sizes) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: null out_sizes");
-    if (out_capacity < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: out_capacity %lld is negative", (long long)out_capacity);
-    const int64_t frame_floats = (int64_t)width * height * (g.depth16 ? 1 : 3);
-    if (n_frames > 1 && src_frame_stride < frame_floats)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: frames overlap (stride %lld floats, a frame has %lld)", (long long)src_frame_stride,
-                 (long long)frame_floats);
+    const char* bad = png_geom(width, height, params, g, why, sizeof why);
+    int rc = check_file_args(ctx, "sgs_encode_png", bad, n_frames, src, "src", src_frame_stride, (int64_t)width * height * (g.depth16 ? 1 : 3), out,
+                             out_capacity, out_offsets, out_sizes, g.n_strips, "strips");
+    if (rc != SGS_OK) return rc;
     const int64_t n = (int64_t)n_frames * g.n_strips;
-    if (n > 0x7fffffffll) SGS_FAIL(ctx, SGS_ERR_INVALID, "sgs_encode_png: %lld strips in one call (at most 2^31 - 1)", (long long)n);
-    SGS_HIP(ctx, hipSetDevice(ctx->device));
     PngScratch& Z = ctx->png;
-    if (!Z.h_status) {
-        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&Z.h_status), 2 * sizeof(long long), 0));
-        Z.h_status[0] = Z.h_status[1] = 0;
-    }
-    if (n_frames == 0) {                                   // nothing to encode: the status is this call's, not the previous one's
-        Z.h_status[0] = 0; Z.h_status[1] = out_capacity;
-        return SGS_OK;
-    }
-    // scratch grows geometrically; hipFree waits for the encodes that still use the old arrays
-    if (n + 1 > Z.cap) {
-        const int64_t c = std::max<int64_t>(n + 1, 2 * Z.cap);
-        if (Z.rec) { (void)hipFree(Z.rec); Z.rec = nullptr; }
-        if (Z.offs) { (void)hipFree(Z.offs); Z.offs = nullptr; }
-        Z.cap = 0;
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.rec), (size_t)c * sizeof(sgs::PngStripRec)));
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.offs), (size_t)c * sizeof(long long)));
-        Z.cap = c;
-    }
-    const int64_t slot = (((int64_t)std::min(g.rows_per_strip, height) * (g.row_bytes + 1) + 16) + 15) & ~(int64_t)15;
-    if (n * slot > Z.slot_bytes) {
-        const int64_t c = std::max<int64_t>(n * slot, 2 * Z.slot_bytes);
-        if (Z.slots) { (void)hipFree(Z.slots); Z.slots = nullptr; }
-        Z.slot_bytes = 0;
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.slots), (size_t)c));
-        Z.slot_bytes = c;
-    }
-    if (n_frames > Z.frame_cap) {
-        const int64_t c = std::max<int64_t>(n_frames, 2 * Z.frame_cap);
-        if (Z.adler) { (void)hipFree(Z.adler); Z.adler = nullptr; }
-        Z.frame_cap = 0;
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&Z.adler), (size_t)c * sizeof(unsigned)));
-        Z.frame_cap = c;
-    }
     sgs::PngJob J;
     memset(&J, 0, sizeof J);
+    if ((rc = ready_file_sink(ctx, Z.files, n, out, out_capacity, out_offsets, out_sizes, J.sink)) != SGS_OK || n == 0) return rc;
+    const int64_t slot = (((int64_t)std::min(g.rows_per_strip, height) * (g.row_bytes + 1) + 16) + 15) & ~(int64_t)15;
+    if ((rc = reserve(ctx, Z.rec, Z.rec_cap, n)) != SGS_OK) return rc;
+    if ((rc = reserve(ctx, Z.slots, Z.slot_bytes, n * slot)) != SGS_OK) return rc;
+    if ((rc = reserve(ctx, Z.adler, Z.frame_cap, n_frames)) != SGS_OK) return rc;
     J.src = src; J.frame_stride = src_frame_stride; J.width = width; J.height = height; J.depth16 = g.depth16;
     J.scale = params->depth_scale; J.dmax = params->depth_max; J.bpp = g.bpp; J.row_bytes = g.row_bytes;
     J.rows_per_strip = g.rows_per_strip; J.n_strips = g.n_strips; J.n_frames = n_frames;
-    J.slot = slot; J.slots = Z.slots; J.rec = Z.rec; J.offs = Z.offs; J.adler = Z.adler; J.out = out; J.cap = out_capacity;
-    J.out_offsets = reinterpret_cast<long long*>(out_offsets); J.out_sizes = reinterpret_cast<long long*>(out_sizes);
-    J.status = Z.h_status;
+    J.slot = slot; J.slots = Z.slots; J.rec = Z.rec; J.adler = Z.adler;
     sgs::png::build_head(J.head, width, height, g.depth16 != 0);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipLaunchKernelGGL(sgs::k_png_strips, dim3((unsigned)n), dim3(64), 0, st, J);
@@ -1946,12 +1940,7 @@ int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_
 }
 
 int sgs_png_status(sgs_ctx* ctx, int64_t* bytes_needed) {
-    if (!ctx) return SGS_ERR_INVALID;
-    const PngScratch& Z = ctx->png;
-    const long long need = Z.h_status ? Z.h_status[0] : 0, cap = Z.h_status ? Z.h_status[1] : 0;
-    if (bytes_needed) *bytes_needed = need;
-    if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "sgs_encode_png: the files take %lld bytes, out_capacity was %lld", need, cap);
-    return SGS_OK;
+    return file_status(ctx, "sgs_encode_png", ctx ? &ctx->png.files : nullptr, bytes_needed);
 }
 
 }  // extern "C"

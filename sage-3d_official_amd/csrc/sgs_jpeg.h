@@ -6,8 +6,8 @@
 // A call of n frames is three stream-ordered launches with no host synchronisation in between:
 //   k_jpeg_intervals<false>  one wave per restart interval: levels, YCbCr, subsampling, DCT, quantiser, Huffman coding into an LDS bit
 //                            buffer, 0xFF count — writes only the interval's stuffed byte length
-//   k_jpeg_scan              one workgroup: exclusive scan of (length + 2 marker bytes [+ header]) over every interval of every frame ->
-//                            the absolute offset of every interval in `out`, the total, the status words
+//   k_jpeg_scan              one workgroup: place_files (sgs_encode.h) over (length + 2 marker bytes [+ header]) of every interval of
+//                            every frame -> the absolute offset of every interval in `out`, the total, the status words
 //   k_jpeg_intervals<true>   the same wave codes the same interval again and writes header / stuffed bytes / RSTn or EOI where the scan
 //                            put them; a frame whose end lies beyond the capacity is not written at all
 // Coding an interval twice saves the worst-case slot per interval a one-pass coder would need (19 898 bytes for 48 blocks, 7.6 MB a
@@ -31,6 +31,7 @@
 #include <cmath>
 
 #include "sgs_common.h"
+#include "sgs_encode.h"
 
 #define SGS_JPEG_BLOCKS 48                 // 8x8 blocks per restart interval
 #define SGS_JPEG_BLOCK_BITS 1658           // most bits a block can take: DC 9 + 11, 63 x (AC code 16 + amplitude 10)
@@ -62,12 +63,7 @@ struct JpegJob {
     int n_frames;
     const JpegTables* tab;
     unsigned* sizes;                       // [n_frames * n_int] stuffed bytes of each interval
-    long long* offs;                       // [n_frames * n_int + 1] where each interval's data starts in out (interval 0: its header)
-    unsigned char* out;
-    long long cap;
-    long long* out_offsets;
-    long long* out_sizes;
-    long long* status;                     // [0] bytes all files take, [1] the capacity they were given
+    FileSink sink;                         // offs: [n_frames * n_int + 1] where each interval's data starts in out (interval 0: its header)
 };
 
 // An 8-bit level as k_pack_rgba8 makes it.
@@ -91,15 +87,13 @@ __global__ __launch_bounds__(64) void k_jpeg_intervals(JpegJob J) {
     const int frame = (int)(gidx / J.n_int), it = (int)(gidx % J.n_int);
     unsigned char* dst = nullptr;
     if (WRITE) {
-        const long long f0 = J.offs[(long long)frame * J.n_int], f1 = J.offs[(long long)(frame + 1) * J.n_int];
-        if (it == 0 && lane == 0) { J.out_offsets[frame] = f0; J.out_sizes[frame] = f1 - f0; }
-        if (f1 > J.cap) return;                            // the frame does not fit: none of it is written
-        long long at = J.offs[gidx];
+        long long at;
+        if (!file_unit_offset(J.sink, gidx, J.n_int, lane == 0, at)) return;
         if (it == 0) {
-            for (int i = lane; i < SGS_JPEG_HEADER; i += 64) J.out[at + i] = J.tab->header[i];
+            for (int i = lane; i < SGS_JPEG_HEADER; i += 64) J.sink.out[at + i] = J.tab->header[i];
             at += SGS_JPEG_HEADER;
         }
-        dst = J.out + at;
+        dst = J.sink.out + at;
     }
     s_q[0][lane] = J.tab->q[0][lane]; s_q[1][lane] = J.tab->q[1][lane];
     s_scale[lane] = J.tab->scale[lane]; s_cos[lane] = J.tab->cosm[lane]; s_nat[lane] = J.tab->nat[lane];
@@ -241,29 +235,12 @@ __global__ __launch_bounds__(64) void k_jpeg_intervals(JpegJob J) {
     }
 }
 
-// Exclusive scan over every interval of every frame of (stuffed bytes + 2 marker bytes + the header at a frame's first interval).
+// place_files over every interval of every frame of (stuffed bytes + 2 marker bytes + the header at a frame's first interval).
 __global__ __launch_bounds__(SGS_JPEG_SCAN_THREADS) void k_jpeg_scan(JpegJob J) {
     __shared__ unsigned long long s_part[SGS_JPEG_SCAN_THREADS];
-    const long long n = (long long)J.n_frames * J.n_int;
-    const long long per = (n + SGS_JPEG_SCAN_THREADS - 1) / SGS_JPEG_SCAN_THREADS;
-    const long long t0 = per * (long long)threadIdx.x, i0 = t0 < n ? t0 : n, i1 = i0 + per < n ? i0 + per : n;
-    unsigned long long sum = 0;
-    for (long long i = i0; i < i1; ++i) sum += (unsigned long long)J.sizes[i] + 2ull + (i % J.n_int == 0 ? (unsigned long long)SGS_JPEG_HEADER : 0ull);
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < SGS_JPEG_SCAN_THREADS; ++t) { const unsigned long long v = s_part[t]; s_part[t] = run; run += v; }
-        J.offs[n] = (long long)run;
-        J.status[0] = (long long)run;
-        J.status[1] = J.cap;
-    }
-    __syncthreads();
-    unsigned long long at = s_part[threadIdx.x];
-    for (long long i = i0; i < i1; ++i) {
-        J.offs[i] = (long long)at;
-        at += (unsigned long long)J.sizes[i] + 2ull + (i % J.n_int == 0 ? (unsigned long long)SGS_JPEG_HEADER : 0ull);
-    }
+    place_files<SGS_JPEG_SCAN_THREADS>(J.sink, (long long)J.n_frames * J.n_int, s_part, [&J](long long i) {
+        return (unsigned long long)J.sizes[i] + 2ull + (i % J.n_int == 0 ? (unsigned long long)SGS_JPEG_HEADER : 0ull);
+    });
 }
 
 // ---- host side: the tables of T.81 Annex K and the file header ---------------------------------------------------------------------

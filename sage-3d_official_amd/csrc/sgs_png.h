@@ -9,8 +9,8 @@
 //   k_png_strips   one 64-lane workgroup per strip: samples, filter choice per row, Adler-32 partial sums, run matching, histogram,
 //                  length-limited Huffman tables, the deflate bits into an LDS buffer, CRC-32 — the finished chunk body ("IDAT" + data)
 //                  goes to the strip's slot of the library's scratch (stored-size slots: a strip is never longer than stored)
-//   k_png_scan     one workgroup: exclusive scan of the chunk sizes over every strip of every frame -> the absolute offset of every
-//                  chunk in `out`, the total, the status words; the Adler-32 of each frame from its strips' (a, b) pairs
+//   k_png_scan     one workgroup: place_files (sgs_encode.h) over the chunk sizes of every strip of every frame -> the absolute offset
+//                  of every chunk in `out`, the total, the status words; the Adler-32 of each frame from its strips' (a, b) pairs
 //   k_png_gather   one workgroup per strip copies the slot to where the scan put it and writes the framing: signature + IHDR before a
 //                  frame's first chunk, length and CRC around each, final block + Adler-32 + IEND after its last
 // Coding once into slots rather than twice around the scan (sgs_jpeg.h's shape): a strip's work is several sweeps over 16 KiB plus a
@@ -28,6 +28,7 @@
 #include <cmath>
 
 #include "sgs_common.h"
+#include "sgs_encode.h"
 
 #define SGS_PNG_STRIP 16384                // filtered bytes per strip (and the longest filtered row)
 #define SGS_PNG_OUT_WORDS 4112             // "IDAT" 4 + zlib header 2 + stored header 5 + strip + alignment block 5 = 16 400 B, + 2 spill words, rounded up
@@ -57,13 +58,8 @@ struct PngJob {
     long long slot;                        // bytes between strip slots
     unsigned char* slots;
     PngStripRec* rec;                      // [n_frames * n_strips]
-    long long* offs;                       // [n_frames * n_strips + 1] where each strip's chunk starts in out (strip 0: the signature)
     unsigned* adler;                       // [n_frames]
-    unsigned char* out;
-    long long cap;
-    long long* out_offsets;
-    long long* out_sizes;
-    long long* status;                     // [0] bytes all files take, [1] the capacity they were given
+    FileSink sink;                         // offs: [n_frames * n_strips + 1] where each strip's chunk starts in out (strip 0: the signature)
     unsigned char head[SGS_PNG_HEAD + 3];
 };
 
@@ -545,29 +541,10 @@ __device__ __forceinline__ unsigned long long png_chunk_bytes(const PngJob& J, l
     return (unsigned long long)J.rec[i].len + 8ull + (st == 0 ? (unsigned long long)SGS_PNG_HEAD : 0ull) + (st == J.n_strips - 1 ? 9ull + 12ull : 0ull);
 }
 
-// Exclusive scan of the chunk sizes over every strip of every frame; the Adler-32 of each frame's filtered stream from its strips' sums.
+// place_files over the chunk sizes of every strip of every frame; the Adler-32 of each frame's filtered stream from its strips' sums.
 __global__ __launch_bounds__(SGS_PNG_SCAN_THREADS) void k_png_scan(PngJob J) {
     __shared__ unsigned long long s_part[SGS_PNG_SCAN_THREADS];
-    const long long n = (long long)J.n_frames * J.n_strips;
-    const long long per = (n + SGS_PNG_SCAN_THREADS - 1) / SGS_PNG_SCAN_THREADS;
-    const long long t0 = per * (long long)threadIdx.x, i0 = t0 < n ? t0 : n, i1 = i0 + per < n ? i0 + per : n;
-    unsigned long long sum = 0;
-    for (long long i = i0; i < i1; ++i) sum += png_chunk_bytes(J, i);
-    s_part[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int t = 0; t < SGS_PNG_SCAN_THREADS; ++t) { const unsigned long long v = s_part[t]; s_part[t] = run; run += v; }
-        J.offs[n] = (long long)run;
-        J.status[0] = (long long)run;
-        J.status[1] = J.cap;
-    }
-    __syncthreads();
-    unsigned long long at = s_part[threadIdx.x];
-    for (long long i = i0; i < i1; ++i) {
-        J.offs[i] = (long long)at;
-        at += png_chunk_bytes(J, i);
-    }
+    place_files<SGS_PNG_SCAN_THREADS>(J.sink, (long long)J.n_frames * J.n_strips, s_part, [&J](long long i) { return png_chunk_bytes(J, i); });
     // Adler-32 over N bytes f: a = 1 + sum f[i], b = N + sum (N - i) f[i]; a strip ending at byte `end` adds b_s + (N - end) a_s to b
     const long long rowlen = (long long)J.row_bytes + 1, N = rowlen * J.height;
     for (int f = (int)threadIdx.x; f < J.n_frames; f += SGS_PNG_SCAN_THREADS) {
@@ -593,10 +570,9 @@ __global__ __launch_bounds__(SGS_PNG_GATHER_THREADS) void k_png_gather(PngJob J)
     const int t = (int)threadIdx.x;
     const long long gidx = (long long)blockIdx.x;
     const int frame = (int)(gidx / J.n_strips), st = (int)(gidx % J.n_strips);
-    const long long f0 = J.offs[(long long)frame * J.n_strips], f1 = J.offs[(long long)(frame + 1) * J.n_strips];
-    if (st == 0 && t == 0) { J.out_offsets[frame] = f0; J.out_sizes[frame] = f1 - f0; }
-    if (f1 > J.cap) return;
-    unsigned char* dst = J.out + J.offs[gidx];
+    long long at;
+    if (!file_unit_offset(J.sink, gidx, J.n_strips, t == 0, at)) return;
+    unsigned char* dst = J.sink.out + at;
     if (st == 0) {
         if (t < SGS_PNG_HEAD) dst[t] = J.head[t];
         dst += SGS_PNG_HEAD;

@@ -578,6 +578,22 @@ class Renderer:
                                                   C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
                                                   self._stream()), self._ctx)
 
+    def _encode_files(self, n: int, cap: int, issue) -> list:
+        """The files (bytes, one per frame) of one synchronous encode of n >= 1 frames.  issue(out, meta) enqueues the C call on the
+        current stream: files into `out` (uint8 [cap], device), offsets and sizes into the pinned int64 [2, n] `meta`.  Files that do
+        not fit `cap` are encoded once more, with the capacity their sizes ask for."""
+        meta = torch.zeros((2, n), dtype=torch.int64, pin_memory=True)
+        while True:
+            out = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+            issue(out, meta)
+            torch.cuda.current_stream(self.device).synchronize()
+            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
+            if total <= cap:
+                break
+            cap = total                                                       # did not fit: the sizes say what does (SGS_ERR_OVERFLOW's figure)
+        host = out[:total].cpu().numpy()
+        return [host[int(o):int(o) + int(z)].tobytes() for o, z in zip(meta[0].tolist(), meta[1].tolist())]
+
     def encode_jpeg(self, rgb: torch.Tensor, quality: int = 95, subsampling: str = "4:2:0") -> list:
         """Baseline JPEG files (bytes, one per frame) of float32 [H,W,3] or [B,H,W,3] frames on the device, encoded there: what
         Image.fromarray(get_rgba()[:, :, :3]).save(f, quality=quality) writes for the same picture, same tables, same default
@@ -589,17 +605,7 @@ class Renderer:
             return []
         params = _capi.jpeg_params(quality, subsampling)
         cap = n * max(1 << 16, int(rgb.shape[1]) * int(rgb.shape[2]))         # a byte a pixel: several times a photographic frame at q95
-        meta = torch.zeros((2, n), dtype=torch.int64, pin_memory=True)
-        while True:
-            out = torch.empty((cap,), dtype=torch.uint8, device=self.device)
-            self._encode_jpeg_into(rgb, n, params, out, meta)
-            torch.cuda.current_stream(self.device).synchronize()
-            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
-            if total <= cap:
-                break
-            cap = total                                                       # did not fit: the sizes say what does
-        host = out[:total].cpu().numpy()
-        return [host[int(o):int(o) + int(z)].tobytes() for o, z in zip(meta[0].tolist(), meta[1].tolist())]
+        return self._encode_files(n, cap, lambda out, meta: self._encode_jpeg_into(rgb, n, params, out, meta))
 
     def jpeg_frames(self, shape, quality: int = 95, subsampling: str = "4:2:0", depth: int = 3) -> "JpegFrames":
         """A ring of `depth` pinned byte buffers (+ device twins, a copy stream, events) for chunks of up to shape[0] frames of
@@ -630,19 +636,12 @@ class Renderer:
             return []
         frame_floats = h * w * (3 if tail else 1)
         cap = n * max(1 << 12, frame_floats // 2)                             # half a byte a sample to begin with; the sizes say what fits
-        meta = torch.zeros((2, n), dtype=torch.int64, pin_memory=True)
-        while True:
-            out = torch.empty((cap,), dtype=torch.uint8, device=self.device)
+
+        def issue(out, meta):
             self._lib.check(self._lib.sgs_encode_png(self._ctx, frames.data_ptr(), w, h, n, int(frames.stride(0)) if n > 1 else frame_floats,
-                                                     C.byref(params), out.data_ptr(), cap, meta[0].data_ptr(), meta[1].data_ptr(),
+                                                     C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
                                                      self._stream()), self._ctx)
-            torch.cuda.current_stream(self.device).synchronize()
-            total = int(meta[0, n - 1]) + int(meta[1, n - 1])
-            if total <= cap:
-                break
-            cap = total                                                       # did not fit: SGS_ERR_OVERFLOW's figure
-        host = out[:total].cpu().numpy()
-        return [host[int(o):int(o) + int(z)].tobytes() for o, z in zip(meta[0].tolist(), meta[1].tolist())]
+        return self._encode_files(n, cap, issue)
 
     # -- test hooks -------------------------------------------------------------------------------
     def debug_buffer(self, what, dtype):

@@ -1,5 +1,6 @@
 """The JPEG encoder's checks, shared by the CPU-emulator tests (test_emu_jpeg.py) and the GPU tests (test_gpu_jpeg.py): the image
-set, a driver of the C ABI over plain buffers, and the assertions on a file (coefficients, structure, interoperability, fidelity)."""
+set, the driver of the C ABI over plain buffers (AbiEncoder: the PNG encoder's is built on it too), and the assertions on a file
+(coefficients, structure, interoperability, fidelity)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -72,8 +73,11 @@ def image_set():
     }
 
 
-class AbiJpeg:
-    """sgs_encode_jpeg over host buffers (the emulator's 'device' is the host).  A GPU driver overrides the three buffer hooks."""
+class AbiEncoder:
+    """One of the file encoders of the C ABI (sgs_encode_jpeg, sgs_encode_png) over host buffers (the emulator's 'device' is the
+    host).  A subclass names its two entry points and supplies _params and bound, which take the encoder's own arguments — the ones
+    encode and encode_one pass through.  A GPU driver overrides the four buffer hooks (GpuBuffers)."""
+    ENCODE = STATUS = None
 
     def __init__(self, lib, ctx=None):
         from sage_gs import _capi
@@ -88,7 +92,7 @@ class AbiJpeg:
             self.lib.sgs_destroy(self.ctx)
             self.ctx = None
 
-    # buffer hooks: (object that keeps the memory alive, address)
+    # buffer hooks: (object that keeps the memory alive, address[, getter of a host copy])
     def _frames(self, frames):
         a = np.ascontiguousarray(frames, np.float32)
         return a, a.ctypes.data
@@ -104,37 +108,73 @@ class AbiJpeg:
     def _sync(self):
         pass
 
-    def bound(self, w, h, quality, subsampling):
-        p = self._capi.jpeg_params(quality, subsampling)
-        return int(self.lib.sgs_jpeg_bound(int(w), int(h), C.byref(p)))
-
-    def encode(self, frames, quality, subsampling, capacity=None, slack=64, stride=None):
-        """frames fp32 [n,H,W,3].  Returns dict(files, offsets, sizes, buffer (capacity + slack bytes, SENTINEL-filled before the
-        call), capacity, rc (sgs_jpeg_status after synchronising), needed).  stride: floats from one frame to the next (default: a
-        frame); the floats between frames are NaN and 1e30 in turn."""
+    def encode(self, frames, *args, capacity=None, slack=64, stride=None, **kw):
+        """frames fp32 [n,H,W,...]; args, kw: the encoder's own (_params).  Returns dict(files, offsets, sizes, buffer (capacity + slack
+        bytes, SENTINEL-filled before the call), capacity, rc (the encoder's status after synchronising), needed).  stride: floats from
+        one frame to the next (default: a frame); the floats between frames are NaN and 1e30 in turn."""
         frames = np.asarray(frames, np.float32)
-        n, h, w, _ = frames.shape
+        n, h, w = frames.shape[:3]
+        frame_floats = int(np.prod(frames.shape[1:]))
         if stride is not None:
             frames = strided(frames, stride)
-        p = self._capi.jpeg_params(quality, subsampling)
-        cap = n * self.bound(w, h, quality, subsampling) if capacity is None else int(capacity)
+        p = self._params(*args, **kw)
+        cap = n * self.bound(w, h, *args, **kw) if capacity is None else int(capacity)
         keep_f, f_ptr = self._frames(frames)
         keep_o, o_ptr, o_get = self._bytes(cap + slack)
         keep_a, a_ptr, a_get = self._i64(n)
         keep_s, s_ptr, s_get = self._i64(n)
-        self.lib.check(self.lib.sgs_encode_jpeg(self.ctx, f_ptr, w, h, n, h * w * 3 if stride is None else int(stride), C.byref(p), o_ptr, cap, a_ptr, s_ptr, None), self.ctx)
+        self.lib.check(getattr(self.lib, self.ENCODE)(self.ctx, f_ptr, w, h, n, frame_floats if stride is None else int(stride), C.byref(p), o_ptr, cap,
+                                                      a_ptr, s_ptr, None), self.ctx)
         self._sync()
         need = C.c_int64(-1)
-        rc = int(self.lib.sgs_jpeg_status(self.ctx, C.byref(need)))
+        rc = int(getattr(self.lib, self.STATUS)(self.ctx, C.byref(need)))
         buf, offs, sizes = o_get(), a_get(), s_get()
         files = [bytes(buf[int(o):int(o) + int(z)]) for o, z in zip(offs, sizes)] if rc == 0 else None
         return {"files": files, "offsets": offs, "sizes": sizes, "buffer": buf, "capacity": cap, "rc": rc, "needed": int(need.value)}
 
-    def encode_one(self, frame, quality, subsampling):
-        r = self.encode(np.asarray(frame, np.float32)[None], quality, subsampling)
+    def encode_one(self, frame, *args, **kw):
+        r = self.encode(np.asarray(frame, np.float32)[None], *args, **kw)
         assert r["rc"] == 0, r["rc"]
         check_nothing_written_beyond(r)
         return r["files"][0]
+
+
+class AbiJpeg(AbiEncoder):
+    """sgs_encode_jpeg: frames fp32 [n,H,W,3]; encode(frames, quality, subsampling, ...)."""
+    ENCODE, STATUS = "sgs_encode_jpeg", "sgs_jpeg_status"
+
+    def _params(self, quality, subsampling):
+        return self._capi.jpeg_params(quality, subsampling)
+
+    def bound(self, w, h, quality, subsampling):
+        return int(self.lib.sgs_jpeg_bound(int(w), int(h), C.byref(self._params(quality, subsampling))))
+
+
+class GpuBuffers:
+    """The buffer hooks over torch device buffers, on a Renderer's context: class GpuX(GpuBuffers, AbiX)."""
+
+    def __init__(self, renderer):
+        super().__init__(renderer._lib, renderer._ctx)
+        self.r = renderer
+
+    def _frames(self, frames):
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(frames, np.float32)).to(self.r.device)
+        return t, t.data_ptr()
+
+    def _bytes(self, n):
+        import torch
+        t = torch.full((n,), SENTINEL, dtype=torch.uint8, device=self.r.device)
+        return t, t.data_ptr(), lambda: t.cpu().numpy()
+
+    def _i64(self, n):
+        import torch
+        t = torch.full((n,), -1, dtype=torch.int64, device=self.r.device)
+        return t, t.data_ptr(), lambda: t.cpu().numpy()
+
+    def _sync(self):
+        import torch
+        torch.cuda.synchronize(self.r.device)
 
 
 def strided(frames, stride):
@@ -276,13 +316,3 @@ def check_exact_ties(encode_one):
             y = parsed["coefficients"][0]
             assert (y[:, :, 0, 0] == want).all(), f"exact tie: grey {v} at q{q} {sub}: luminance DC {int(y[0, 0, 0, 0])}, halves away from zero give {want}"
             assert (y.reshape(-1, 64)[:, 1:] == 0).all() and all((c == 0).all() for c in parsed["coefficients"][1:]), "a flat grey frame has one non-zero coefficient per block"
-
-
-def emu_library():
-    """The emulator library of csrc/, rebuilt when sgs_jpeg.h is newer than it (emu_harness's own staleness check does not know that
-    header)."""
-    import os
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_jpeg.h")
-    lib = emu_harness.EMU_LIB
-    return emu_harness.build_emu(force=os.path.exists(lib) and os.path.getmtime(hdr) > os.path.getmtime(lib))

@@ -12,7 +12,7 @@ import numpy as np
 import jpeg_cases
 import png_ref
 
-SENTINEL = 0xA5
+SENTINEL = jpeg_cases.SENTINEL
 # Test 5: our file against zlib restricted to the same design (the same filtered bytes, every strip deflated alone at level 1 with run
 # matches only, the same framing).  The worst ratio over the whole picture set, measured on the emulator build (whose bytes are the
 # GPU's), was 1.0519 (depth_1x1: 81 bytes against 77, and colour_1x1: 82 against 78 — a strip of 3 or 4 bytes, which we store and zlib
@@ -90,71 +90,15 @@ def samples_of(frame, fmt, depth_scale=10000.0, depth_max=6.5):
     return png_ref.rgb_samples(frame) if fmt == "rgb8" else png_ref.depth_samples(frame, depth_scale, depth_max)
 
 
-class AbiPng:
-    """sgs_encode_png over host buffers (the emulator's 'device' is the host).  A GPU driver overrides the four buffer hooks."""
+class AbiPng(jpeg_cases.AbiEncoder):
+    """sgs_encode_png: frames fp32 [n,H,W,3] (rgb8) or [n,H,W] (depth16); encode(frames, fmt, depth_scale=, depth_max=, ...)."""
+    ENCODE, STATUS = "sgs_encode_png", "sgs_png_status"
 
-    def __init__(self, lib, ctx=None):
-        from sage_gs import _capi
-        self._capi, self.lib = _capi, lib
-        self.ctx, self._own = ctx, ctx is None
-        if ctx is None:
-            self.ctx = C.c_void_p()
-            lib.check(lib.sgs_create(0, _capi.BACKEND_HIP, C.byref(self.ctx)))
-
-    def close(self):
-        if self._own and self.ctx:
-            self.lib.sgs_destroy(self.ctx)
-            self.ctx = None
-
-    # buffer hooks: (object that keeps the memory alive, address[, getter of a host copy])
-    def _frames(self, frames):
-        a = np.ascontiguousarray(frames, np.float32)
-        return a, a.ctypes.data
-
-    def _bytes(self, n):
-        a = np.full(n, SENTINEL, np.uint8)
-        return a, a.ctypes.data, lambda: a
-
-    def _i64(self, n):
-        a = np.full(n, -1, np.int64)
-        return a, a.ctypes.data, lambda: a
-
-    def _sync(self):
-        pass
+    def _params(self, fmt="rgb8", depth_scale=10000.0, depth_max=6.5):
+        return self._capi.png_params(fmt, depth_scale, depth_max)
 
     def bound(self, w, h, fmt="rgb8", depth_scale=10000.0, depth_max=6.5):
-        p = self._capi.png_params(fmt, depth_scale, depth_max)
-        return int(self.lib.sgs_png_bound(int(w), int(h), C.byref(p)))
-
-    def encode(self, frames, fmt="rgb8", capacity=None, slack=64, depth_scale=10000.0, depth_max=6.5, stride=None):
-        """frames fp32 [n,H,W,3] (rgb8) or [n,H,W] (depth16).  Returns dict(files, offsets, sizes, buffer (capacity + slack bytes,
-        SENTINEL-filled before the call), capacity, rc (sgs_png_status after synchronising), needed).  stride: floats from one frame
-        to the next (default: a frame); the floats between frames are NaN and 1e30 in turn."""
-        frames = np.asarray(frames, np.float32)
-        n, h, w = frames.shape[:3]
-        frame_floats = int(np.prod(frames.shape[1:]))
-        if stride is not None:
-            frames = jpeg_cases.strided(frames, stride)
-        p = self._capi.png_params(fmt, depth_scale, depth_max)
-        cap = n * self.bound(w, h, fmt, depth_scale, depth_max) if capacity is None else int(capacity)
-        keep_f, f_ptr = self._frames(frames)
-        keep_o, o_ptr, o_get = self._bytes(cap + slack)
-        keep_a, a_ptr, a_get = self._i64(n)
-        keep_s, s_ptr, s_get = self._i64(n)
-        self.lib.check(self.lib.sgs_encode_png(self.ctx, f_ptr, w, h, n, frame_floats if stride is None else int(stride), C.byref(p), o_ptr, cap, a_ptr, s_ptr, None),
-                       self.ctx)
-        self._sync()
-        need = C.c_int64(-1)
-        rc = int(self.lib.sgs_png_status(self.ctx, C.byref(need)))
-        buf, offs, sizes = o_get(), a_get(), s_get()
-        files = [bytes(buf[int(o):int(o) + int(z)]) for o, z in zip(offs, sizes)] if rc == 0 else None
-        return {"files": files, "offsets": offs, "sizes": sizes, "buffer": buf, "capacity": cap, "rc": rc, "needed": int(need.value)}
-
-    def encode_one(self, frame, fmt="rgb8", **kw):
-        r = self.encode(np.asarray(frame, np.float32)[None], fmt, **kw)
-        assert r["rc"] == 0, r["rc"]
-        jpeg_cases.check_nothing_written_beyond(r)
-        return r["files"][0]
+        return int(self.lib.sgs_png_bound(int(w), int(h), C.byref(self._params(fmt, depth_scale, depth_max))))
 
 
 def pil_size(samples, **kw):
@@ -233,16 +177,6 @@ def check_smaller_than_raw(fig, label, noise=False):
     """Check 4's last item: every picture but noise is smaller than its raw bytes (from SMALLER_THAN_RAW_FROM raw bytes on)."""
     if not noise and fig["raw"] >= SMALLER_THAN_RAW_FROM:
         assert fig["bytes"] < fig["raw"], f"{label}: {fig['bytes']} bytes, raw {fig['raw']}"
-
-
-def emu_library():
-    """The emulator library of csrc/, rebuilt when sgs_png.h is newer than it (emu_harness's own staleness check does not know that
-    header)."""
-    import os
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_png.h")
-    lib = emu_harness.EMU_LIB
-    return emu_harness.build_emu(force=os.path.exists(lib) and os.path.getmtime(hdr) > os.path.getmtime(lib))
 
 
 # ---- the deflate coder: what every strip's block must be (check_strip_coding), and pictures built to reach its branches ----------------

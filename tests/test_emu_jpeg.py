@@ -21,8 +21,7 @@ JPEG_H = os.path.join(emu_harness.PKG, "csrc", "sgs_jpeg.h")
 
 @pytest.fixture(scope="module")
 def drv():
-    # emu_harness's staleness check does not know sgs_jpeg.h: rebuild when the header is newer than the emulator library
-    d = jc.AbiJpeg(_capi.Lib(jc.emu_library()))
+    d = jc.AbiJpeg(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 

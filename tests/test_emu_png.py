@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import emu_harness
 import jpeg_cases
 import png_cases as pc
 import png_ref
@@ -16,7 +17,7 @@ from sage_gs import _capi
 
 @pytest.fixture(scope="module")
 def drv():
-    d = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    d = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 

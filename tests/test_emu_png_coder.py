@@ -22,7 +22,7 @@ from sage_gs import _capi
 
 @pytest.fixture(scope="module")
 def drv():
-    d = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    d = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 

@@ -8,37 +8,15 @@ import os
 import numpy as np
 import pytest
 
+import emu_harness
 import jpeg_cases as jc
 import jpeg_ref
 
 pytestmark = pytest.mark.gpu
 
 
-class GpuJpeg(jc.AbiJpeg):
+class GpuJpeg(jc.GpuBuffers, jc.AbiJpeg):
     """jpeg_cases.AbiJpeg over torch device buffers, on a Renderer's context."""
-
-    def __init__(self, renderer):
-        super().__init__(renderer._lib, renderer._ctx)
-        self.r = renderer
-
-    def _frames(self, frames):
-        import torch
-        t = torch.from_numpy(np.ascontiguousarray(frames, np.float32)).to(self.r.device)
-        return t, t.data_ptr()
-
-    def _bytes(self, n):
-        import torch
-        t = torch.full((n,), jc.SENTINEL, dtype=torch.uint8, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _i64(self, n):
-        import torch
-        t = torch.full((n,), -1, dtype=torch.int64, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _sync(self):
-        import torch
-        torch.cuda.synchronize(self.r.device)
 
 
 @pytest.fixture(scope="module")
@@ -143,7 +121,7 @@ def test_gpu_bytes_equal_the_emulators(r):
     # input on the levels themselves (k / 255): how x * 255 + 0.5 is rounded on a level boundary is k_pack_rgba8's own property in each
     # build (one fused rounding under hipcc, two on the host), not the encoder's — everything after the levels is held to equality
     img = (jc.levels_of(jc.gradient_noise(192, 256, 5) * 1.1 - 0.05).astype(np.float32) / np.float32(255.0))
-    emu = jc.AbiJpeg(_capi.Lib(jc.emu_library()))
+    emu = jc.AbiJpeg(_capi.Lib(emu_harness.build_emu()))
     d = GpuJpeg(r)
     try:
         for q, sub in ((95, "4:2:0"), (100, "4:4:4"), (50, "4:2:0")):
@@ -256,7 +234,7 @@ def test_padded_stride_and_long_scan_on_the_gpu(r):
     for i in (0, 9, 10, 19):
         assert d.encode_one(frames[i], 75, "4:4:4") == batch["files"][i], f"frame {i} depends on the batch it is issued in"
     jc.check_stride_and_long_scan(d.encode, frames[:3], 0, 4, quality=95, subsampling="4:2:0")
-    emu = jc.AbiJpeg(_capi.Lib(jc.emu_library()))
+    emu = jc.AbiJpeg(_capi.Lib(emu_harness.build_emu()))
     try:
         assert emu.encode(frames, 75, "4:4:4")["files"] == batch["files"], "the GPU's files are not the emulator's"
     finally:

@@ -6,6 +6,7 @@ import io
 import numpy as np
 import pytest
 
+import emu_harness
 import jpeg_cases
 import png_cases as pc
 import png_ref
@@ -13,31 +14,8 @@ import png_ref
 pytestmark = pytest.mark.gpu
 
 
-class GpuPng(pc.AbiPng):
+class GpuPng(jpeg_cases.GpuBuffers, pc.AbiPng):
     """png_cases.AbiPng over torch device buffers, on a Renderer's context."""
-
-    def __init__(self, renderer):
-        super().__init__(renderer._lib, renderer._ctx)
-        self.r = renderer
-
-    def _frames(self, frames):
-        import torch
-        t = torch.from_numpy(np.ascontiguousarray(frames, np.float32)).to(self.r.device)
-        return t, t.data_ptr()
-
-    def _bytes(self, n):
-        import torch
-        t = torch.full((n,), pc.SENTINEL, dtype=torch.uint8, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _i64(self, n):
-        import torch
-        t = torch.full((n,), -1, dtype=torch.int64, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _sync(self):
-        import torch
-        torch.cuda.synchronize(self.r.device)
 
 
 @pytest.fixture(scope="module")
@@ -107,7 +85,7 @@ def test_gpu_bytes_equal_the_emulators(r):
     colour from input on the levels, k / 255 (the level is k_pack_rgba8's x * 255 + 0.5, which hipcc fuses and the host compiler does
     not).  From the samples on the encoder is integer-only, so the files must be equal byte for byte."""
     from sage_gs import _capi
-    emu = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    emu = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
     d = GpuPng(r)
     try:
         for name, img in pc.depth_set().items():
@@ -195,7 +173,7 @@ def test_coder_pictures_on_the_gpu(r):
     dynamic decision and its neighbours): the property from the reference alone, checks 1-5 with the coder's own, and the emulator's
     bytes.  The colour input is on the levels, so the reference's samples are the build's."""
     from sage_gs import _capi
-    emu = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    emu = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
     d = GpuPng(r)
     try:
         for name, case in pc.coder_set().items():
@@ -223,7 +201,7 @@ def test_padded_stride_and_long_scan_on_the_gpu(r):
         assert d.encode_one(frames[i], "rgb8") == batch["files"][i], f"frame {i} depends on the batch it is issued in"
     depth = np.stack([pc.depth_levels(9, 5) * np.float32(1 + 0.01 * i) for i in range(257)])
     dbatch = jpeg_cases.check_stride_and_long_scan(d.encode, depth, 256, 1, fmt="depth16")
-    emu = pc.AbiPng(_capi.Lib(pc.emu_library()))
+    emu = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
     try:
         assert emu.encode(frames, "rgb8")["files"] == batch["files"] and emu.encode(depth, "depth16")["files"] == dbatch["files"]
     finally:

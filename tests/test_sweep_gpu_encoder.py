@@ -15,7 +15,7 @@ from sage_gs import _capi, sweep
 
 @pytest.fixture(scope="module")
 def drv():
-    d = jc.AbiJpeg(_capi.Lib(jc.emu_library()))
+    d = jc.AbiJpeg(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 
