@@ -346,6 +346,35 @@ int sgs_render_mesh_depth(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* 
 int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams,
                                 const sgs_config* cfg, float* out_depth, sgs_stats* stats, void* hip_stream);
 
+/* ---- Collision-mesh object ids — which object each pixel shows: the label of the triangle whose hit sgs_render_mesh_depth* reports.
+ * The reference never reads such a channel (its ObjectNav / object-based success decide on the 2-D map only): this is THIS PROJECT'S
+ * definition, checked against the fp64 ray caster that checks the depth (tests/mesh_id_ref.py).  No new struct, no new version.
+ *
+ *   Labels   one int32 per triangle, 0 <= label <= INT32_MAX - 1 (sgs_mesh_set_labels; typically the index of the `def Mesh` prim the
+ *            triangle came from).  A mesh without labels uses the triangle's index.
+ *   Frames   exactly as sgs_render_mesh_depth*: the same rays, near / far rule, both faces, refusals, record buffer and its growth, stats,
+ *            synchronous only; a band of tile rows leaves the other rows of BOTH outputs untouched.  The same five launches per group of
+ *            up to 8 frames, the last one k_mesh_ids in place of k_mesh_depth; 4 more bytes are gathered per record, 4 more written per pixel.
+ *   Value    out_id[y * W + x] (a DEVICE buffer of H*W int32) = the label of the hit the depth frame reports: among the hits with
+ *            near_z < z <= far_z the one with the least fp32 z, and among hits whose z is bit-equal the LEAST LABEL; SGS_ID_NONE where
+ *            nothing is hit.  Both kernels decide a hit with the same source (mesh_hit, csrc/sgs_mesh.h).
+ *   Depth    out_depth (nullable) is bit-identical to what sgs_render_mesh_depth* writes for the same call.
+ *   Exact    a pixel's value is the minimum of the pair (z, label), in that order, over the triangles listed for its tile, so it does not
+ *            depend on the order of the records: a frame's ids are bit-identical alone or in a batch, as a band or as the full frame, and
+ *            under any permutation of the triangles that carries the labels along.  With the default labels (the triangle's index) the last
+ *            guarantee does not hold: a permutation renames the triangles. */
+#define SGS_ID_NONE (-1)
+/* labels int32[n_triangles of the mesh] (a host pointer, or a device pointer when on_device != 0): copied.  NULL restores the default
+ * (label = triangle index).  A label outside [0, INT32_MAX - 1] is refused with SGS_ERR_INVALID — checked on the device through the status
+ * word, as the upload checks indices — and the mesh's previous labels stay in force.  Synchronises the device. */
+int sgs_mesh_set_labels(sgs_ctx* ctx, sgs_mesh* mesh, const int32_t* labels, int on_device);
+/* One frame: the tile rows [tile_row_begin, tile_row_end) (end < 0: all) of out_id (H*W int32) and, when given, of out_depth (H*W floats). */
+int sgs_render_mesh_ids(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cam, const sgs_config* cfg, int tile_row_begin,
+                        int tile_row_end, float* out_depth, int32_t* out_id, sgs_stats* stats, void* hip_stream);
+/* n_cams whole frames, out_id[B][H][W] and (nullable) out_depth[B][H][W]. */
+int sgs_render_mesh_ids_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams, const sgs_config* cfg,
+                              float* out_depth, int32_t* out_id, sgs_stats* stats, void* hip_stream);
+
 /* ---- Baseline JPEG encoding of rendered frames — replaces Image.fromarray(rgb).save(path) of the data-generation loop
  * (generate_images.py:431-432) and the JPEG encoding of every observation the VLM client sends (vlm_client_modular.py:346-351): the file
  * is made on the device from the fp32 frame sgs_render* left there, and only its bytes cross the link.  No new version: no existing

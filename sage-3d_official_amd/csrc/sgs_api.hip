@@ -145,6 +145,7 @@ struct sgs_mesh {
     int64_t n_verts = 0, n_tris = 0;
     float* verts = nullptr;
     int* tris = nullptr;
+    int* labels = nullptr;                   // sgs_mesh_set_labels: [n_tris], or nullptr: a triangle's label is its index
 };
 
 struct sgs_ctx {
@@ -1546,7 +1547,42 @@ int sgs_mesh_free(sgs_ctx* ctx, sgs_mesh* mesh) {
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipDeviceSynchronize(); }
     if (mesh->verts) (void)hipFree(mesh->verts);
     if (mesh->tris) (void)hipFree(mesh->tris);
+    if (mesh->labels) (void)hipFree(mesh->labels);
     delete mesh;
+    return SGS_OK;
+}
+
+int sgs_mesh_set_labels(sgs_ctx* ctx, sgs_mesh* mesh, const int32_t* labels, int on_device) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (!mesh) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh is NULL");
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    SGS_HIP(ctx, hipDeviceSynchronize());                    // no frame still reads the labels that are replaced
+    int* fresh = nullptr;
+    if (labels && mesh->n_tris > 0) {
+        const size_t lb = (size_t)mesh->n_tris * sizeof(int);
+        hipError_t e = hipSuccess;
+        if ((e = hipMalloc(reinterpret_cast<void**>(&fresh), lb)) != hipSuccess ||
+            (e = hipMemcpy(fresh, labels, lb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess) {
+            if (fresh) (void)hipFree(fresh);
+            SGS_FAIL(ctx, e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "mesh labels: %s", hipGetErrorString(e));
+        }
+        // checked on the device (the caller's array may live there), through the upload's status word
+        if (!ctx->mesh.d_st) { (void)hipFree(fresh); SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: the mesh was not uploaded through this context"); }
+        unsigned* bad = &ctx->mesh.d_st[SGS_MESH_MAX_GROUP].n_visible;
+        unsigned flags = 0;
+        if ((e = hipMemset(bad, 0, sizeof(unsigned))) == hipSuccess) {
+            hipLaunchKernelGGL(sgs::k_mesh_validate_labels, dim3((unsigned)std::min<long long>((mesh->n_tris + 255) / 256, 4096)), dim3(256), 0,
+                               nullptr, (long long)mesh->n_tris, (const int*)fresh, bad);
+            if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost);
+        }
+        if (e != hipSuccess || flags) {
+            (void)hipFree(fresh);
+            if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "mesh labels: %s", hipGetErrorString(e));
+            SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: labels outside [0, INT32_MAX - 1] (the mesh keeps its previous labels)");
+        }
+    }
+    if (mesh->labels) (void)hipFree(mesh->labels);
+    mesh->labels = fresh;
     return SGS_OK;
 }
 
@@ -1579,10 +1615,11 @@ int mesh_grow(sgs_ctx* ctx, T*& p, int64_t& cap, int64_t want, int64_t count_per
 }
 
 // Frames [0, n) of cams: groups of up to SGS_MESH_MAX_GROUP frames, each five launches and one synchronisation; frame i is written at
-// out + i * frame_stride.  stats: n entries (nullable).
+// out + i * frame_stride.  stats: n entries (nullable).  out_id != nullptr: the id frames (sgs_render_mesh_ids*: k_mesh_ids as the last
+// launch, out nullable); otherwise the depth frames.
 int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n, const sgs_config* cfg_in, int row_begin, int row_end,
-                float* out, int64_t frame_stride, sgs_stats* stats, void* hip_stream) {
-    if (!mesh || !cams || !out) SGS_FAIL(ctx, SGS_ERR_INVALID, "null mesh / camera / output");
+                float* out, int32_t* out_id, bool ids, int64_t frame_stride, sgs_stats* stats, void* hip_stream) {
+    if (!mesh || !cams || (ids ? !out_id : !out)) SGS_FAIL(ctx, SGS_ERR_INVALID, "null mesh / camera / output");
     if (n < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "n_cams = %d", n);
     sgs_config cfg;
     if (cfg_in) cfg = *cfg_in; else sgs_config_default(&cfg);
@@ -1655,10 +1692,11 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
                 for (int k = 0; k < 12; ++k) P.view[k] = c.view[k];
                 P.fx = c.fx; P.fy = c.fy; P.cx = c.cx; P.cy = c.cy; P.near_z = cfg.near_z; P.far_z = cfg.far_z;
                 P.width = W; P.height = H; P.gx = gx; P.row_begin = row_begin; P.row_end = row_end;
-                P.out = out + (int64_t)(g0 + f) * frame_stride;
+                P.out = out ? out + (int64_t)(g0 + f) * frame_stride : nullptr;
+                P.out_id = ids ? out_id + (int64_t)(g0 + f) * frame_stride : nullptr;
             }
             G.nf = nf; G.n_tiles = n_tiles; G.n_tris = F; G.cap = M.list_cap;
-            G.verts = mesh->verts; G.tris = mesh->tris;
+            G.verts = mesh->verts; G.tris = mesh->tris; G.labels = mesh->labels;
             G.rec = M.rec; G.rect = M.rect; G.big = M.big; G.counts = M.counts; G.offs = M.offs; G.list = M.list; G.st = M.d_st;
             if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[0], stream));
             SGS_HIP(ctx, hipMemsetAsync(M.d_st, 0, sizeof(sgs::MeshStatus) * nf, stream));
@@ -1673,7 +1711,8 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
                 } else {
                     hipLaunchKernelGGL(sgs::k_mesh_scan, dim3(1, (unsigned)nf), dim3(SGS_MESH_SCAN_THREADS), 0, stream, G);
                 }
-                hipLaunchKernelGGL(sgs::k_mesh_depth, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
+                if (ids) hipLaunchKernelGGL(sgs::k_mesh_ids, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
+                else hipLaunchKernelGGL(sgs::k_mesh_depth, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
             }
             if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[1], stream));
             SGS_HIP(ctx, hipGetLastError());
@@ -1713,14 +1752,27 @@ extern "C" {
 int sgs_render_mesh_depth(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cam, const sgs_config* cfg, int tile_row_begin,
                           int tile_row_end, float* out_depth, sgs_stats* stats, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    return mesh_frames(ctx, mesh, cam, 1, cfg, tile_row_begin, tile_row_end, out_depth, 0, stats, hip_stream);
+    return mesh_frames(ctx, mesh, cam, 1, cfg, tile_row_begin, tile_row_end, out_depth, nullptr, false, 0, stats, hip_stream);
 }
 
 int sgs_render_mesh_depth_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams, const sgs_config* cfg,
                                 float* out_depth, sgs_stats* stats, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
     if (!cams || n_cams < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "no cameras");
-    return mesh_frames(ctx, mesh, cams, n_cams, cfg, 0, -1, out_depth, (int64_t)cams[0].width * cams[0].height, stats, hip_stream);
+    return mesh_frames(ctx, mesh, cams, n_cams, cfg, 0, -1, out_depth, nullptr, false, (int64_t)cams[0].width * cams[0].height, stats, hip_stream);
+}
+
+int sgs_render_mesh_ids(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cam, const sgs_config* cfg, int tile_row_begin,
+                        int tile_row_end, float* out_depth, int32_t* out_id, sgs_stats* stats, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    return mesh_frames(ctx, mesh, cam, 1, cfg, tile_row_begin, tile_row_end, out_depth, out_id, true, 0, stats, hip_stream);
+}
+
+int sgs_render_mesh_ids_batch(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int n_cams, const sgs_config* cfg,
+                              float* out_depth, int32_t* out_id, sgs_stats* stats, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    if (!cams || n_cams < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "no cameras");
+    return mesh_frames(ctx, mesh, cams, n_cams, cfg, 0, -1, out_depth, out_id, true, (int64_t)cams[0].width * cams[0].height, stats, hip_stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// sgs_mesh.h — gfx950 kernels of the collision-mesh depth path (sgs_render_mesh_depth*, include/sage_gs.h).
+// sgs_mesh.h — gfx950 kernels of the collision-mesh depth and object-id path (sgs_render_mesh_depth*, sgs_render_mesh_ids*,
+// include/sage_gs.h).
 //
 // A group of up to SGS_MESH_MAX_GROUP frames of one resolution is five stream-ordered launches with no host synchronisation in between:
 //   k_mesh_setup      one thread per (triangle, frame): fp64 transform, cull, 16-float record, tile rect of the part with z >= near_z
@@ -6,6 +7,7 @@
 //   k_mesh_scan       one workgroup per frame: exclusive scan of the counts -> tile offsets, D, the longest list
 //   k_mesh_bin<1>     the same walk again, scattering triangle ids into the per-tile lists (the record buffer)
 //   k_mesh_depth      one 256-lane workgroup per 16x16-pixel tile: the list's records staged through LDS, a running min per pixel
+//   (k_mesh_ids       in its place for sgs_render_mesh_ids*: the same walk, a running min of (z, label) per pixel)
 // The result of a pixel is a MINIMUM over the triangles its tile lists, so it depends neither on the order of a list nor on which other
 // tiles / frames share the launches: batch, band and single frame agree bit for bit, as do permutations of the triangles.
 //
@@ -38,7 +40,8 @@ struct MeshFrame {
     int32_t width, height;
     int32_t gx;                     // tiles per row
     int32_t row_begin, row_end;     // the band of tile rows [row_begin, row_end) of the frame
-    float* out;                     // the frame's H*W depth buffer
+    float* out;                     // the frame's H*W depth buffer (k_mesh_ids: nullable)
+    int32_t* out_id;                // k_mesh_ids: the frame's H*W label buffer
 };
 
 struct MeshStatus {
@@ -56,6 +59,7 @@ struct MeshGroup {
     long long cap;                  // entries the record buffer holds
     const float* verts;             // [V][3]
     const int* tris;                // [F][3]
+    const int* labels;              // k_mesh_ids: [F] labels >= 0, or NULL: a triangle's label is its index
     float4* rec;                    // [nf][F][4]: (e0, 0) (e1, 0) (e2, 0) (n, n.p0), edges already multiplied by sign(det)
     uint2* rect;                    // [nf][F]: tile rect, x0 | x1 << 16, y0 | y1 << 16 (x0 > x1: empty)
     unsigned* big;                  // [nf][F]: triangles whose rect exceeds SGS_MESH_SMALL tiles
@@ -74,6 +78,15 @@ __global__ __launch_bounds__(256) void k_mesh_validate(long long n_verts, const 
         if ((__float_as_uint(verts[i]) & 0x7f800000u) == 0x7f800000u) flags |= 1u;     // inf / NaN
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < 3 * n_tris; i += stride)
         if (tris[i] < 0 || (long long)tris[i] >= n_verts) flags |= 2u;
+    if (flags) atomicOr(bad, flags);
+}
+
+// sgs_mesh_set_labels' check: every label in [0, INT32_MAX - 1] (bit 2 of *bad).
+__global__ __launch_bounds__(256) void k_mesh_validate_labels(long long n_tris, const int* __restrict__ labels, unsigned* __restrict__ bad) {
+    unsigned flags = 0;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_tris; i += stride)
+        if (labels[i] < 0 || labels[i] == 0x7fffffff) flags |= 4u;
     if (flags) atomicOr(bad, flags);
 }
 
@@ -296,10 +309,41 @@ __device__ __forceinline__ bool mesh_inside64(const MeshGroup& G, const MeshFram
     return true;
 }
 
-// One workgroup per tile of the band, one pixel per lane.
-__global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
+// The per-record test both last-stage kernels share, so that they can never disagree about a hit: record k of the staged batch against
+// the lane's ray — the fp32 edge functions, the fp64 re-decision of an edge within rounding of 0, z and the near / far rule.  Returns the
+// hit's z, or +inf when the ray misses the triangle or z is outside (near_z, far_z].
+__device__ __forceinline__ float mesh_hit(const MeshGroup& G, const MeshFrame& F, const float4 (*s_rec)[256], const unsigned* s_id, int k, float rx,
+                                          float ry, float rmax, float near_z, float far_z) {
+    float best = __uint_as_float(0x7f800000u);
+    const float4 e0 = s_rec[0][k], e1 = s_rec[1][k], e2 = s_rec[2][k];
+    const float s0 = fmaf(e0.x, rx, fmaf(e0.y, ry, e0.z));
+    const float s1 = fmaf(e1.x, rx, fmaf(e1.y, ry, e1.z));
+    const float s2 = fmaf(e2.x, rx, fmaf(e2.y, ry, e2.z));
+    bool in = s0 >= 0.f && s1 >= 0.f && s2 >= 0.f;
+    if (!in && fmaf(e0.w, rmax, fminf(s0, fminf(s1, s2))) >= 0.f) {         // within rounding of an edge: fp64 (header)
+        const float4 e[3] = {e0, e1, e2};
+        const float sv[3] = {s0, s1, s2};
+        in = mesh_inside64(G, F, s_id[k], e, sv, rx, ry);
+    }
+    if (in) {
+        const float4 pl = s_rec[3][k];
+        const float z = pl.w / fmaf(pl.x, rx, fmaf(pl.y, ry, pl.z));
+        if (z > near_z && z <= far_z) best = z;
+    }
+    return best;
+}
+
+// The last stage of a tile: one 256-lane workgroup, one pixel per lane, the tile's list staged through LDS 256 records at a time.
+// IDS = false (k_mesh_depth): a running minimum of z per lane.  IDS = true (k_mesh_ids): each record's label is staged beside its id and
+// the lane keeps the minimum of the PAIR (z, label) in that order — the least fp32 z, the least label among hits whose z is bit-equal —
+// so the id belongs to the depth the same walk reports, and neither depends on the order of the list.  Two plain compares and a select
+// per record, not a packed 64-bit key (the bits of a float order as its value only while it is positive): noise beside the three edge
+// functions, in a kernel bound by its longest list walked serially.
+template <bool IDS>
+__device__ __forceinline__ void mesh_tile_walk(const MeshGroup& G) {
     __shared__ float4 s_rec[4][256];
     __shared__ unsigned s_id[256];
+    __shared__ int s_label[IDS ? 256 : 1];
     const int f = blockIdx.y;
     const MeshFrame& F = G.f[f];
     unsigned long long total = 0, base = 0;
@@ -315,35 +359,37 @@ __global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) {
     const float near_z = F.near_z, far_z = F.far_z;
     const float4* rec = G.rec + 4 * (size_t)f * (size_t)G.n_tris;
     float best = __uint_as_float(0x7f800000u);
+    int best_label = SGS_ID_NONE;                            // (a label is >= 0: a miss, z = +inf, never replaces it)
     for (unsigned long long b = begin; b < end; b += 256) {
         const int n = end - b < 256ull ? (int)(end - b) : 256;
         if ((int)threadIdx.x < n) {
             const unsigned id = G.list[b + threadIdx.x];
             const float4* R = rec + 4 * (size_t)id;
             s_id[threadIdx.x] = id;
+            if (IDS) s_label[threadIdx.x] = G.labels ? G.labels[id] : (int)id;
             s_rec[0][threadIdx.x] = R[0]; s_rec[1][threadIdx.x] = R[1]; s_rec[2][threadIdx.x] = R[2]; s_rec[3][threadIdx.x] = R[3];
         }
         __syncthreads();
         for (int k = 0; k < n; ++k) {
-            const float4 e0 = s_rec[0][k], e1 = s_rec[1][k], e2 = s_rec[2][k];
-            const float s0 = fmaf(e0.x, rx, fmaf(e0.y, ry, e0.z));
-            const float s1 = fmaf(e1.x, rx, fmaf(e1.y, ry, e1.z));
-            const float s2 = fmaf(e2.x, rx, fmaf(e2.y, ry, e2.z));
-            bool in = s0 >= 0.f && s1 >= 0.f && s2 >= 0.f;
-            if (!in && fmaf(e0.w, rmax, fminf(s0, fminf(s1, s2))) >= 0.f) {         // within rounding of an edge: fp64 (header)
-                const float4 e[3] = {e0, e1, e2};
-                const float sv[3] = {s0, s1, s2};
-                in = mesh_inside64(G, F, s_id[k], e, sv, rx, ry);
-            }
-            if (in) {
-                const float4 pl = s_rec[3][k];
-                const float z = pl.w / fmaf(pl.x, rx, fmaf(pl.y, ry, pl.z));
-                if (z > near_z && z <= far_z) best = fminf(best, z);
+            const float z = mesh_hit(G, F, s_rec, s_id, k, rx, ry, rmax, near_z, far_z);
+            if (IDS) {
+                const int label = s_label[k];
+                if (z < best || (z == best && label < best_label)) { best = z; best_label = label; }
+            } else {
+                best = fminf(best, z);
             }
         }
         __syncthreads();
     }
-    if (px < F.width && py < F.height) F.out[(size_t)py * F.width + px] = best;
+    if (px < F.width && py < F.height) {
+        if (!IDS || F.out) F.out[(size_t)py * F.width + px] = best;
+        if (IDS) F.out_id[(size_t)py * F.width + px] = best_label;
+    }
 }
+
+__global__ __launch_bounds__(256) void k_mesh_depth(const MeshGroup G) { mesh_tile_walk<false>(G); }
+
+// sgs_render_mesh_ids*: per pixel the label of the hit the depth frame reports (SGS_ID_NONE where nothing is hit), and that depth.
+__global__ __launch_bounds__(256) void k_mesh_ids(const MeshGroup G) { mesh_tile_walk<true>(G); }
 
 }  // namespace sgs

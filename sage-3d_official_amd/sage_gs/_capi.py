@@ -18,6 +18,7 @@ FLAG_ASYNC, FLAG_TIMING, FLAG_STATS, FLAG_FULL_SORT, FLAG_PIPELINED, FLAG_LOOSE_
 FLAG_NO_DEEP = 256
 FLAG_NO_FINE_TILES = 512
 BACKEND_CPU, BACKEND_HIP = 0, 1
+ID_NONE = -1             # include/sage_gs.h SGS_ID_NONE: sgs_render_mesh_ids* where nothing is hit
 BUF_TILE_OFFSETS, BUF_SORTED_SLOTS, BUF_SLOT_IDS, BUF_SPLATS, BUF_CHUNK_SKIPPED, BUF_SCENE_GEOM, BUF_SCENE_SH = 0, 1, 2, 3, 4, 5, 6
 
 ERR_NAMES = {-1: "SGS_ERR_INVALID", -2: "SGS_ERR_HIP", -3: "SGS_ERR_OOM", -4: "SGS_ERR_OVERFLOW",
@@ -32,6 +33,7 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_render_rgbd", "sgs_render_batch", "sgs_render_batch_strided", "sgs_frame_sync", "sgs_row_records", "sgs_pack_rgba8", "sgs_debug_read",
            "sgs_tuning_default", "sgs_set_tuning", "sgs_get_tuning",
            "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch",
+           "sgs_mesh_set_labels", "sgs_render_mesh_ids", "sgs_render_mesh_ids_batch",
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status")
 
@@ -173,6 +175,9 @@ class Lib:
         lib.sgs_mesh_set_record_capacity.argtypes = [vp, i64]
         lib.sgs_render_mesh_depth.argtypes = [vp, vp, C.POINTER(SgsCamera), C.POINTER(SgsConfig), i32, i32, vp, C.POINTER(SgsStats), vp]
         lib.sgs_render_mesh_depth_batch.argtypes = [vp, vp, vp, i32, C.POINTER(SgsConfig), vp, vp, vp]
+        lib.sgs_mesh_set_labels.argtypes = [vp, vp, vp, i32]
+        lib.sgs_render_mesh_ids.argtypes = [vp, vp, C.POINTER(SgsCamera), C.POINTER(SgsConfig), i32, i32, vp, vp, C.POINTER(SgsStats), vp]
+        lib.sgs_render_mesh_ids_batch.argtypes = [vp, vp, vp, i32, C.POINTER(SgsConfig), vp, vp, vp, vp]
         lib.sgs_jpeg_params_default.argtypes = [C.POINTER(SgsJpegParams)]; lib.sgs_jpeg_params_default.restype = None
         lib.sgs_jpeg_bound.argtypes = [i32, i32, C.POINTER(SgsJpegParams)]; lib.sgs_jpeg_bound.restype = i64
         lib.sgs_encode_jpeg.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsJpegParams), vp, i64, vp, vp, vp]

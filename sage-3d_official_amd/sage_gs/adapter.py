@@ -25,13 +25,17 @@ MESH_CONFIG = RenderConfig(near=0.01)
 class GsCamera:
     def __init__(self, renderer: Renderer, scene, prim_path: str = "/World/Camera", frequency: int = 30,
                  resolution: Tuple[int, int] = (640, 480), config: Optional[RenderConfig] = None, collision_mesh=None,
-                 mesh_config: Optional[RenderConfig] = None):
+                 mesh_config: Optional[RenderConfig] = None, instance_paths: Optional[Sequence[str]] = None):
         """collision_mesh: a Mesh (Renderer.upload_mesh) — get_depth() / get_current_frame()["distance_to_image_plane"] then come
         from it, as the reference's come from /World/scene_collision (simple_env.py:1395-1589); mesh_config: its near / far (default
-        MESH_CONFIG).  Without a mesh, depth is the Gaussians' expected depth, as before."""
+        MESH_CONFIG).  Without a mesh, depth is the Gaussians' expected depth, as before.
+        instance_paths: the prim path of every label of the mesh (mesh.read_usda_mesh(return_prims=True)'s prim_paths, the mesh uploaded
+        with labels=tri_prim) — the names of the instance-id channel (get_instance_ids, add_instance_id_segmentation_to_frame)."""
         self._r, self._scene, self.prim_path, self.frequency = renderer, scene, prim_path, frequency
         self._mesh = collision_mesh
         self._mesh_config = mesh_config if mesh_config is not None else MESH_CONFIG
+        self._instance_paths = None if instance_paths is None else [str(p) for p in instance_paths]
+        self._instance_in_frame = False
         self._w, self._h = int(resolution[0]), int(resolution[1])         # Isaac resolution = (width, height)
         self._pos = np.zeros(3, np.float32)
         self._orient = np.array([1.0, 0.0, 0.0, 0.0], np.float32)         # (w, x, y, z)
@@ -120,7 +124,52 @@ class GsCamera:
             depth = self._mesh_depth()
         else:
             rgb, depth = self._rgb_depth()
-        return {"rgba": self._r.pack_rgba8(rgb).cpu().numpy(), "distance_to_image_plane": depth.cpu().numpy()}
+        frame = {"rgba": self._r.pack_rgba8(rgb).cpu().numpy(), "distance_to_image_plane": depth.cpu().numpy()}
+        if self._instance_in_frame:
+            frame["instance_id_segmentation"] = self._instance_segmentation()
+        return frame
+
+    # -- instance ids: which object of the collision mesh each pixel shows.  THIS PROJECT'S OWN channel: the reference never reads one
+    # (its object-based success decides on the 2-D map), and the dictionary below follows Isaac Sim's instance_id_segmentation
+    # annotator only as far as its shape is commonly described — nothing of the reference depends on it.
+    def _mesh_ids(self):
+        """ids [H,W] int32 on the GPU (Renderer.render_mesh_ids): the label of the nearest collision-mesh triangle, -1 where none."""
+        if self._mesh is None:
+            raise RuntimeError("instance ids come from the collision mesh: construct the camera with collision_mesh=")
+        return self._r.render_mesh_ids(self._camera(), self._mesh, config=self._mesh_config)
+
+    def get_instance_ids(self) -> np.ndarray:
+        """int32 [H,W]: per pixel the label of the collision-mesh object in view — the index into instance_paths when the mesh was
+        uploaded with labels=tri_prim — and -1 where nothing is hit.  The hit is the one get_depth() reports."""
+        return self._mesh_ids().cpu().numpy()
+
+    def add_instance_id_segmentation_to_frame(self):
+        """get_current_frame() also returns "instance_id_segmentation" from now on (needs collision_mesh=)."""
+        if self._mesh is None:
+            raise RuntimeError("instance ids come from the collision mesh: construct the camera with collision_mesh=")
+        self._instance_in_frame = True
+
+    def _instance_segmentation(self) -> dict:
+        """{"data": uint32 [H,W] = id + 1 (0: nothing hit), "info": {"idToLabels": {"0": "BACKGROUND", str(k + 1): instance_paths[k]}}};
+        without instance_paths, the ids in the frame are named "label_<id>"."""
+        ids = self.get_instance_ids()
+        if self._instance_paths is not None:
+            if ids.max(initial=-1) >= len(self._instance_paths):
+                raise ValueError(f"the mesh has a label {int(ids.max())}, instance_paths names {len(self._instance_paths)}")
+            names = {str(k + 1): p for k, p in enumerate(self._instance_paths)}
+        else:
+            names = {str(int(k) + 1): f"label_{int(k)}" for k in np.unique(ids[ids >= 0])}
+        return {"data": (ids + 1).astype(np.uint32), "info": {"idToLabels": {"0": "BACKGROUND", **names}}}
+
+    def get_instance_id_png(self) -> bytes:
+        """The instance ids as a 16-bit grey PNG of id + 1 (0: nothing hit), encoded on the GPU by Renderer.encode_png's depth16 format
+        with depth_scale 1 and depth_max 65535: integers below 2^24 are exact in fp32 and pass the encoder's truncation unchanged.
+        More than 65 534 distinct labels do not fit and are refused."""
+        ids = self._mesh_ids()
+        n = len(self._instance_paths) if self._instance_paths is not None else int(ids.max().item()) + 1
+        if n > 65534:
+            raise ValueError(f"{n} labels do not fit a 16-bit PNG of id + 1 (at most 65534)")
+        return self._r.encode_png((ids + 1).float().contiguous(), format="depth16", depth_scale=1.0, depth_max=65535.0)[0]
 
     def get_depth(self, clip=(0.1, 6.5)) -> np.ndarray:
         """float32 [H,W] metres, limited to [0.1, 6.5] exactly as SimpleVLNEnv.get_depth does with the simulator's

@@ -51,6 +51,8 @@ def configure(renderer=None, loader=None, scene_root=None, collision=None):
     """collision=True: open_stage also loads the stage's collision payload (/World/scene_collision, an ASCII .usda — a crate file must
     be converted with usdcat first) and the cameras' get_depth() / distance_to_image_plane come from it, as the reference's do
     (simple_env.py:1395-1589); a missing or unreadable payload then raises.  Default off: depth from the Gaussians.
+    The payload's triangles are labelled by their `def Mesh` prim, and the cameras name them (GsCamera.get_instance_ids,
+    add_instance_id_segmentation_to_frame: /World/scene_collision/<prim path below the payload's root>) — this project's own channel.
     renderer: the sage_gs.Renderer frames are drawn with (default: one on cuda:LOCAL_RANK / cuda:0, created at the first
     open_stage).  loader(path, compressed) -> (means, scales, quats, opacities, sh, degree) (default: sage_gs.ply).  scene_root: an
     extra directory searched for `<scene_id>.ply` / `<scene_id>_compressed.ply` when nothing lies beside the referenced USDZ."""
@@ -241,8 +243,11 @@ def _load_collision(usd_path, parsed, r):
     path = rel if os.path.isabs(rel) else os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(usd_path)), rel))
     if not os.path.isfile(path):
         raise FileNotFoundError(f"{usd_path}: collision payload {path} not found")
-    verts, tris = mesh_io.read_usda_mesh(path)
-    return r.upload_mesh(verts, tris, adapter.collision_model_to_world(parsed))
+    verts, tris, tri_prim, paths = mesh_io.read_usda_mesh(path, return_prims=True)
+    mesh = r.upload_mesh(verts, tris, adapter.collision_model_to_world(parsed), labels=tri_prim)
+    # the payload's root prim is composed onto /World/scene_collision: /<root>/chair_3/mesh is /World/scene_collision/chair_3/mesh there
+    mesh.prim_paths = ["/World/scene_collision" + (p[p.index("/", 1):] if "/" in p[1:] else "") for p in paths]
+    return mesh
 
 
 class World:
@@ -300,7 +305,7 @@ def Camera(prim_path: str = "/World/Camera", frequency: int = 30, resolution: Tu
     if st is None:
         raise RuntimeError("Camera(): no stage is open (call open_stage first)")
     cam = adapter.GsCamera(_renderer(), st.scene, prim_path=str(prim_path), frequency=int(frequency), resolution=tuple(resolution),
-                           collision_mesh=st.collision_mesh)
+                           collision_mesh=st.collision_mesh, instance_paths=getattr(st.collision_mesh, "prim_paths", None))
     if "position" in kwargs or "orientation" in kwargs:
         cam.set_world_pose(kwargs.get("position"), kwargs.get("orientation"))
     st.DefinePrim(str(prim_path), "Camera")

@@ -151,7 +151,8 @@ def fan_triangulate(counts: np.ndarray, indices: np.ndarray) -> np.ndarray:
     return np.stack([indices[s], indices[s + k + 1], indices[s + k + 2]], 1) if len(face) else np.zeros((0, 3), np.int64)
 
 
-def parse_usda_mesh_text(text: str) -> Tuple[np.ndarray, np.ndarray]:
+def parse_usda_mesh_text(text: str, return_prims: bool = False):
+    """read_usda_mesh of a layer given as text."""
     text = _strip_comments(text)
     mpu = 1.0
     head = re.match(r"\s*\(", text)
@@ -163,8 +164,9 @@ def parse_usda_mesh_text(text: str) -> Tuple[np.ndarray, np.ndarray]:
             mpu = float(m.group(1))
         root_start = k + 1
     verts, tris, n_off = [], [], 0
+    tri_prim, prim_paths = [], []
 
-    def walk(start, end, parent, kind):
+    def walk(start, end, parent, kind, path=""):
         nonlocal n_off
         own, kids = split_prim(text, start, end)
         M = parent @ xform_from_attrs(own) if kind is not None else parent
@@ -178,23 +180,30 @@ def parse_usda_mesh_text(text: str) -> Tuple[np.ndarray, np.ndarray]:
                 verts.append(p @ M[:3, :3].T + M[:3, 3])
                 tris.append(t + n_off)
                 n_off += len(p)
-        for ktype, _, b, e in kids:
-            walk(b, e, M, ktype or "")
+                if len(t):                                              # a Mesh that contributes triangles: the next index
+                    tri_prim.append(np.full(len(t), len(prim_paths), np.int32))
+                    prim_paths.append(path)
+        for ktype, name, b, e in kids:
+            walk(b, e, M, ktype or "", path + "/" + name)
 
     S = np.eye(4)
     S[:3, :3] *= mpu
     walk(root_start, len(text), S, None)
-    if not verts:
-        return np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64)
-    return np.concatenate(verts), np.concatenate(tris)
+    V, T = (np.concatenate(verts), np.concatenate(tris)) if verts else (np.zeros((0, 3), np.float64), np.zeros((0, 3), np.int64))
+    if not return_prims:
+        return V, T
+    return V, T, (np.concatenate(tri_prim) if tri_prim else np.zeros(0, np.int32)), prim_paths
 
 
-def read_usda_mesh(path: str) -> Tuple[np.ndarray, np.ndarray]:
+def read_usda_mesh(path: str, return_prims: bool = False):
     """(vertices float64 [V,3] in metres, triangles int64 [F,3]) of every `def Mesh` in the ASCII USD layer at `path`, in the layer's
-    root frame (each mesh's own and enclosing transform ops and the layer's metersPerUnit applied)."""
+    root frame (each mesh's own and enclosing transform ops and the layer's metersPerUnit applied).
+    return_prims=True: (vertices, triangles, tri_prim, prim_paths) — which Mesh prim each triangle came from: tri_prim int32 [F] indexes
+    prim_paths, the full prim paths (such as /World/scene_collision/chair_3/mesh) of the Mesh prims that contribute triangles, numbered
+    in traversal order (depth first, children in file order).  These are the labels of Renderer.render_mesh_ids."""
     with open(path, "rb") as fh:
         data = fh.read()
     if data[:8] == b"PXR-USDC":
         raise ValueError(f"{path} is a binary USD crate file, which sage_gs does not parse: convert it to ASCII first "
                          f"(`usdcat {path} -o {path.rsplit('.', 1)[0]}.usda` where USD is installed) and pass the .usda")
-    return parse_usda_mesh_text(data.decode("utf-8", "replace"))
+    return parse_usda_mesh_text(data.decode("utf-8", "replace"), return_prims)

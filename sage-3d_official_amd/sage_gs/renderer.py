@@ -663,10 +663,11 @@ class Renderer:
         return off, ids[slots].astype(np.int64), ids[live].astype(np.int64), splats[live]
 
     # -- collision-mesh depth (include/sage_gs.h sgs_render_mesh_depth*) ---------------------------------------------------------
-    def upload_mesh(self, vertices, triangles, model_to_world=None) -> Mesh:
+    def upload_mesh(self, vertices, triangles, model_to_world=None, labels=None) -> Mesh:
         """vertices [V,3] and triangles [F,3] (int) — NumPy arrays or tensors, on the host or on a device.  The non-rigid part of
         model_to_world (a scale, a shear: USD xformOp:scale / metersPerUnit) is baked into the vertices here, so that the view the
-        library gets stays rigid; the rotation + translation travel with the Mesh and are applied by moving the camera."""
+        library gets stays rigid; the rotation + translation travel with the Mesh and are applied by moving the camera.
+        labels: int32 [F], one object label >= 0 per triangle for render_mesh_ids (set_mesh_labels); None: the triangle's index."""
         rigid, bake = (None, None) if model_to_world is None else _split_model_to_world(model_to_world)
         v = vertices.detach().cpu().numpy() if isinstance(vertices, torch.Tensor) else np.asarray(vertices)
         t = triangles.detach().cpu().numpy() if isinstance(triangles, torch.Tensor) else np.asarray(triangles)
@@ -685,7 +686,14 @@ class Renderer:
             h = C.c_void_p()
             self._lib.check(self._lib.sgs_mesh_upload(self._ctx, int(vf.shape[0]), vf.data_ptr() if vf.numel() else None, int(tf.shape[0]),
                                                       tf.data_ptr() if tf.numel() else None, 1, C.byref(h)), self._ctx)
-        return Mesh(self, h, int(vf.shape[0]), int(tf.shape[0]), rigid)
+        mesh = Mesh(self, h, int(vf.shape[0]), int(tf.shape[0]), rigid)
+        if labels is not None:
+            try:
+                self.set_mesh_labels(mesh, labels)
+            except Exception:
+                mesh.free()
+                raise
+        return mesh
 
     def _mesh_of(self, mesh: Mesh) -> Mesh:
         if not isinstance(mesh, Mesh) or mesh._r is not self:
@@ -736,6 +744,92 @@ class Renderer:
                                                               stats, self._stream()), self._ctx)
         self.last_stats = stats[b - 1].as_dict()
         return (out, [s.as_dict() for s in stats]) if want_stats else out
+
+    # -- collision-mesh object ids (include/sage_gs.h sgs_render_mesh_ids*: this project's own channel, the reference has none) ----
+    def set_mesh_labels(self, mesh: Mesh, labels):
+        """One int32 label per triangle of `mesh`, 0 <= label <= 2^31 - 2 (typically mesh.read_usda_mesh(return_prims=True)'s tri_prim) —
+        a NumPy array or a tensor, on the host or on the device; copied.  None restores the default: a triangle's label is its index.
+        A wrong length, a dtype other than int32 and (for host arrays) labels out of range are refused here; for a device tensor the
+        range is checked by the library on the device.  A refused call leaves the mesh's labels as they were."""
+        mesh = self._mesh_of(mesh)
+        if labels is None:
+            self._lib.check(self._lib.sgs_mesh_set_labels(self._ctx, mesh.handle, None, 0), self._ctx)
+            return
+        if isinstance(labels, torch.Tensor):
+            if labels.dtype != torch.int32:
+                raise ValueError(f"labels must be int32 (got {labels.dtype})")
+            lab = labels.detach().reshape(-1)
+        else:
+            a = np.asarray(labels)
+            if a.dtype != np.int32:
+                raise ValueError(f"labels must be int32 (got {a.dtype})")
+            if a.size and (int(a.min()) < 0 or int(a.max()) > 2 ** 31 - 2):
+                raise ValueError("labels must lie in [0, 2^31 - 2]")
+            lab = torch.from_numpy(np.ascontiguousarray(a.reshape(-1)))
+        if lab.numel() != mesh.n_triangles:
+            raise ValueError(f"{lab.numel()} labels for a mesh of {mesh.n_triangles} triangles")
+        lab = lab.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            torch.cuda.synchronize(self.device)
+            self._lib.check(self._lib.sgs_mesh_set_labels(self._ctx, mesh.handle, lab.data_ptr() if lab.numel() else None, 1), self._ctx)
+
+    def _ids_out(self, out, shape, dtype, name):
+        if out is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        if out.device != self.device or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} {list(shape)} tensor on the renderer's device")
+        return out
+
+    def render_mesh_ids(self, camera: Camera, mesh: Mesh, *, config: Optional[RenderConfig] = None, tile_rows=None,
+                        out: Optional[torch.Tensor] = None, out_depth: Optional[torch.Tensor] = None, return_depth=False, stats=False,
+                        timing=False):
+        """int32 [H,W] on the device: per pixel the label of the triangle of `mesh` whose hit render_mesh_depth reports — the nearest
+        hit with near < z <= far, the least label among hits at bit-equal z — and -1 (_capi.ID_NONE) where nothing is hit.
+        return_depth=True: (ids, depth), depth bit for bit render_mesh_depth's frame.  tile_rows, out (ids) and out_depth as
+        render_mesh_depth's: a band leaves the other rows of both alone.  stats=True appends the frame's statistics (also in
+        last_stats).  The channel is this project's own definition (the reference has no such observation)."""
+        mesh = self._mesh_of(mesh)
+        h, w = camera.height, camera.width
+        out = self._ids_out(out, (h, w), torch.int32, "out")
+        depth = self._ids_out(out_depth, (h, w), torch.float32, "out_depth") if (return_depth or out_depth is not None) else None
+        r0, r1 = (0, -1) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
+        cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
+        cam = self._c_camera(camera, mesh)
+        st = _capi.SgsStats()
+        self._lib.check(self._lib.sgs_render_mesh_ids(self._ctx, mesh.handle, C.byref(cam), C.byref(cfg), r0, r1,
+                                                      depth.data_ptr() if depth is not None else None, out.data_ptr(), C.byref(st),
+                                                      self._stream()), self._ctx)
+        self.last_stats = st.as_dict()
+        ret = (out, depth) if return_depth else (out,)
+        if stats:
+            ret += (self.last_stats,)
+        return ret if len(ret) > 1 else ret[0]
+
+    def render_mesh_ids_batch(self, cameras: Sequence[Camera], mesh: Mesh, *, config: Optional[RenderConfig] = None,
+                              out: Optional[torch.Tensor] = None, out_depth: Optional[torch.Tensor] = None, return_depth=False,
+                              timing=False, want_stats=False):
+        """render_mesh_ids for B cameras of one resolution in one call: int32 [B,H,W], or (ids, depth [B,H,W]) with return_depth, and
+        the frames' statistics last with want_stats.  Every frame equals the one render_mesh_ids draws, bit for bit."""
+        mesh = self._mesh_of(mesh)
+        b = len(cameras)
+        if b == 0:
+            raise ValueError("no cameras")
+        h, w = cameras[0].height, cameras[0].width
+        if any(c.height != h or c.width != w for c in cameras):
+            raise ValueError("all cameras of a batch must share a resolution")
+        out = self._ids_out(out, (b, h, w), torch.int32, "out")
+        depth = self._ids_out(out_depth, (b, h, w), torch.float32, "out_depth") if (return_depth or out_depth is not None) else None
+        cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
+        arr = self._c_cameras(cameras, mesh)
+        st = (_capi.SgsStats * b)()
+        self._lib.check(self._lib.sgs_render_mesh_ids_batch(self._ctx, mesh.handle, arr.ctypes.data, b, C.byref(cfg),
+                                                            depth.data_ptr() if depth is not None else None, out.data_ptr(), st,
+                                                            self._stream()), self._ctx)
+        self.last_stats = st[b - 1].as_dict()
+        ret = (out, depth) if return_depth else (out,)
+        if want_stats:
+            ret += ([s.as_dict() for s in st],)
+        return ret if len(ret) > 1 else ret[0]
 
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""

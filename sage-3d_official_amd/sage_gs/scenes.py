@@ -448,3 +448,25 @@ def make_room_mesh(n_triangles=50_000, seed=1, size=(6.0, 5.0), height=2.8):
     for v, t in parts:
         V.append(v); T.append(t + off); off += len(v)
     return RoomMesh(np.concatenate(V), np.concatenate(T), (sx, sy, height), ((0.0, 0.0, sx, sy),), np.eye(4))
+
+
+ROOM_MESH_PARTS = ("shell",) + tuple(f"box_{k}" for k in range(6)) + ("sphere_0", "sphere_1") + tuple(f"cylinder_{k}" for k in range(3))
+
+
+def make_room_mesh_parts(n_triangles=50_000, seed=1, size=(6.0, 5.0), height=2.8):
+    """(vertices, triangles, part): make_room_mesh's mesh for the same arguments — the arrays are equal — and part int32 [F], the object
+    each triangle belongs to, 0 .. 11 in ROOM_MESH_PARTS' order: the shell, six boxes, two spheres, three cylinders.  These are the
+    labels of the object-id channel's tests (Renderer.render_mesh_ids).
+    make_room_mesh concatenates its twelve closed surfaces, each with a vertex range of its own; a surface is connected, so the vertex
+    spans [min, max] of its triangles chain over its whole range and never reach into the next: the parts are the maximal runs of
+    overlapping spans."""
+    m = make_room_mesh(n_triangles, seed, size, height)
+    lo, hi = m.triangles.min(1), m.triangles.max(1)
+    order = np.argsort(lo, kind="stable")
+    reach = np.maximum.accumulate(hi[order])
+    first = np.concatenate([[True], lo[order][1:] > reach[:-1]])       # a span that starts past everything before it: the next part
+    part = np.empty(len(lo), np.int32)
+    part[order] = np.cumsum(first) - 1
+    if int(part.max()) + 1 != len(ROOM_MESH_PARTS) or (np.diff(part) < 0).any():
+        raise RuntimeError(f"make_room_mesh_parts: found {int(part.max()) + 1} parts, expected {len(ROOM_MESH_PARTS)} in order")
+    return m.vertices, m.triangles, part
