@@ -466,6 +466,56 @@ int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_
  * bytes_needed (nullable) receives the bytes they take end to end. */
 int sgs_png_status(sgs_ctx* ctx, int64_t* bytes_needed);
 
+/* ---- Resizing frames — replaces the host-side resize of the benchmark's low-res mode (run_benchmark.py:1409-1419 for RGB,
+ * :1441-1451 for depth: cv2.resize or PIL's Image.resize to 320x240) and of odd video frames (simple_env.py:2750): the resized frame is
+ * made on the device from the fp32 frame sgs_render* left there and is a frame like any other, so sgs_pack_rgba8, sgs_encode_jpeg and
+ * sgs_encode_png take it unchanged.  No new version: no existing struct changes.
+ *
+ *   Frames   SGS_RESIZE_RGB8: src is fp32 [H,W,3]; each channel first becomes the 8-bit level sgs_pack_rgba8 would write (clamp to
+ *            [0,1], (unsigned)(x * 255 + 0.5)), the LEVELS are resampled in integers, and dst is fp32 [h,w,3] holding the fp32
+ *            nearest k / 255 of every resampled level k — a value that x * 255 + 0.5 takes back to k, fused or not.
+ *            SGS_RESIZE_F32: src is fp32 [H,W], dst fp32 [h,w]; every sample is clipped as it is loaded,
+ *            x < clip_lo ? clip_lo : (x > clip_hi ? clip_hi : x) (NaN stays NaN, as with np.clip): the reference's order, clip in
+ *            get_depth and then resize, which makes the +inf of a pixel that hit nothing finite before it meets a negative weight.
+ *            A window that holds a non-finite sample after the clip gives an unspecified value; every other pixel is unaffected.
+ *   Filters  SGS_RESIZE_BICUBIC is PIL's Image.resize(size) at its default resample, bit for bit: separable convolution, per axis
+ *            scale = in / out, support = 2 max(scale, 1), centre c = (o + 0.5) scale, taps [max((int)(c - support + 0.5), 0),
+ *            min((int)(c + support + 0.5), in)), the cubic with a = -0.5 at (tap - c + 0.5) * (1 / max(scale, 1)), the weights divided by
+ *            their sum in tap order, all in fp64 with multiply and add unfused.  RGB8: weights as (int)(w 2^22 +- 0.5), a sample is
+ *            clamp((2^21 + sum level kk) >> 22, 0, 255); the horizontal pass runs first and writes 8-bit levels, which the vertical
+ *            pass reads.  F32: a sample is (float) sum (double)x w from 0.0 in tap order, unfused; fp32 between the passes.  A pass
+ *            whose in-size equals its out-size is skipped, not run with identity weights.
+ *            SGS_RESIZE_LINEAR is bilinear at half-pixel centres without a prefilter, clamped at the edges — the sampling cv2
+ *            documents for INTER_LINEAR; it is NOT pinned to cv2's bytes but defined exactly: sx = max((2x + 1) W - w, 0),
+ *            x0 = sx div 2w, fx = sx mod 2w (x0 >= W - 1: x0 = W - 1, fx = 0), y likewise; RGB8: (sum of the four corners' level
+ *            wx wy + 2wh) div 4wh in 64-bit integers, the exact bilinear value rounded half up; F32: the weights fx / 2w and fy / 2h
+ *            in fp32, a + (b - a) t horizontally on both rows, then vertically.
+ *   Exact    a frame's values depend on its samples and the parameters alone — not on the batch it is issued in or its place there. */
+enum { SGS_RESIZE_RGB8 = 0, SGS_RESIZE_F32 = 1 };          /* sgs_resize_params.format */
+enum { SGS_RESIZE_BICUBIC = 0, SGS_RESIZE_LINEAR = 1 };    /* sgs_resize_params.filter */
+typedef struct sgs_resize_params {
+    int32_t format;        /* SGS_RESIZE_RGB8 or SGS_RESIZE_F32 */
+    int32_t filter;        /* SGS_RESIZE_BICUBIC or SGS_RESIZE_LINEAR */
+    int32_t dst_width;     /* 1..65535 */
+    int32_t dst_height;    /* 1..65535 */
+    float   clip_lo;       /* SGS_RESIZE_F32: applied to every sample as it is loaded; -inf clips nothing */
+    float   clip_hi;       /*                 +inf clips nothing */
+    int32_t reserved[2];   /* 0 */
+} sgs_resize_params;
+/* SGS_RESIZE_RGB8, SGS_RESIZE_BICUBIC, 320 x 240, -inf, +inf. */
+void sgs_resize_params_default(sgs_resize_params* params);
+/* Resizes n_frames frames of width x height to dst_width x dst_height: frame i is read at src + i * src_frame_stride and written at
+ * dst + i * dst_frame_stride (strides in floats).  src is a DEVICE buffer; dst is a device buffer or pinned host memory the device can
+ * address, as for sgs_pack_rgba8.  Nothing of dst outside the frames is written.  Stream-ordered and asynchronous: the call does not
+ * synchronise (it may, once, when it first sees a pair of sizes or grows its scratch); one resize stream at a time per context.
+ * n_frames == 0 is SGS_OK and launches nothing.  The library owns 4 bytes per pixel of the horizontally resized frames (grown
+ * geometrically) and one tap table per (in-size, out-size, filter, format) and axis, freed by sgs_destroy.
+ * SGS_ERR_INVALID (nothing is ever clamped): an unknown format or filter, reserved != 0, a null buffer with n_frames > 0, n_frames < 0,
+ * a size < 1 or > 65535, frames closer together than their size, clip_lo > clip_hi or either of them NaN, src and dst ranges that
+ * overlap. */
+int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
+               const sgs_resize_params* params, float* dst, int64_t dst_frame_stride, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

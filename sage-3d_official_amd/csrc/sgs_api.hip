@@ -23,6 +23,7 @@
 #include "sgs_mesh.h"
 #include "sgs_jpeg.h"
 #include "sgs_png.h"
+#include "sgs_resize.h"
 
 namespace {
 
@@ -141,6 +142,15 @@ struct PngScratch {
     FileScratch files;
 };
 
+// The resize's scratch (sgs_resize): the horizontally resized frames of a call that runs both passes, and the tap tables of the axes
+// seen so far (a table is never rewritten: a resize still in flight keeps reading its own).
+struct ResizeScratch {
+    struct Entry { int in, out, filter, format, ksize; int* bounds; void* weights; };
+    std::vector<Entry> tables;
+    int64_t mid_cap = 0;
+    unsigned* mid = nullptr;
+};
+
 struct sgs_mesh {
     int64_t n_verts = 0, n_tris = 0;
     float* verts = nullptr;
@@ -153,6 +163,7 @@ struct sgs_ctx {
     MeshScratch mesh;
     JpegScratch jpeg;
     PngScratch png;
+    ResizeScratch resize;
     std::string err;
     Lane lanes[kMaxLanes];
     int n_lanes = 3, next_lane = 0;          // sgs_tuning.lanes: lanes that SGS_FLAG_PIPELINED single frames rotate over
@@ -814,6 +825,11 @@ int sgs_destroy(sgs_ctx* ctx) {
         for (void* b : bufs) if (b) (void)hipFree(b);
         free_file_scratch(ctx->jpeg.files);
         free_file_scratch(ctx->png.files);
+        for (ResizeScratch::Entry& e : ctx->resize.tables) {
+            if (e.bounds) (void)hipFree(e.bounds);
+            if (e.weights) (void)hipFree(e.weights);
+        }
+        if (ctx->resize.mid) (void)hipFree(ctx->resize.mid);
     }
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->row_acc) (void)hipFree(ctx->row_acc);
@@ -1993,6 +2009,122 @@ int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_
 
 int sgs_png_status(sgs_ctx* ctx, int64_t* bytes_needed) {
     return file_status(ctx, "sgs_encode_png", ctx ? &ctx->png.files : nullptr, bytes_needed);
+}
+
+}  // extern "C"
+
+// ---- resize (csrc/sgs_resize.h) ---------------------------------------------------------------------------------------------------
+namespace {
+
+// The tap table of one axis on the device: the context's own of these sizes, built and uploaded on first use (a synchronous copy, so
+// it is complete before any launch that follows).
+int resize_axis(sgs_ctx* ctx, int in, int out, int filter, int format, sgs::ResizeAxis& A) {
+    ResizeScratch& Z = ctx->resize;
+    const ResizeScratch::Entry* hit = nullptr;
+    for (const ResizeScratch::Entry& e : Z.tables)
+        if (e.in == in && e.out == out && e.filter == filter && e.format == format) hit = &e;
+    if (!hit) {
+        const bool fixed = format == SGS_RESIZE_RGB8;
+        sgs::resize::AxisTable T;
+        sgs::resize::build_axis(in, out, fixed, T);
+        ResizeScratch::Entry e = {in, out, filter, format, T.ksize, nullptr, nullptr};
+        const void* w = fixed ? static_cast<const void*>(T.ki.data()) : static_cast<const void*>(T.kd.data());
+        const size_t w_bytes = fixed ? T.ki.size() * sizeof(int) : T.kd.size() * sizeof(double), b_bytes = T.bounds.size() * sizeof(int);
+        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&e.bounds), b_bytes));
+        hipError_t err = hipMalloc(&e.weights, w_bytes);
+        if (err == hipSuccess) err = hipMemcpy(e.bounds, T.bounds.data(), b_bytes, hipMemcpyHostToDevice);
+        if (err == hipSuccess) err = hipMemcpy(e.weights, w, w_bytes, hipMemcpyHostToDevice);
+        if (err != hipSuccess) {
+            (void)hipFree(e.bounds);
+            if (e.weights) (void)hipFree(e.weights);
+            SGS_FAIL(ctx, err == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "sgs_resize: the tap table of %d -> %d: %s", in, out, hipGetErrorString(err));
+        }
+        Z.tables.push_back(e);                 // only a filled table is remembered; never trimmed: a few KB per pair of sizes a context has seen
+        hit = &Z.tables.back();
+    }
+    A.bounds = hit->bounds; A.ksize = hit->ksize;
+    A.ki = format == SGS_RESIZE_RGB8 ? static_cast<const int*>(hit->weights) : nullptr;
+    A.kd = format == SGS_RESIZE_RGB8 ? nullptr : static_cast<const double*>(hit->weights);
+    return SGS_OK;
+}
+
+template <int FMT>
+void resize_launch(const sgs::ResizeJob& J, int filter, bool do_h, bool do_v, int n_frames, hipStream_t st) {
+    const dim3 block(SGS_RESIZE_THREADS);
+    auto grid = [&](long long pixels) { return dim3((unsigned)((pixels + SGS_RESIZE_THREADS - 1) / SGS_RESIZE_THREADS), (unsigned)n_frames); };
+    if (filter == SGS_RESIZE_LINEAR) {
+        hipLaunchKernelGGL(sgs::k_resize_linear<FMT>, grid((long long)J.w * J.h), block, 0, st, J);
+        return;
+    }
+    if (!do_h && !do_v) hipLaunchKernelGGL(sgs::k_resize_copy<FMT>, grid((long long)J.w * J.h), block, 0, st, J);
+    if (do_h) hipLaunchKernelGGL(sgs::k_resize_h<FMT>, grid((long long)J.w * J.H), block, 0, st, J);
+    if (do_v) hipLaunchKernelGGL(sgs::k_resize_v<FMT>, grid((long long)J.w * J.h), block, 0, st, J);
+}
+
+}  // namespace
+
+extern "C" {
+
+void sgs_resize_params_default(sgs_resize_params* p) {
+    if (!p) return;
+    p->format = SGS_RESIZE_RGB8; p->filter = SGS_RESIZE_BICUBIC; p->dst_width = 320; p->dst_height = 240;
+    p->clip_lo = -INFINITY; p->clip_hi = INFINITY; p->reserved[0] = p->reserved[1] = 0;
+}
+
+int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
+               const sgs_resize_params* p, float* dst, int64_t dst_frame_stride, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_resize";
+    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: params is NULL", who);
+    if (p->format != SGS_RESIZE_RGB8 && p->format != SGS_RESIZE_F32)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: format %d is neither SGS_RESIZE_RGB8 nor SGS_RESIZE_F32", who, p->format);
+    if (p->filter != SGS_RESIZE_BICUBIC && p->filter != SGS_RESIZE_LINEAR)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: filter %d is neither SGS_RESIZE_BICUBIC nor SGS_RESIZE_LINEAR", who, p->filter);
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = {%d, %d}, must be 0", who, p->reserved[0], p->reserved[1]);
+    if (n_frames < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
+    if (width < 1 || height < 1 || width > 65535 || height > 65535) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: source %d x %d is outside 1..65535", who, width, height);
+    if (p->dst_width < 1 || p->dst_height < 1 || p->dst_width > 65535 || p->dst_height > 65535)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: destination %d x %d is outside 1..65535", who, p->dst_width, p->dst_height);
+    if (std::isnan(p->clip_lo) || std::isnan(p->clip_hi)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: clip bound is NaN", who);
+    if (p->clip_lo > p->clip_hi) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: clip_lo %g is above clip_hi %g", who, (double)p->clip_lo, (double)p->clip_hi);
+    if (n_frames == 0) return SGS_OK;
+    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
+    if (!dst) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dst", who);
+    const int ch = p->format == SGS_RESIZE_RGB8 ? 3 : 1;
+    const int64_t src_floats = (int64_t)width * height * ch, dst_floats = (int64_t)p->dst_width * p->dst_height * ch;
+    if (n_frames > 1 && src_frame_stride < src_floats)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src frames overlap (stride %lld floats, a frame has %lld)", who, (long long)src_frame_stride, (long long)src_floats);
+    if (n_frames > 1 && dst_frame_stride < dst_floats)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dst frames overlap (stride %lld floats, a frame has %lld)", who, (long long)dst_frame_stride, (long long)dst_floats);
+    {
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
+        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_frames - 1) * src_frame_stride + src_floats) * 4);
+        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_frames - 1) * dst_frame_stride + dst_floats) * 4);
+        if (s0 < d1 && d0 < s1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src and dst overlap", who);
+    }
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    sgs::ResizeJob J;
+    memset(&J, 0, sizeof J);
+    J.W = width; J.H = height; J.w = p->dst_width; J.h = p->dst_height;
+    J.src_stride = src_frame_stride; J.dst_stride = dst_frame_stride; J.clip_lo = p->clip_lo; J.clip_hi = p->clip_hi;
+    const bool bicubic = p->filter == SGS_RESIZE_BICUBIC;
+    const bool do_h = bicubic && J.W != J.w, do_v = bicubic && J.H != J.h;
+    J.h_to_dst = !do_v; J.v_from_src = !do_h;
+    int rc;
+    if (do_h && (rc = resize_axis(ctx, J.W, J.w, p->filter, p->format, J.ax)) != SGS_OK) return rc;
+    if (do_v && (rc = resize_axis(ctx, J.H, J.h, p->filter, p->format, J.ay)) != SGS_OK) return rc;
+    const int kMaxFrames = 65535;              // gridDim.y
+    if (do_h && do_v && (rc = reserve(ctx, ctx->resize.mid, ctx->resize.mid_cap, (int64_t)std::min(n_frames, kMaxFrames) * J.H * J.w)) != SGS_OK) return rc;
+    J.mid = ctx->resize.mid;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFrames) {
+        J.src = src + (int64_t)f0 * src_frame_stride; J.dst = dst + (int64_t)f0 * dst_frame_stride;
+        const int n = std::min(kMaxFrames, n_frames - f0);
+        if (p->format == SGS_RESIZE_RGB8) resize_launch<sgs::RESIZE_RGB8>(J, p->filter, do_h, do_v, n, st);
+        else resize_launch<sgs::RESIZE_F32>(J, p->filter, do_h, do_v, n, st);
+    }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
 }
 
 }  // extern "C"

@@ -35,7 +35,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_mesh_upload", "sgs_mesh_free", "sgs_mesh_set_record_capacity", "sgs_render_mesh_depth", "sgs_render_mesh_depth_batch",
            "sgs_mesh_set_labels", "sgs_render_mesh_ids", "sgs_render_mesh_ids_batch",
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
-           "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status")
+           "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
+           "sgs_resize_params_default", "sgs_resize")
 
 
 class SgsError(RuntimeError):
@@ -101,6 +102,31 @@ def png_params(format="rgb8", depth_scale=10000.0, depth_max=6.5):
             raise ValueError("format must be 'rgb8' or 'depth16'")
         format = PNG_FORMAT[format]
     return SgsPngParams(int(format), float(depth_scale), float(depth_max), 0)
+
+
+RESIZE_RGB8, RESIZE_F32 = 0, 1
+RESIZE_FORMAT = {"rgb8": RESIZE_RGB8, "f32": RESIZE_F32}
+RESIZE_BICUBIC, RESIZE_LINEAR = 0, 1
+RESIZE_FILTER = {"bicubic": RESIZE_BICUBIC, "linear": RESIZE_LINEAR}
+
+
+class SgsResizeParams(C.Structure):
+    """include/sage_gs.h sgs_resize_params."""
+    _fields_ = [("format", C.c_int32), ("filter", C.c_int32), ("dst_width", C.c_int32), ("dst_height", C.c_int32),
+                ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def resize_params(format="rgb8", filter="bicubic", dst_width=320, dst_height=240, clip_lo=float("-inf"), clip_hi=float("inf")):
+    """sgs_resize_params of a format given as "rgb8" / "f32" and a filter given as "bicubic" / "linear" (or SGS_RESIZE_* themselves)."""
+    if isinstance(format, str):
+        if format not in RESIZE_FORMAT:
+            raise ValueError("format must be 'rgb8' or 'f32'")
+        format = RESIZE_FORMAT[format]
+    if isinstance(filter, str):
+        if filter not in RESIZE_FILTER:
+            raise ValueError("filter must be 'bicubic' or 'linear'")
+        filter = RESIZE_FILTER[filter]
+    return SgsResizeParams(int(format), int(filter), int(dst_width), int(dst_height), float(clip_lo), float(clip_hi))
 
 
 class SgsStats(C.Structure):
@@ -186,6 +212,8 @@ class Lib:
         lib.sgs_png_bound.argtypes = [i32, i32, C.POINTER(SgsPngParams)]; lib.sgs_png_bound.restype = i64
         lib.sgs_encode_png.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsPngParams), vp, i64, vp, vp, vp]
         lib.sgs_png_status.argtypes = [vp, C.POINTER(i64)]
+        lib.sgs_resize_params_default.argtypes = [C.POINTER(SgsResizeParams)]; lib.sgs_resize_params_default.restype = None
+        lib.sgs_resize.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsResizeParams), vp, i64, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

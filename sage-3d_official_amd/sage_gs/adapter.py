@@ -25,12 +25,25 @@ MESH_CONFIG = RenderConfig(near=0.01)
 class GsCamera:
     def __init__(self, renderer: Renderer, scene, prim_path: str = "/World/Camera", frequency: int = 30,
                  resolution: Tuple[int, int] = (640, 480), config: Optional[RenderConfig] = None, collision_mesh=None,
-                 mesh_config: Optional[RenderConfig] = None, instance_paths: Optional[Sequence[str]] = None):
+                 mesh_config: Optional[RenderConfig] = None, instance_paths: Optional[Sequence[str]] = None,
+                 output_size: Optional[Tuple[int, int]] = None, resample: str = "bicubic"):
         """collision_mesh: a Mesh (Renderer.upload_mesh) — get_depth() / get_current_frame()["distance_to_image_plane"] then come
         from it, as the reference's come from /World/scene_collision (simple_env.py:1395-1589); mesh_config: its near / far (default
         MESH_CONFIG).  Without a mesh, depth is the Gaussians' expected depth, as before.
         instance_paths: the prim path of every label of the mesh (mesh.read_usda_mesh(return_prims=True)'s prim_paths, the mesh uploaded
-        with labels=tri_prim) — the names of the instance-id channel (get_instance_ids, add_instance_id_segmentation_to_frame)."""
+        with labels=tri_prim) — the names of the instance-id channel (get_instance_ids, add_instance_id_segmentation_to_frame).
+        output_size=(w, h): the camera still renders at `resolution`, with unchanged intrinsics, and every colour and depth getter
+        returns the picture resized on the device (Renderer.resize with `resample`: "bicubic" is PIL's Image.resize((w, h)) bit for
+        bit, "linear" bilinear) — what the benchmark's low-res mode makes of each observation on the host
+        (run_benchmark.py:1409-1419, 1441-1451); a loop that finds the frame's shape already (h, w) skips its own resize.  Depth is
+        clipped on the device, then resized, then not clipped again.  The instance-id channel is NOT resized — ids do not interpolate
+        — and keeps the render resolution.  None (default): every method is what it is without the argument."""
+        if resample not in ("bicubic", "linear"):
+            raise ValueError("resample must be 'bicubic' or 'linear'")
+        self._out = None if output_size is None else (int(output_size[0]), int(output_size[1]))
+        if self._out is not None and (min(self._out) < 1 or max(self._out) > 65535):
+            raise ValueError("output_size must be (width, height) within 1..65535")
+        self._resample = resample
         self._r, self._scene, self.prim_path, self.frequency = renderer, scene, prim_path, frequency
         self._mesh = collision_mesh
         self._mesh_config = mesh_config if mesh_config is not None else MESH_CONFIG
@@ -62,14 +75,25 @@ class GsCamera:
     def get_resolution(self):
         return self._w, self._h
 
+    def get_output_size(self):
+        """(width, height) of the pictures the getters return: output_size, or the resolution without one."""
+        return self._out if self._out is not None else (self._w, self._h)
+
+    def _resized(self, frames, kind="rgb", clip=None):
+        """`frames` as the getters return them: resized to output_size on the device (with one), else unchanged."""
+        if self._out is None:
+            return frames
+        return self._r.resize(frames.contiguous(), self._out, filter=self._resample, kind=kind, clip=clip)
+
     def _camera(self) -> Camera:
         f = self._w * self._focal_over_aperture
         return Camera(self._w, self._h, f, f, self._w / 2.0, self._h / 2.0,
                       cam_conv.view_from_isaac_pose(self._pos, self._orient))
 
     def get_rgb_tensor(self):
-        """float32 [H,W,3] on the GPU (linear RGB) — for consumers that stay on the device."""
-        return self._r.render(self._camera(), self._scene, config=self._config)
+        """float32 [H,W,3] on the GPU (linear RGB) — for consumers that stay on the device.  With output_size: [h,w,3] on the levels
+        k / 255 (Renderer.resize)."""
+        return self._resized(self._r.render(self._camera(), self._scene, config=self._config))
 
     def get_rgba(self, copy: bool = True) -> np.ndarray:
         """uint8 [H,W,4], alpha 255 — what `cam.get_rgba()` returns (simple_env.py:1380; generate_images.py:428).  Render, pack and
@@ -79,7 +103,10 @@ class GsCamera:
         renderer, or a caller that keeps its last N observations.  copy=False: a VIEW of the renderer's pinned ring of depth 2, which all
         cameras of one resolution on this renderer SHARE — the third get_rgba() at that resolution, from any of them, overwrites the
         first; for the reference's own callers, which copy at once (generate_images.py:431 `.copy()`, simple_env.py:1386 `.astype`)."""
-        img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config)
+        if self._out is None:
+            img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config)
+        else:
+            img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config, output_size=self._out, resample=self._resample)
         return img.copy() if copy else img
 
     def get_jpeg(self, quality: int = 75) -> bytes:
@@ -99,7 +126,10 @@ class GsCamera:
         link.  The lower clip bound is applied on the device before the encoder; its upper bound is the encoder's depth_max."""
         import torch
         depth = self._mesh_depth() if self._mesh is not None else self._rgb_depth()[1]
-        depth = torch.clamp(depth, min=float(clip[0])).contiguous()
+        if self._out is not None:        # clipped as it is loaded, resized, and not clipped again below the encoder's own depth_max
+            depth = self._resized(depth, "depth", (float(clip[0]), float(clip[1])))
+        else:
+            depth = torch.clamp(depth, min=float(clip[0])).contiguous()
         return self._r.encode_png(depth, format="depth16", depth_scale=10000.0, depth_max=float(clip[1]))[0]
 
     def _mesh_depth(self):
@@ -118,13 +148,15 @@ class GsCamera:
         return rgb, depth
 
     def get_current_frame(self) -> dict:
-        """{'rgba': uint8 [H,W,4], 'distance_to_image_plane': float32 [H,W]} (simple_env.py:286,1425,1659)."""
+        """{'rgba': uint8 [H,W,4], 'distance_to_image_plane': float32 [H,W]} (simple_env.py:286,1425,1659).  With output_size both are
+        resized; the distance is the simulator's raw one (+inf where nothing is hit) and is resized unclipped: a pixel whose window
+        holds such a sample is unspecified (get_depth() clips first, as the reference's get_depth does)."""
         if self._mesh is not None:
             rgb = self._r.render(self._camera(), self._scene, config=self._config)
             depth = self._mesh_depth()
         else:
             rgb, depth = self._rgb_depth()
-        frame = {"rgba": self._r.pack_rgba8(rgb).cpu().numpy(), "distance_to_image_plane": depth.cpu().numpy()}
+        frame = {"rgba": self._r.pack_rgba8(self._resized(rgb)).cpu().numpy(), "distance_to_image_plane": self._resized(depth, "depth").cpu().numpy()}
         if self._instance_in_frame:
             frame["instance_id_segmentation"] = self._instance_segmentation()
         return frame
@@ -176,6 +208,8 @@ class GsCamera:
         distance_to_image_plane (simple_env.py:1573-1578: astype(float32), np.clip(depth, 0.1, 6.5)); a pixel that hit
         nothing (inf) therefore reads 6.5.  With a collision mesh, from the mesh (the reference's source)."""
         depth = self._mesh_depth() if self._mesh is not None else self._rgb_depth()[1]
+        if self._out is not None:        # the reference's order: clip (on the device, as the samples are loaded), then resize
+            return self._resized(depth, "depth", None if clip is None else (float(clip[0]), float(clip[1]))).cpu().numpy()
         d = depth.cpu().numpy().astype(np.float32)
         return np.clip(d, clip[0], clip[1]) if clip is not None else d
 

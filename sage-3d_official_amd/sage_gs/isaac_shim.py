@@ -44,10 +44,11 @@ import numpy as np
 
 from . import adapter
 
-_state = {"renderer": None, "loader": None, "stage": None, "app": None, "scene_root": None, "collision": False}
+_state = {"renderer": None, "loader": None, "stage": None, "app": None, "scene_root": None, "collision": False,
+          "output_size": None, "resample": "bicubic"}
 
 
-def configure(renderer=None, loader=None, scene_root=None, collision=None):
+def configure(renderer=None, loader=None, scene_root=None, collision=None, output_size=None, resample=None):
     """collision=True: open_stage also loads the stage's collision payload (/World/scene_collision, an ASCII .usda — a crate file must
     be converted with usdcat first) and the cameras' get_depth() / distance_to_image_plane come from it, as the reference's do
     (simple_env.py:1395-1589); a missing or unreadable payload then raises.  Default off: depth from the Gaussians.
@@ -55,7 +56,9 @@ def configure(renderer=None, loader=None, scene_root=None, collision=None):
     add_instance_id_segmentation_to_frame: /World/scene_collision/<prim path below the payload's root>) — this project's own channel.
     renderer: the sage_gs.Renderer frames are drawn with (default: one on cuda:LOCAL_RANK / cuda:0, created at the first
     open_stage).  loader(path, compressed) -> (means, scales, quats, opacities, sh, degree) (default: sage_gs.ply).  scene_root: an
-    extra directory searched for `<scene_id>.ply` / `<scene_id>_compressed.ply` when nothing lies beside the referenced USDZ."""
+    extra directory searched for `<scene_id>.ply` / `<scene_id>_compressed.ply` when nothing lies beside the referenced USDZ.
+    output_size=(w, h), resample="bicubic" | "linear": handed to the cameras made from now on (GsCamera: they render at their resolution
+    and return every picture resized on the device, as the benchmark's low-res mode resizes it on the host)."""
     if renderer is not None:
         _state["renderer"] = renderer
     if loader is not None:
@@ -64,6 +67,10 @@ def configure(renderer=None, loader=None, scene_root=None, collision=None):
         _state["scene_root"] = scene_root
     if collision is not None:
         _state["collision"] = bool(collision)
+    if output_size is not None:
+        _state["output_size"] = (int(output_size[0]), int(output_size[1]))
+    if resample is not None:
+        _state["resample"] = str(resample)
 
 
 def _renderer():
@@ -305,7 +312,8 @@ def Camera(prim_path: str = "/World/Camera", frequency: int = 30, resolution: Tu
     if st is None:
         raise RuntimeError("Camera(): no stage is open (call open_stage first)")
     cam = adapter.GsCamera(_renderer(), st.scene, prim_path=str(prim_path), frequency=int(frequency), resolution=tuple(resolution),
-                           collision_mesh=st.collision_mesh, instance_paths=getattr(st.collision_mesh, "prim_paths", None))
+                           collision_mesh=st.collision_mesh, instance_paths=getattr(st.collision_mesh, "prim_paths", None),
+                           output_size=_state["output_size"], resample=_state["resample"])
     if "position" in kwargs or "orientation" in kwargs:
         cam.set_world_pose(kwargs.get("position"), kwargs.get("orientation"))
     st.DefinePrim(str(prim_path), "Camera")

@@ -542,12 +542,17 @@ class Renderer:
             ring = self._host_rings[key] = HostFrames(self, key[0], key[1])
         return ring
 
-    def render_rgba8_host(self, camera: Camera, gaussians, *, config: Optional[RenderConfig] = None, tonemap: Optional[str] = None) -> np.ndarray:
+    def render_rgba8_host(self, camera: Camera, gaussians, *, config: Optional[RenderConfig] = None, tonemap: Optional[str] = None,
+                          output_size=None, resample: str = "bicubic") -> np.ndarray:
         """One frame as the reference's callers receive it: uint8 [H,W,4] (alpha 255) in HOST memory (simple_env.py:1380-1386;
         generate_images.py:428-431).  Render and pack are enqueued back to back on the current stream — the pack kernel writes the
         pinned host buffer itself (no device twin, no copy engine, no pageable staging copy) — and the call waits once.  The array is renderer-owned
-        and stays valid until the next-but-one call at this resolution (the reference's callers copy what they keep)."""
+        and stays valid until the next-but-one call at this resolution (the reference's callers copy what they keep).
+        output_size=(w, h): the frame is rendered at the camera's resolution, resized on the device (resize: `resample`) and packed into
+        the pinned ring of the output size — render, resize and pack back to back, still one wait."""
         scene = self._scene_of(gaussians)
+        if output_size is not None:
+            return self._render_resized_rgba8_host(camera, scene, config, tonemap, (int(output_size[0]), int(output_size[1])), resample)
         ring = self.host_frames((camera.height, camera.width, 4))
         rgb = self.render(camera, scene, config=config, out=ring.rgb_scratch(), sync=False)
         h = ring.submit(rgb, tonemap=tonemap, direct=True)
@@ -559,6 +564,33 @@ class Renderer:
             h.wait()
             rgb = self.render(camera, scene, config=config, out=ring.rgb_scratch(), sync=True)
             h = ring.submit(rgb, tonemap=tonemap, direct=True)
+        return h.wait()
+
+    def _render_resized_rgba8_host(self, camera: Camera, scene, config, tonemap, size, resample) -> np.ndarray:
+        """render_rgba8_host with output_size: the full-resolution frame goes into a scratch of its own (cached per resolution), the
+        resized one into the output ring's."""
+        if tonemap is not None and tonemap != "reinhard":
+            raise ValueError("tonemap must be None or 'reinhard'")
+        ring = self.host_frames((size[1], size[0], 4))
+        full = self.__dict__.setdefault("_resize_sources", {})
+        key = (camera.height, camera.width)
+        if key not in full:
+            full[key] = torch.zeros(key + (3,), dtype=torch.float32, device=self.device)
+
+        def issue(sync):
+            rgb = self.render(camera, scene, config=config, out=full[key], sync=sync)
+            if tonemap is not None:                      # (before the levels are made, as in pack_rgba8)
+                rgb = rgb / (1.0 + rgb.clamp_min(0.0))
+            return ring.submit(self.resize(rgb, size, filter=resample, out=ring.rgb_scratch()), direct=True)
+
+        h = issue(False)
+        try:
+            self.sync()
+        except _capi.SgsError as e:
+            if e.code != -4:             # SGS_ERR_OVERFLOW: see render_rgba8_host
+                raise
+            h.wait()
+            h = issue(True)
         return h.wait()
 
     # -- JPEG files made on the device (include/sage_gs.h sgs_encode_jpeg) ------------------------------------------------------
@@ -642,6 +674,45 @@ class Renderer:
                                                      C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
                                                      self._stream()), self._ctx)
         return self._encode_files(n, cap, issue)
+
+    # -- frames resized on the device (include/sage_gs.h sgs_resize) ------------------------------------------------------------
+    def resize(self, frames: torch.Tensor, size, *, filter: str = "bicubic", kind: str = "rgb", clip=None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float32 frames on the device resized there to size = (width, height), as Pillow and Isaac give sizes: what the benchmark's
+        low-res mode does on the host (run_benchmark.py:1409-1419, 1441-1451).  kind="rgb": [H,W,3] or [n,H,W,3] colour; the 8-bit
+        LEVELS get_rgba() shows are resampled, and the result is a frame on k / 255 that pack_rgba8, encode_jpeg and encode_png show as
+        exactly those levels.  kind="depth": [H,W] or [n,H,W]; clip=(lo, hi) is applied to every sample as it is loaded (the reference
+        clips in get_depth, then resizes).  filter="bicubic" is PIL's Image.resize(size) at its default resample, bit for bit;
+        "linear" is bilinear at half-pixel centres (the sampling cv2 documents for INTER_LINEAR; not pinned to cv2's bytes).
+        out: a contiguous float32 tensor of the result's shape on the device to write into.  Asynchronous on the current stream."""
+        if kind not in ("rgb", "depth"):
+            raise ValueError("kind must be 'rgb' or 'depth'")
+        tail = 1 if kind == "rgb" else 0
+        if clip is not None and kind != "depth":
+            raise ValueError("clip applies to kind='depth' only")
+        lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
+        w, h = int(size[0]), int(size[1])
+        params = _capi.resize_params("rgb8" if tail else "f32", filter, w, h, lo, hi)
+        single = frames.dim() == 2 + tail
+        if single:
+            frames = frames.unsqueeze(0)
+        if (frames.device != self.device or frames.dtype != torch.float32 or frames.dim() != 3 + tail or (tail and frames.shape[-1] != 3)
+                or (frames.shape[0] > 0 and not frames[0].is_contiguous())):
+            raise ValueError("frames must be float32 [H,W,3] / [n,H,W,3] (rgb) or [H,W] / [n,H,W] (depth) on the renderer's device "
+                             "with contiguous frames")
+        n, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        shape = (n, h, w, 3) if tail else (n, h, w)
+        if out is None:
+            res = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            if (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous()
+                    or tuple(out.shape) != (shape[1:] if single else shape)):
+                raise ValueError("out must be a contiguous float32 tensor of the result's shape on the renderer's device")
+            res = out.unsqueeze(0) if single else out
+        ch = 3 if tail else 1
+        self._lib.check(self._lib.sgs_resize(self._ctx, frames.data_ptr(), W, H, n, int(frames.stride(0)) if n > 1 else H * W * ch,
+                                             C.byref(params), res.data_ptr(), h * w * ch, self._stream()), self._ctx)
+        return res[0] if single else res
 
     # -- test hooks -------------------------------------------------------------------------------
     def debug_buffer(self, what, dtype):
