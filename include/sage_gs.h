@@ -516,6 +516,41 @@ void sgs_resize_params_default(sgs_resize_params* params);
 int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
                const sgs_resize_params* params, float* dst, int64_t dst_frame_stride, void* hip_stream);
 
+/* ---- Per-frame visible-object table — which objects a frame shows, how large, where in the picture, how near: one row per label,
+ * reduced on the device from the id frame sgs_render_mesh_ids* wrote (and the depth beside it), so that a few dozen rows cross the
+ * link where the id frame is 4 bytes a pixel.  Like the id channel this is THIS PROJECT'S definition: the reference reads no such
+ * observation (Isaac Sim's camera offers bounding_box_2d_tight beside instance_id_segmentation; nothing of the reference depends on
+ * either).  No new version: no existing struct changes.
+ *
+ *   Rows     row k of a frame describes label k, 0 <= k < n_labels: the pixels of the frame whose id == k.  Every row of every frame
+ *            is written, empty ones included; what out_rows held before does not matter.
+ *   Counts   out_counts[f][0] = pixels equal to SGS_ID_NONE; out_counts[f][1] = pixels whose id is neither SGS_ID_NONE nor in
+ *            [0, n_labels): they are counted there and enter no row, which is not an error here.  For every frame
+ *            sum_k n_pixels + counts[0] + counts[1] == height * width.
+ *   z_min    a minimum over the fp32 BIT PATTERNS of the label's depth samples, read as uint32, among those <= 0x7F800000: +0,
+ *            denormals, positive finite values and +inf enter; negative numbers, -0 and NaNs do not (their pixels still count in
+ *            every other field).  For the frames of the mesh path (positive z, +inf where nothing is hit) it is the plain minimum.
+ *   Exact    every field is an integer count, sum, minimum or maximum, so a frame's table depends on its pixels and n_labels alone —
+ *            not on the batch it is issued in, its place there, frame_stride, or how the kernel splits the frame: it equals the table
+ *            of the frame alone, bit for bit.  Kernels: sage-3d_official_amd/csrc/sgs_objects.h. */
+typedef struct sgs_object_row {      /* 40 bytes, 8-byte aligned; row k of a frame's table describes label k */
+    uint32_t n_pixels;               /* pixels of the frame whose id == k */
+    int32_t  x_min, y_min;           /* least x / y among them;            INT32_MAX in an empty row */
+    int32_t  x_end, y_end;           /* greatest x / y among them, plus 1; 0 in an empty row         */
+    float    z_min;                  /* least depth among them (rule above); +inf in an empty row, and everywhere when depth == NULL */
+    uint64_t sum_x, sum_y;           /* sum of x, sum of y over them (centroid = sum / n_pixels); 0 in an empty row */
+} sgs_object_row;
+/* n_frames frames of height x width: frame f's ids at ids + f * frame_stride and (depth nullable) its depth at depth + f * frame_stride
+ * (elements; the same stride for both), laid out as sgs_render_mesh_ids_batch writes them — but any int32 frame is accepted.  ids and
+ * depth are DEVICE buffers; out_rows [n_frames][n_labels] and out_counts [n_frames][2] are device buffers too: the kernels update them
+ * with integer atomics (add, unsigned min / max), which a link to pinned host memory need not carry, so unlike sgs_pack_rgba8's output
+ * they must not be host memory.  Stream-ordered and asynchronous, as the encoders are: the call never synchronises, owns no scratch and
+ * leaves none behind.  Two launches: a clear of the table and one reduction over frames x regions of a frame.
+ * SGS_ERR_INVALID, before anything is enqueued or written: null ids, out_rows or out_counts; n_frames < 1; height < 1 or width < 1;
+ * height * width > 2^31 - 1; frame_stride < height * width; n_labels < 1. */
+int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n_frames, int height, int width, int64_t frame_stride,
+                     int32_t n_labels, sgs_object_row* out_rows, uint32_t* out_counts, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@
 #include "sgs_jpeg.h"
 #include "sgs_png.h"
 #include "sgs_resize.h"
+#include "sgs_objects.h"
 
 namespace {
 
@@ -2122,6 +2123,48 @@ int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_fram
         const int n = std::min(kMaxFrames, n_frames - f0);
         if (p->format == SGS_RESIZE_RGB8) resize_launch<sgs::RESIZE_RGB8>(J, p->filter, do_h, do_v, n, st);
         else resize_launch<sgs::RESIZE_F32>(J, p->filter, do_h, do_v, n, st);
+    }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_object_table ------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(sgs_object_row) == sizeof(sgs::ObjRow) && alignof(sgs_object_row) == 8, "sgs_object_row is 40 bytes, 8-byte aligned");
+
+extern "C" {
+
+int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n_frames, int height, int width, int64_t frame_stride,
+                     int32_t n_labels, sgs_object_row* out_rows, uint32_t* out_counts, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_object_table";
+    if (!ids) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null ids", who);
+    if (!out_rows) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_rows", who);
+    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
+    if (height < 1 || width < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d", who, width, height);
+    const int64_t pixels = (int64_t)height * width;
+    if (pixels > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d has more than 2^31 - 1 pixels", who, width, height);
+    if (frame_stride < pixels)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (stride %lld elements, a frame has %lld)", who, (long long)frame_stride, (long long)pixels);
+    if (n_labels < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_labels = %d", who, (int)n_labels);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::ObjJob J;
+    J.ids = ids; J.depth = depth; J.rows = reinterpret_cast<sgs::ObjRow*>(out_rows); J.counts = out_counts;
+    J.stride = frame_stride; J.W = width; J.H = height; J.n_labels = n_labels; J.n_frames = n_frames;
+    const int64_t n_rows = (int64_t)n_frames * n_labels;
+    const int64_t clear_blocks = std::min<int64_t>((std::max<int64_t>(n_rows, 2ll * n_frames) + SGS_OBJ_THREADS - 1) / SGS_OBJ_THREADS, 65536);
+    hipLaunchKernelGGL(sgs::k_obj_clear, dim3((unsigned)clear_blocks), dim3(SGS_OBJ_THREADS), 0, st, J);
+    const unsigned regions = (unsigned)((pixels + SGS_OBJ_REGION - 1) / SGS_OBJ_REGION);
+    const int kMaxFrames = 65535;              // gridDim.y
+    for (int f0 = 0; f0 < n_frames; f0 += kMaxFrames) {
+        sgs::ObjJob K = J;
+        K.ids = ids + (int64_t)f0 * frame_stride; K.depth = depth ? depth + (int64_t)f0 * frame_stride : nullptr;
+        K.rows = J.rows + (int64_t)f0 * n_labels; K.counts = out_counts + 2ll * f0;
+        K.n_frames = std::min(kMaxFrames, n_frames - f0);
+        hipLaunchKernelGGL(sgs::k_obj_reduce, dim3(regions, (unsigned)K.n_frames), dim3(SGS_OBJ_THREADS), 0, st, K);
     }
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;

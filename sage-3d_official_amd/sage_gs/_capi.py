@@ -36,7 +36,7 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_mesh_set_labels", "sgs_render_mesh_ids", "sgs_render_mesh_ids_batch",
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
-           "sgs_resize_params_default", "sgs_resize")
+           "sgs_resize_params_default", "sgs_resize", "sgs_object_table")
 
 
 class SgsError(RuntimeError):
@@ -129,6 +129,24 @@ def resize_params(format="rgb8", filter="bicubic", dst_width=320, dst_height=240
     return SgsResizeParams(int(format), int(filter), int(dst_width), int(dst_height), float(clip_lo), float(clip_hi))
 
 
+class SgsObjectRow(C.Structure):
+    """include/sage_gs.h sgs_object_row: row k of a frame's visible-object table describes label k."""
+    _fields_ = [("n_pixels", C.c_uint32), ("x_min", C.c_int32), ("y_min", C.c_int32), ("x_end", C.c_int32), ("y_end", C.c_int32),
+                ("z_min", C.c_float), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64)]
+
+
+def _object_row_dtype():
+    import numpy as np
+    return np.dtype([("n_pixels", "<u4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_end", "<i4"), ("y_end", "<i4"), ("z_min", "<f4"),
+                     ("sum_x", "<u8"), ("sum_y", "<u8")])
+
+
+OBJECT_ROW_DTYPE = _object_row_dtype()       # the same 40 bytes as a NumPy record: ten int32 words of Renderer.object_table's rows
+OBJECT_ROW_WORDS = 10
+VISIBLE_OBJECT_DTYPE = __import__("numpy").dtype([("label", "<i4")] + [(n, OBJECT_ROW_DTYPE.fields[n][0]) for n in OBJECT_ROW_DTYPE.names])
+assert OBJECT_ROW_DTYPE.itemsize == C.sizeof(SgsObjectRow) == 4 * OBJECT_ROW_WORDS
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -214,6 +232,7 @@ class Lib:
         lib.sgs_png_status.argtypes = [vp, C.POINTER(i64)]
         lib.sgs_resize_params_default.argtypes = [C.POINTER(SgsResizeParams)]; lib.sgs_resize_params_default.restype = None
         lib.sgs_resize.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsResizeParams), vp, i64, vp]
+        lib.sgs_object_table.argtypes = [vp, vp, vp, i32, i32, i32, i64, C.c_int32, vp, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -49,6 +49,7 @@ class GsCamera:
         self._mesh_config = mesh_config if mesh_config is not None else MESH_CONFIG
         self._instance_paths = None if instance_paths is None else [str(p) for p in instance_paths]
         self._instance_in_frame = False
+        self._boxes_in_frame = False
         self._w, self._h = int(resolution[0]), int(resolution[1])         # Isaac resolution = (width, height)
         self._pos = np.zeros(3, np.float32)
         self._orient = np.array([1.0, 0.0, 0.0, 0.0], np.float32)         # (w, x, y, z)
@@ -159,6 +160,8 @@ class GsCamera:
         frame = {"rgba": self._r.pack_rgba8(self._resized(rgb)).cpu().numpy(), "distance_to_image_plane": self._resized(depth, "depth").cpu().numpy()}
         if self._instance_in_frame:
             frame["instance_id_segmentation"] = self._instance_segmentation()
+        if self._boxes_in_frame:
+            frame["bounding_box_2d_tight"] = self._bounding_boxes()
         return frame
 
     # -- instance ids: which object of the collision mesh each pixel shows.  THIS PROJECT'S OWN channel: the reference never reads one
@@ -185,13 +188,62 @@ class GsCamera:
         """{"data": uint32 [H,W] = id + 1 (0: nothing hit), "info": {"idToLabels": {"0": "BACKGROUND", str(k + 1): instance_paths[k]}}};
         without instance_paths, the ids in the frame are named "label_<id>"."""
         ids = self.get_instance_ids()
+        return {"data": (ids + 1).astype(np.uint32), "info": {"idToLabels": self._id_to_labels(np.unique(ids[ids >= 0]))}}
+
+    def _id_to_labels(self, present) -> dict:
+        """idToLabels of a frame that shows the labels `present` (ascending)."""
         if self._instance_paths is not None:
-            if ids.max(initial=-1) >= len(self._instance_paths):
-                raise ValueError(f"the mesh has a label {int(ids.max())}, instance_paths names {len(self._instance_paths)}")
+            if len(present) and int(present[-1]) >= len(self._instance_paths):
+                raise ValueError(f"the mesh has a label {int(present[-1])}, instance_paths names {len(self._instance_paths)}")
             names = {str(k + 1): p for k, p in enumerate(self._instance_paths)}
         else:
-            names = {str(int(k) + 1): f"label_{int(k)}" for k in np.unique(ids[ids >= 0])}
-        return {"data": (ids + 1).astype(np.uint32), "info": {"idToLabels": {"0": "BACKGROUND", **names}}}
+            names = {str(int(k) + 1): f"label_{int(k)}" for k in present}
+        return {"0": "BACKGROUND", **names}
+
+    def _visible_rows(self, min_pixels=1):
+        """The visible-object rows (Renderer.visible_objects) of ONE render_mesh_ids(return_depth=True) at the render resolution."""
+        if self._mesh is None:
+            raise RuntimeError("instance ids come from the collision mesh: construct the camera with collision_mesh=")
+        ids, depth = self._r.render_mesh_ids(self._camera(), self._mesh, config=self._mesh_config, return_depth=True)
+        n = len(self._instance_paths) if self._instance_paths is not None else max(int(ids.max().item()) + 1, 1)
+        return self._r.visible_objects(ids, depth, n_labels=n, min_pixels=min_pixels)[0]
+
+    def get_visible_objects(self, min_pixels: int = 1) -> list:
+        """Which objects of the collision mesh the view shows, reduced on the GPU from the ids and the depth of one render (only the
+        table's rows cross the link): a list, by ascending label, of {"label", "path" (instance_paths[label], or None without
+        instance_paths), "pixels", "bbox" (x_min, y_min, x_max, y_max — inclusive), "centre" (mean x, mean y of the object's pixels,
+        float64), "nearest_m" (the least distance to the image plane among them)} for every label that covers at least min_pixels
+        pixels.  Ids are never resized: the figures are in pixels of the render resolution, whatever output_size is.  Needs
+        collision_mesh=.  This project's own observation (the reference reads none like it); a label instance_paths does not name
+        raises ValueError."""
+        out = []
+        for r in self._visible_rows(min_pixels):
+            k, n = int(r["label"]), int(r["n_pixels"])
+            out.append({"label": k, "path": self._instance_paths[k] if self._instance_paths is not None else None, "pixels": n,
+                        "bbox": (int(r["x_min"]), int(r["y_min"]), int(r["x_end"]) - 1, int(r["y_end"]) - 1),
+                        "centre": (int(r["sum_x"]) / n, int(r["sum_y"]) / n), "nearest_m": float(r["z_min"])})
+        return out
+
+    def add_bounding_box_2d_tight_to_frame(self):
+        """get_current_frame() also returns "bounding_box_2d_tight" from now on (needs collision_mesh=): {"data": a structured array
+        with semanticId <u4 (= label + 1, the value instance_id_segmentation shows), x_min, y_min, x_max, y_max <i4 (inclusive) and
+        occlusionRatio <f4 (always NaN: it is not computed), one record per visible label, "info": {"idToLabels": as
+        instance_id_segmentation's}}.  It follows Isaac Sim's annotator of that name only as far as this shape: nothing of the
+        reference depends on it, and the boxes are this project's own definition (tight around the pixels whose nearest collision-mesh
+        hit has the label)."""
+        if self._mesh is None:
+            raise RuntimeError("instance ids come from the collision mesh: construct the camera with collision_mesh=")
+        self._boxes_in_frame = True
+
+    BOX_DTYPE = np.dtype([("semanticId", "<u4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_max", "<i4"), ("y_max", "<i4"), ("occlusionRatio", "<f4")])
+
+    def _bounding_boxes(self) -> dict:
+        rows = self._visible_rows(1)
+        data = np.zeros(len(rows), self.BOX_DTYPE)
+        data["semanticId"] = rows["label"].astype(np.uint32) + 1
+        data["x_min"], data["y_min"], data["x_max"], data["y_max"] = rows["x_min"], rows["y_min"], rows["x_end"] - 1, rows["y_end"] - 1
+        data["occlusionRatio"] = np.nan
+        return {"data": data, "info": {"idToLabels": self._id_to_labels(rows["label"])}}
 
     def get_instance_id_png(self) -> bytes:
         """The instance ids as a 16-bit grey PNG of id + 1 (0: nothing hit), encoded on the GPU by Renderer.encode_png's depth16 format

@@ -902,6 +902,64 @@ class Renderer:
             ret += ([s.as_dict() for s in st],)
         return ret if len(ret) > 1 else ret[0]
 
+    # -- the visible-object table of id frames (include/sage_gs.h sgs_object_table: this project's own definition, as the ids are) ----
+    def _id_frames_of(self, ids: torch.Tensor, depth: Optional[torch.Tensor]):
+        if ids.dim() == 2:
+            ids = ids.unsqueeze(0)
+            depth = depth.unsqueeze(0) if depth is not None and depth.dim() == 2 else depth
+        if (ids.device != self.device or ids.dtype != torch.int32 or ids.dim() != 3 or ids.shape[0] < 1 or ids.shape[1] < 1 or ids.shape[2] < 1
+                or not ids[0].is_contiguous()):
+            raise ValueError("ids must be int32 [H,W] or [B,H,W] on the renderer's device with contiguous frames")
+        if depth is not None and (depth.device != self.device or depth.dtype != torch.float32 or tuple(depth.shape) != tuple(ids.shape)
+                                  or depth.stride() != ids.stride()):
+            raise ValueError("depth must be float32 of the ids' shape and strides on the renderer's device")
+        return ids, depth
+
+    def object_table(self, ids: torch.Tensor, depth: Optional[torch.Tensor] = None, *, n_labels: int, out=None):
+        """The visible-object table of int32 id frames [H,W] or [B,H,W] on the device (render_mesh_ids*'s, or any other), reduced there
+        in one launch for the whole batch: (rows, counts).  rows is int32 [B, n_labels, 10] whose bytes are sgs_object_row
+        (_capi.OBJECT_ROW_DTYPE): row k of a frame describes label k — pixels, tight box (x_min, y_min, x_end, y_end: ends exclusive),
+        the least depth of `depth` (float32, the ids' shape; +inf without it) and the sums of x and y; counts is int32 [B, 2]: the
+        pixels equal to -1 (nothing hit) and the pixels whose id is neither -1 nor a label below n_labels, which enter no row.
+        out=(rows, counts): contiguous tensors of those shapes to write into.  Nothing is copied to the host; asynchronous on the
+        current stream.  A frame's table does not depend on the batch it is in.  This project's own definition: the reference has no
+        such observation."""
+        ids, depth = self._id_frames_of(ids, depth)
+        b, h, w = int(ids.shape[0]), int(ids.shape[1]), int(ids.shape[2])
+        n_labels = int(n_labels)
+        if n_labels < 1:
+            raise ValueError("n_labels must be at least 1")
+        if out is None:
+            rows = torch.empty((b, n_labels, _capi.OBJECT_ROW_WORDS), dtype=torch.int32, device=self.device)
+            counts = torch.empty((b, 2), dtype=torch.int32, device=self.device)
+        else:
+            rows, counts = out
+            rows = self._ids_out(rows, (b, n_labels, _capi.OBJECT_ROW_WORDS), torch.int32, "out[0]")
+            counts = self._ids_out(counts, (b, 2), torch.int32, "out[1]")
+        self._lib.check(self._lib.sgs_object_table(self._ctx, ids.data_ptr(), depth.data_ptr() if depth is not None else None, b, h, w,
+                                                   int(ids.stride(0)) if b > 1 else h * w, n_labels, rows.data_ptr(), counts.data_ptr(),
+                                                   self._stream()), self._ctx)
+        return rows, counts
+
+    def visible_objects(self, ids: torch.Tensor, depth: Optional[torch.Tensor] = None, *, n_labels: int, min_pixels: int = 1) -> list:
+        """Per frame a NumPy structured array (_capi.VISIBLE_OBJECT_DTYPE: `label` and sgs_object_row's fields) of the labels that cover
+        at least min_pixels pixels, by ascending label: object_table on the device, the rows selected there, and only those copied to
+        the host.  ValueError (naming the frame and the count) when a frame holds ids that are neither -1 nor below n_labels."""
+        rows, counts = self.object_table(ids, depth, n_labels=n_labels)
+        where = torch.nonzero(rows[:, :, 0] >= max(int(min_pixels), 1))           # [K, 2]: (frame, label), in that order
+        picked = rows[where[:, 0], where[:, 1]]
+        counts_h, where_h, picked_h = counts.cpu().numpy(), where.cpu().numpy(), picked.cpu().numpy()
+        bad = np.flatnonzero(counts_h[:, 1])
+        if len(bad):
+            raise ValueError(f"frame {int(bad[0])}: {int(counts_h[bad[0], 1].view(np.uint32))} pixels hold ids that are neither -1 nor below n_labels = {int(n_labels)}")
+        out = np.zeros(len(where_h), _capi.VISIBLE_OBJECT_DTYPE)
+        out["label"] = where_h[:, 1]
+        rec = np.ascontiguousarray(picked_h).view(_capi.OBJECT_ROW_DTYPE).reshape(-1)
+        for name in _capi.OBJECT_ROW_DTYPE.names:
+            out[name] = rec[name]
+        cuts = np.searchsorted(where_h[:, 0], np.arange(rows.shape[0] + 1))
+        return [out[cuts[f]:cuts[f + 1]] for f in range(rows.shape[0])]
+
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
         self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)

@@ -96,7 +96,8 @@ def cameras_for(points, resolution=CAMERA_RESOLUTION):
 
 
 def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESOLUTION, force=False, quality=95,
-        chunk=64, on_frame=None, write=True, encode_workers=8, encoder="pil"):
+        chunk=64, on_frame=None, write=True, encode_workers=8, encoder="pil", collision_mesh=None, instance_paths=None,
+        min_object_pixels=64):
     """Renders every trajectory (one GPU batch per `chunk` poses) and writes the reference's output layout.
     on_frame(trajectory_id, index, rgb uint8 [H,W,3]) — optional — sees each frame as it is handed to the JPEG encoder
     (the array `cam.get_rgba()[:, :, :3]` would be in generate_images.py:428-432).  The array is a VIEW of a pinned ring buffer that
@@ -111,7 +112,13 @@ def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESO
     waypoints held gigabytes per process.  The pool is shut down on every exit path.
     encoder="gpu": the files are made on the GPU from the fp32 frames (Renderer.jpeg_frames: same tables, same 4:2:0 as PIL's save at
     this quality); only their bytes cross the link and the worker threads just write them.  The uint8 RGBA copy is then made only when
-    on_frame is given."""
+    on_frame is given.
+    collision_mesh (a Mesh, Renderer.upload_mesh with labels=) with instance_paths (the labels' names, or None): every sequence of
+    image_metadata.json gains "visible_objects", one list per frame of {"label", "path", "pixels", "bbox" (x_min, y_min, x_max, y_max,
+    inclusive), "nearest_m"} for the objects that cover at least min_object_pixels pixels — Renderer.render_mesh_ids_batch(return_depth=
+    True) and Renderer.visible_objects per chunk, so only the selected rows reach the host.  The pass covers every frame the metadata
+    lists, those whose JPEG exists already (and is skipped) included.  This project's own annotation: the reference's file has no such
+    key, and without a mesh the file is byte for byte what it was."""
     from concurrent.futures import ThreadPoolExecutor
     if encoder not in ("pil", "gpu"):
         raise ValueError("encoder must be 'pil' or 'gpu'")
@@ -198,12 +205,32 @@ def run(renderer, scene, trajectories, scene_id, out_dir, resolution=CAMERA_RESO
     finally:
         if pool is not None:
             pool.shutdown(wait=True, cancel_futures=True)
+    if collision_mesh is not None:
+        visible_objects_pass(renderer, collision_mesh, instance_paths, trajectories, sequences, resolution, chunk, min_object_pixels)
     meta = {"scene_id": scene_id, "scene_name": scene_id, "total_image_sequences": len(sequences),
             "frames_per_sequence": "variable_based_on_action_sampling", "image_resolution": list(resolution),
             "camera_settings": {"focal_length": CAMERA_FOCAL_LENGTH, "height": CAMERA_HEIGHT},
             "sequences": sequences, "processing_mode": {"type": "gpu_batch", "scene_reuse": True, "single_camera": True}}
     json.dump(meta, open(os.path.join(out_dir, "image_metadata.json"), "w", encoding="utf-8"), ensure_ascii=False, indent=2)
     return total
+
+
+def visible_objects_pass(renderer, mesh, instance_paths, trajectories, sequences, resolution, chunk, min_pixels):
+    """sequences[i]["visible_objects"] for every trajectory: the poses of all of them as one work list cut into chunks."""
+    from .adapter import MESH_CONFIG
+    cams, owner = [], []
+    for t, tr in enumerate(trajectories):
+        sequences[t]["visible_objects"] = []
+        for cam in cameras_for(tr["points"], resolution):
+            cams.append(cam); owner.append(t)
+    for c0 in range(0, len(cams), chunk):
+        ids, depth = renderer.render_mesh_ids_batch(cams[c0:c0 + chunk], mesh, config=MESH_CONFIG, return_depth=True)
+        n = len(instance_paths) if instance_paths is not None else max(int(ids.max().item()) + 1, 1)
+        for k, rows in enumerate(renderer.visible_objects(ids, depth, n_labels=n, min_pixels=min_pixels)):
+            sequences[owner[c0 + k]]["visible_objects"].append(
+                [{"label": int(r["label"]), "path": instance_paths[int(r["label"])] if instance_paths is not None else None,
+                  "pixels": int(r["n_pixels"]), "bbox": [int(r["x_min"]), int(r["y_min"]), int(r["x_end"]) - 1, int(r["y_end"]) - 1],
+                  "nearest_m": float(r["z_min"])} for r in rows])
 
 
 def torch_pad(frames, chunk):
@@ -231,6 +258,9 @@ def main(argv=None):
     ap.add_argument("--force", action="store_true")
     ap.add_argument("--encoder", choices=("pil", "gpu"), default="pil",
                     help="who makes the .jpg files: PIL threads on the host (default), or the GPU (sgs_encode_jpeg)")
+    ap.add_argument("--collision", metavar="PATH.usda", help="the scene's collision layer (ASCII USD): image_metadata.json then lists, per frame, "
+                    "the objects in view (this project's own annotation; one scene only)")
+    ap.add_argument("--min-object-pixels", type=int, default=64, help="with --collision: list the objects that cover at least N pixels")
     ap.add_argument("--quality", type=int, default=95, help="JPEG quality, 1..100 (generate_images.py writes PIL's default subsampling)")
     a = ap.parse_args(argv)
     if not 0 <= a.instance_id < a.total_instances:
@@ -240,6 +270,8 @@ def main(argv=None):
         ap.error("give either --scene/--actions/--scene-id (one scene) or --action-root/--scene-root (many)")
     if not 1 <= a.quality <= 100:
         ap.error("--quality must be in 1..100")
+    if a.collision and many:
+        ap.error("--collision names one scene's layer: give it with --scene/--actions/--scene-id")
     from . import ply, scenes
     from .renderer import Renderer
     import torch
@@ -259,7 +291,15 @@ def main(argv=None):
     for sid, path, comp, actions, out_dir in jobs:
         arrays = (ply.load_compressed_ply if comp else ply.load_ply)(path)
         scene = r.upload(ply.to_gaussians(arrays, dev, scenes.MODEL_TO_WORLD))      # template.usda:120
-        n = run(r, scene, load_trajectories(actions), sid, out_dir, (a.width, a.height), a.force, quality=a.quality, encoder=a.encoder)
+        cmesh = paths = None
+        if a.collision:
+            from . import mesh as mesh_io
+            verts, tris, tri_prim, paths = mesh_io.read_usda_mesh(a.collision, return_prims=True)
+            cmesh = r.upload_mesh(verts, tris, labels=tri_prim)
+        n = run(r, scene, load_trajectories(actions), sid, out_dir, (a.width, a.height), a.force, quality=a.quality, encoder=a.encoder,
+                collision_mesh=cmesh, instance_paths=paths, min_object_pixels=a.min_object_pixels)
+        if cmesh is not None:
+            cmesh.free()
         scene.free()
         total += n
         print(f"[sage_gs.sweep] instance {a.instance_id + 1}/{a.total_instances}: scene {sid}: {n} frames -> {out_dir}")
