@@ -547,7 +547,8 @@ typedef struct sgs_object_row {      /* 40 bytes, 8-byte aligned; row k of a fra
  * they must not be host memory.  Stream-ordered and asynchronous, as the encoders are: the call never synchronises, owns no scratch and
  * leaves none behind.  Two launches: a clear of the table and one reduction over frames x regions of a frame.
  * SGS_ERR_INVALID, before anything is enqueued or written: null ids, out_rows or out_counts; n_frames < 1; height < 1 or width < 1;
- * height * width > 2^31 - 1; frame_stride < height * width; n_labels < 1. */
+ * height * width > 2^31 - 1; frame_stride < height * width; n_labels < 1; out_rows not 8-byte aligned (sum_x and sum_y are updated
+ * with 64-bit atomics); ids, depth (when given) or out_counts not 4-byte aligned.  The message names the argument. */
 int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n_frames, int height, int width, int64_t frame_stride,
                      int32_t n_labels, sgs_object_row* out_rows, uint32_t* out_counts, void* hip_stream);
 

@@ -2149,6 +2149,11 @@ int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n
     if (frame_stride < pixels)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (stride %lld elements, a frame has %lld)", who, (long long)frame_stride, (long long)pixels);
     if (n_labels < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_labels = %d", who, (int)n_labels);
+    // the kernels' atomics are 64-bit on sum_x / sum_y and 32-bit elsewhere; a misaligned one must never reach the device
+    if (reinterpret_cast<uintptr_t>(out_rows) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_rows %p is not 8-byte aligned", who, (const void*)out_rows);
+    if (reinterpret_cast<uintptr_t>(ids) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: ids %p is not 4-byte aligned", who, (const void*)ids);
+    if (reinterpret_cast<uintptr_t>(depth) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: depth %p is not 4-byte aligned", who, (const void*)depth);
+    if (reinterpret_cast<uintptr_t>(out_counts) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_counts %p is not 4-byte aligned", who, (const void*)out_counts);
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     sgs::ObjJob J;
@@ -2158,12 +2163,11 @@ int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n
     const int64_t clear_blocks = std::min<int64_t>((std::max<int64_t>(n_rows, 2ll * n_frames) + SGS_OBJ_THREADS - 1) / SGS_OBJ_THREADS, 65536);
     hipLaunchKernelGGL(sgs::k_obj_clear, dim3((unsigned)clear_blocks), dim3(SGS_OBJ_THREADS), 0, st, J);
     const unsigned regions = (unsigned)((pixels + SGS_OBJ_REGION - 1) / SGS_OBJ_REGION);
-    const int kMaxFrames = 65535;              // gridDim.y
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFrames) {
+    for (int f0 = 0; f0 < n_frames; f0 += SGS_OBJ_MAX_FRAMES) {
         sgs::ObjJob K = J;
         K.ids = ids + (int64_t)f0 * frame_stride; K.depth = depth ? depth + (int64_t)f0 * frame_stride : nullptr;
         K.rows = J.rows + (int64_t)f0 * n_labels; K.counts = out_counts + 2ll * f0;
-        K.n_frames = std::min(kMaxFrames, n_frames - f0);
+        K.n_frames = std::min(SGS_OBJ_MAX_FRAMES, n_frames - f0);
         hipLaunchKernelGGL(sgs::k_obj_reduce, dim3(regions, (unsigned)K.n_frames), dim3(SGS_OBJ_THREADS), 0, st, K);
     }
     SGS_HIP(ctx, hipGetLastError());

@@ -41,6 +41,7 @@
 #define SGS_OBJ_HASH 0x9E3779B1u                                   // slot = (label * SGS_OBJ_HASH) >> (32 - SGS_OBJ_SLOT_BITS)
 #define SGS_OBJ_Z_INF 0x7F800000u                                  // +inf: an empty row's z_min, and the largest pattern that enters
 #define SGS_OBJ_ID_NONE (-1)                                       // SGS_ID_NONE
+#define SGS_OBJ_MAX_FRAMES 65535                                   // frames per k_obj_reduce launch (gridDim.y); more are issued in chunks
 
 namespace sgs {
 

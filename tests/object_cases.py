@@ -23,11 +23,37 @@ def slot_of(label):
 
 
 def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_objects.h is newer than it (emu_harness's staleness list predates the header)."""
+    """The emulator library (emu_harness rebuilds it when a file of csrc/ is newer than it)."""
     import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_objects.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
+    return emu_harness.build_emu()
+
+
+def start_emu_copy(base, edits, name="libsage_gs_objects_copy.so"):
+    """A copy of csrc/ under `base` with edits = {file of csrc/: [(anchor, replacement)]} made in it (every anchor must occur exactly
+    once), and its emulator build started: (the library's path, the compiler's Popen).  The caller waits."""
+    import shutil
+    import emu_harness
+    base = str(base)
+    csrc = os.path.join(base, "pkg", "csrc")
+    shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), csrc)
+    os.makedirs(os.path.join(base, "include"))
+    shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), os.path.join(base, "include", "sage_gs.h"))     # (../../include/sage_gs.h)
+    for fname, pairs in edits.items():
+        path = os.path.join(csrc, fname)
+        with open(path) as fh:
+            text = fh.read()
+        for old, new in pairs:
+            assert text.count(old) == 1, f"{fname}: anchor found {text.count(old)} times: {old!r}"
+            text = text.replace(old, new)
+        with open(path, "w") as fh:
+            fh.write(text)
+    out = os.path.join(base, name)
+    return out, emu_harness.build_emu(src_dir=csrc, out=out, wait=False)
+
+
+def chunk_edit(chunk):
+    """The edit that makes sgs_object_table cut its frames into launches of `chunk` (SGS_OBJ_MAX_FRAMES, csrc/sgs_objects.h)."""
+    return ("#define SGS_OBJ_MAX_FRAMES 65535 ", f"#define SGS_OBJ_MAX_FRAMES {int(chunk)} ")
 
 
 # ---- pictures: name -> [(ids int32 [H,W], depth fp32 [H,W] or None, n_labels)] ------------------------------------------------------------
@@ -110,8 +136,72 @@ def depth_specials():
     return [(ids, d, 3), (ids, None, 3)]
 
 
+def _collider_labels():
+    """(a, b, c): a < b in one slot (the search of colliding()), c in another."""
+    same = [k for k in range(1, 20000) if slot_of(k) == slot_of(1)]
+    a, b = same[0], same[1]
+    c = next(k for k in range(2, 20000) if slot_of(k) != slot_of(a))
+    assert a < b and slot_of(a) == slot_of(b) != slot_of(c)
+    return a, b, c
+
+
+MIXED_W, MIXED_H, MIXED_ROWS = 64, 96, REGION // 64          # three regions of 32 image rows each
+
+
+def mixed_paths():
+    """64 x 96, three regions of 32 rows; a < b share a slot, c has another.  Label a changes path from region to region, so its row
+    receives the slot's flush of one workgroup and the no-slot sends of two others:
+      region 0   a (columns 10..49 of rows 3..28) in c: a owns its slot
+      region 1   a and b interleaved in runs of 1 to 5 pixels: b owns the slot, every run of a goes straight to the global row
+      region 2   b in the left half, a in the right half but for the last column (c): a has no slot here either
+    a touches column 0 and column 63 in region 1 alone and its least depth (0.5, at three pixels) lies there, so x_min, x_end and
+    z_min are attained only in region 1; y_min comes from region 0 alone.  y_end is that of a's last image row, which is in region
+    2 whatever the placement: no slot there either, so y_end too comes from the no-slot path alone.  Variant [1] moves the least depth
+    to region 0 (the slot path)."""
+    a, b, c = _collider_labels()
+    W, H, R = MIXED_W, MIXED_H, MIXED_ROWS
+    ids = np.full((H, W), c, np.int32)
+    ids[3:29, 10:50] = a
+    rs = np.random.RandomState(12)
+    runs = rs.randint(1, 6, REGION)                                               # more runs than the region can hold
+    ids[R:2 * R] = np.repeat(np.resize(np.array([a, b], np.int32), REGION), runs)[:REGION].reshape(R, W)
+    ids[2 * R:, :W // 2] = b
+    ids[2 * R:, W // 2:W - 1] = a
+    out = []
+    for region in (1, 0):
+        d = _depth(H, W, 30 + region)                                             # 1.0 .. 8.625
+        ys, xs = np.nonzero(ids[region * R:(region + 1) * R] == a)
+        pick = rs.choice(len(ys), 3, replace=False)
+        d[ys[pick] + region * R, xs[pick]] = 0.5
+        out.append((ids, d, max(a, b, c) + 1))
+    return out
+
+
+NARROW_SIZES = ((1, 2500), (2, 1500), (3, 1000), (5, 700))
+
+
+def narrow():
+    """Frames 1, 2, 3 and 5 pixels wide that cross a region (2500, 3000, 3000 and 3500 pixels): dozens of image rows per wave, a head
+    with x == 0 at every few lanes (W = 1: at every lane), x wrapping at every k.  Per size one frame in vertical bands (label = x:
+    the label that ends row y differs from the one that starts row y + 1 unless W = 1, where the one label continues across every row
+    start) and one in horizontal bands of 1 to 9 rows (the label continues across the row starts inside a band and changes at a
+    band's first row); 4 % SGS_ID_NONE sprinkled in, a depth with each."""
+    out = []
+    for k, (W, H) in enumerate(NARROW_SIZES):
+        assert W * H > REGION and (W * H) % REGION != 0
+        rs = np.random.RandomState(40 + k)
+        yy, xx = np.mgrid[0:H, 0:W]
+        band_of_row = np.repeat(np.arange(H), rs.randint(1, 10, H))[:H] % 6
+        for ids in (xx.astype(np.int32), np.repeat(band_of_row[:, None], W, 1).astype(np.int32)):
+            ids = ids.copy()
+            ids[rs.rand(H, W) < 0.04] = NONE
+            out.append((ids, _depth(H, W, 50 + len(out)), 6))
+    return out
+
+
 SMALL = (one_pixel, one_label_ragged, bands_and_stripes, checker_with_holes, colliding, edge_labels, depth_specials)
 LARGE = (sum_over_2_32, own_label)             # the emulator's largest: one run each there
+PATHS = (mixed_paths, narrow)                  # a label that changes path between regions; very narrow frames across regions
 
 
 def check_picture_properties():
@@ -127,6 +217,37 @@ def check_picture_properties():
     for ids, d, n in edge_labels():
         rows, counts = ref.table(ids, d, n)
         assert counts[1] == 4 * ids.shape[0] and rows["n_pixels"][0] > 0 and rows["n_pixels"][n - 1] > 0
+    check_mixed_paths_properties()
+    pictures = narrow()
+    for k, (W, H) in enumerate(NARROW_SIZES):
+        frames = pictures[2 * k:2 * k + 2]                                         # vertical bands, horizontal bands
+        for ids, d, n in frames:
+            rows, counts = ref.table(ids, d, n)
+            assert ids.shape == (H, W) and d is not None and counts[0] > 0 and counts[1] == 0 and (rows["n_pixels"][:min(W, n)] > 0).all()
+        across = [(f[0][1:, 0] == f[0][:-1, -1]) & (f[0][1:, 0] != NONE) for f in frames]       # row y's last label starts row y + 1
+        assert across[1].any() and not across[1].all() and (across[0].any() if W == 1 else not across[0].any())
+
+
+def check_mixed_paths_properties():
+    """The condition under which mixed_paths can catch a fault of one path alone, from the restatement of each region by itself."""
+    a, b, c = _collider_labels()
+    R = MIXED_ROWS
+    for variant, (ids, d, n) in enumerate(mixed_paths()):
+        assert ids.shape == (MIXED_H, MIXED_W) and MIXED_W * R == REGION and MIXED_H == 3 * R
+        part = [ref.table(ids[k * R:(k + 1) * R], d[k * R:(k + 1) * R], n)[0] for k in range(3)]     # y counts from the region's first row
+        whole = ref.table(ids, d, n)[0]
+        labels = [set(np.flatnonzero(p["n_pixels"]).tolist()) for p in part]
+        assert labels == [{a, c}, {a, b}, {a, b, c}]             # a owns its slot in region 0 alone: b, the larger, takes it in 1 and 2
+        runs = np.diff(np.flatnonzero(np.diff(ids[R:2 * R].reshape(-1)) != 0))
+        assert runs.min() == 1 and runs.max() == 5
+        pa, wa = [p[a] for p in part], whole[a]
+        assert wa["x_min"] == pa[1]["x_min"] == 0 < min(pa[0]["x_min"], pa[2]["x_min"])
+        assert wa["x_end"] == pa[1]["x_end"] == MIXED_W > max(pa[0]["x_end"], pa[2]["x_end"])
+        assert wa["y_min"] == pa[0]["y_min"] and wa["y_end"] == 2 * R + pa[2]["y_end"] == MIXED_H    # the first row from the slot, the last without one
+        z = [int(ref.z_bits(p)[a]) for p in part]
+        low = 1 if variant == 0 else 0
+        assert int(ref.z_bits(whole)[a]) == z[low] and all(z[low] < z[k] for k in range(3) if k != low)
+        assert (d[ids == a] == d[ids == a].min()).sum() == 3
 
 
 # ---- the C ABI over plain buffers ---------------------------------------------------------------------------------------------------------
@@ -271,3 +392,50 @@ def check_refusals(drv):
     assert call() == 0 and call(n=1, H=46340, W=1, stride=46340 * 4, ids=None) == -1          # the context still works
     drv._sync()
     assert (np.array(r_get())[:2 * 3 * 40].view(ref.ROW_DTYPE)["n_pixels"] == [64, 0, 0, 64, 0, 0]).all()
+
+
+def check_misaligned(drv):
+    """out_rows 4 bytes off its 8-byte alignment, ids, depth and out_counts 1 and 2 bytes off their 4: each is refused with
+    SGS_ERR_INVALID and a message that names the argument, before anything is enqueued — the poisoned outputs stay untouched."""
+    pad = 16                                                                        # room behind every buffer for the offsets tried
+    keep_i, i_ptr = drv._ints(np.zeros(2 * 64 + pad, np.int32))
+    keep_d, d_ptr = drv._frames(np.ones(2 * 64 + pad, np.float32))
+    keep_r, r_ptr, r_get = drv._bytes(2 * 3 * 40 + 4 * pad)
+    keep_c, c_ptr, c_get = drv._bytes(2 * 8 + 4 * pad)
+    assert i_ptr % 8 == 0 and d_ptr % 8 == 0 and r_ptr % 8 == 0 and c_ptr % 8 == 0
+
+    def call(ids=0, depth=0, rows=0, counts=0):
+        return drv.call(i_ptr + ids, d_ptr + depth, 2, 8, 8, 64, 3, r_ptr + rows, c_ptr + counts)
+
+    bad = [(b"out_rows", dict(rows=4))] + [(word, {arg: off}) for word, arg in ((b"ids", "ids"), (b"depth", "depth"), (b"out_counts", "counts"))
+                                           for off in (1, 2)]
+    for word, kw in bad:
+        assert call(**kw) == -1, f"{word.decode()} off by {kw} bytes was accepted"
+        msg = drv.lib.sgs_last_error(drv.ctx)
+        assert word in msg and b"aligned" in msg, (word, msg)
+    drv._sync()
+    assert (np.array(r_get()) == jpeg_cases.SENTINEL).all() and (np.array(c_get()) == jpeg_cases.SENTINEL).all(), "a refused call wrote to its outputs"
+    assert call() == 0 and call(rows=8, counts=4, ids=4, depth=4) == 0               # aligned, and aligned again: the context still works
+    drv._sync()
+    assert (np.array(r_get())[8:8 + 2 * 3 * 40].view(ref.ROW_DTYPE)["n_pixels"] == [64, 0, 0, 64, 0, 0]).all()
+
+
+def check_split(drv, chunk, n_frames=None):
+    """2 * chunk + 3 frames of 1 x 1 in one call (chunk: SGS_OBJ_MAX_FRAMES of the library driven): two full launches and a short one,
+    each with ids, depth, rows and counts re-based.  n_labels = 2, ids 0, 1, SGS_ID_NONE, 7 in turn, depth 1 + (f % 13) / 8,
+    frame_stride 3: every frame's two rows and its counters are the restatement's, and (tables) nothing is written behind either output."""
+    n = 2 * chunk + 3 if n_frames is None else int(n_frames)
+    assert n > chunk
+    f = np.arange(n)
+    ids = np.array([0, 1, NONE, 7], np.int32)[f % 4].reshape(n, 1, 1)
+    depth = (1 + (f % 13) / 8).astype(np.float32).reshape(n, 1, 1)
+    rows, counts = drv.tables(ids, depth, 2, stride=3)
+    period = [ref.table(ids[k], depth[k], 2) for k in range(min(n, 52))]             # (id, depth) repeats every lcm(4, 13) frames
+    want = np.stack([p[0] for p in period])[f % 52]
+    want_counts = np.stack([p[1] for p in period])[f % 52]
+    same = (rows.view(np.uint32).reshape(n, 20) == want.view(np.uint32).reshape(n, 20)).all(1) & (counts == want_counts).all(1)
+    if not same.all():
+        k = int(np.argmin(same))
+        check_frame(f"split: frame {k} of {n} (launches of {chunk})", rows[k], counts[k], ids[k], depth[k], 2)
+        raise AssertionError(f"split: frame {k} of {n} differs from the restatement")
+    return n

@@ -1,11 +1,10 @@
 """Seeded faults in the visible-object table (csrc/sgs_objects.h), under the wave64 emulator: each is made in a copy of csrc/, compiled,
-and must be caught by object_cases.check_pictures — by the assertion named for it.
+and must be caught by object_cases.check_pictures — by the assertion named for it — or, for the faults of the host entry and of one
+path of the reduction (CHECK_MUTANTS), by the check named for it.
 
 z_min's filter is the unsigned comparison itself (patterns with the sign bit, and NaNs, lie above +inf's): the fault that admits
 negatives is therefore a run's minimum taken over the patterns read as SIGNED integers, where every negative number and -0 comes first."""
-import os
 import re
-import shutil
 
 import pytest
 
@@ -36,27 +35,44 @@ CAUGHT_BY = {
 }
 
 
+# Seeded faults that pictures of one frame cannot see, or that one picture is built for: name: ({file of csrc/: edits}, the checks run —
+# EACH of them must catch the fault by itself —, what the first failure of each says).  The launch split is exercised with
+# SGS_OBJ_MAX_FRAMES at 4, as test_emu_objects.py does.
+CHUNK = 4
+_SPLIT = lambda d: oc.check_split(d, CHUNK)                                                    # noqa: E731
+_MIXED, _COLLIDING = (lambda d: oc.check_pictures(d, (oc.mixed_paths,))), (lambda d: oc.check_pictures(d, (oc.colliding,)))   # noqa: E731
+_NO_REFUSAL = [(f"if (reinterpret_cast<uintptr_t>({arg}) % {n}) SGS_FAIL", f"if (false) SGS_FAIL")
+               for arg, n in (("out_rows", 8), ("ids", 4), ("depth", 4), ("out_counts", 4))]
+CHECK_MUTANTS = {
+    "chunk_rows_not_rebased": ({"sgs_api.hip": [("K.rows = J.rows + (int64_t)f0 * n_labels; ", "")], "sgs_objects.h": [oc.chunk_edit(CHUNK)]},
+                               [_SPLIT], [r"split: frame 0 of 11 \(launches of 4\): label 0: n_pixels is 3, the restatement has 1"]),
+    "chunk_counts_not_rebased": ({"sgs_api.hip": [("K.counts = out_counts + 2ll * f0;", "")], "sgs_objects.h": [oc.chunk_edit(CHUNK)]},
+                                 [_SPLIT], [r"split: frame 2 of 11 \(launches of 4\): counts are \[3, 0\], the restatement has \[1, 0\]"]),
+    "no_slot_path_drops_y_end": ({"sgs_objects.h": [("else obj_send(&rows[v], len, x, y, x + len, y + 1u, sx, sy);",
+                                                     "else obj_send(&rows[v], len, x, y, x + len, 0u, sx, sy);")]},
+                                 [_MIXED, _COLLIDING], [r"mixed_paths\[0\] 64x96: label 1: y_end is 29, the restatement has 96",
+                                                        r"colliding\[0\] 40x9: label 1: y_end is 0, the restatement has 9"]),
+    "no_slot_path_drops_its_depth": ({"sgs_objects.h": [("else obj_send_z(&rows[v], z);", "else {}")]},
+                                     [_MIXED, _COLLIDING], [r"mixed_paths\[0\] 64x96: label 1: z_min is 0x3f800000, the restatement has 0x3f000000",
+                                                            r"colliding\[0\] 40x9: label 1: z_min is 0x7f800000, the restatement has"]),
+    "slot_flush_drops_x_min": ({"sgs_objects.h": [("obj_send(r, s_n[s], s_x0[s], s_y0[s], s_x1[s], s_y1[s], s_sx[s], s_sy[s]);",
+                                                   "obj_send(r, s_n[s], 0x7FFFFFFFu, s_y0[s], s_x1[s], s_y1[s], s_sx[s], s_sy[s]);")]},
+                               [_MIXED, _COLLIDING], [r"mixed_paths\[0\] 64x96: label 2: x_min is 2147483647, the restatement has 0",
+                                                      r"colliding\[0\] 40x9: label \d+: x_min is 2147483647, the restatement has"]),
+    "alignment_refusal_removed": ({"sgs_api.hip": _NO_REFUSAL}, [oc.check_misaligned], [r"out_rows off by \{'rows': 4\} bytes was accepted"]),
+}
+
+
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
     root = tmp_path_factory.mktemp("object_mutants")
-    procs, libs = {}, {}
-    for k, (name, (edits, _)) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        path = base / "pkg" / "csrc" / "sgs_objects.h"
-        s = path.read_text()
-        for old, new in edits:
-            assert s.count(old) == 1, f"mutant anchor found {s.count(old)} times: {old!r}"
-            s = s.replace(old, new)
-        path.write_text(s)
-        libs[name] = str(base / "libsage_gs_objects_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
+    edits = {name: {"sgs_objects.h": e} for name, (e, _) in MUTANTS.items()}
+    edits.update({name: e for name, (e, _, _) in CHECK_MUTANTS.items()})
+    started = {name: oc.start_emu_copy(root / f"m{k}", e, "libsage_gs_objects_mutant.so") for k, (name, e) in enumerate(edits.items())}
+    for name, (_, p) in started.items():
         assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return {name: path for name, (path, _) in started.items()}
 
 
 @pytest.mark.parametrize("name", list(MUTANTS))
@@ -74,9 +90,31 @@ def test_object_mutant_is_caught(mutant_libs, name):
     assert re.search(CAUGHT_BY[name], str(caught)), f"{name}: failed on another assertion: {str(caught)[:300]}"
 
 
+@pytest.mark.parametrize("name", list(CHECK_MUTANTS))
+def test_object_check_mutant_is_caught(mutant_libs, name):
+    """The launch split: a chunk's rows or counts pointer left at the call's first frame is caught by check_split (the second launch
+    adds its frames to the first four's rows / counters).  The alignment refusal removed is caught by check_misaligned alone, and
+    only here: on a GPU the misaligned atomics must not run.
+    The path faults — the no-slot path dropping y_end or its depth, the slot's flush dropping x_min — are caught by mixed_paths, on
+    label a (no-slot: its y_end falls back to region 0's, its z_min to the slot path's least) or on c (flush).  The older `colliding`
+    picture catches each of them as well — four of its five labels have no slot anywhere and its fifth has nothing but the slot — so
+    both are run, each by itself; what only mixed_paths has is a row fed by both paths from different workgroups."""
+    _, checks, caught_by = CHECK_MUTANTS[name]
+    d = oc.AbiObjects(_capi.Lib(mutant_libs[name]))
+    try:
+        for check, pattern in zip(checks, caught_by):
+            with pytest.raises(AssertionError) as e:
+                check(d)
+            print(f"[object mutant] {name}: caught: {str(e.value)[:200]}")
+            assert re.search(pattern, str(e.value)), f"{name}: failed on another assertion: {str(e.value)[:300]}"
+    finally:
+        d.close()
+
+
 def test_the_unmutated_library_passes_the_mutants_checks():
     d = oc.AbiObjects(_capi.Lib(oc.emu_lib_path()))
     try:
-        oc.check_pictures(d, oc.SMALL)
+        oc.check_pictures(d, oc.SMALL + oc.PATHS)
+        oc.check_misaligned(d)
     finally:
         d.close()

@@ -1,5 +1,6 @@
 """The visible-object table on the MI355X (sgs_object_table): object_cases' pictures, rendered frames, batches and refusals through device
-pointers, a 16-frame 1024 x 768 batch against the restatement, and the layers above the C ABI — Renderer.object_table /
+pointers (misaligned ones among them), a call of 131073 frames that the entry splits into three launches, a table large enough for the
+clear's second trip, a caller's stream, a 16-frame 1024 x 768 batch against the restatement, and the layers above the C ABI — Renderer.object_table /
 visible_objects, GsCamera.get_visible_objects and its frame dictionary, sweep.run(collision_mesh=).  Every comparison is exact."""
 import json
 import os
@@ -35,7 +36,7 @@ def room(r):
     m.free()
 
 
-@pytest.mark.parametrize("make", oc.SMALL + oc.LARGE, ids=lambda m: m.__name__)
+@pytest.mark.parametrize("make", oc.SMALL + oc.PATHS + oc.LARGE, ids=lambda m: m.__name__)
 def test_pictures_on_the_gpu(drv, make):
     oc.check_pictures(drv, [make])
 
@@ -47,6 +48,59 @@ def test_rendered_room_frames_on_the_gpu(r, drv):
 def test_batches_strides_and_refusals_on_the_gpu(drv):
     oc.check_batches(drv)
     oc.check_refusals(drv)
+
+
+def test_misaligned_buffers_are_refused_on_the_gpu(drv):
+    """Refused by the host entry: the misaligned 64- and 32-bit atomics never reach the device."""
+    oc.check_misaligned(drv)
+
+
+def test_split_launch_of_131073_frames(drv):
+    """2 * 65535 + 3 one-pixel frames in one call, at the library's own SGS_OBJ_MAX_FRAMES: two launches of gridDim.y = 65535 and one of 3."""
+    assert oc.check_split(drv, 65535) == 131073
+
+
+def test_clear_makes_a_second_trip(r):
+    """One 1 x 1 frame with n_labels = 65536 * 256 + 5: k_obj_clear runs its most workgroups (65536 of 256 threads) and five threads
+    go round their loop a second time.  Every row but the last is the empty row, the last is the one pixel's; compared on the device."""
+    import torch
+    n_labels = 65536 * 256 + 5
+    row_bytes = n_labels * 40
+    free = torch.cuda.mem_get_info(r.device)[0]
+    if free < 2 * row_bytes:
+        pytest.skip(f"the table takes {row_bytes >> 20} MiB and the comparison as much again at most; the card has {free >> 20} MiB free")
+    ids = torch.tensor([[n_labels - 1]], dtype=torch.int32, device=r.device)
+    depth = torch.tensor([[2.5]], dtype=torch.float32, device=r.device)
+    rows, counts = r.object_table(ids, depth, n_labels=n_labels)
+    assert rows.shape == (1, n_labels, 10)
+    inf_bits, z_bits = 0x7F800000, int(np.float32(2.5).view(np.uint32))
+    empty = torch.tensor([0, oc.INT32_MAX, oc.INT32_MAX, 0, 0, inf_bits, 0, 0, 0, 0], dtype=torch.int32, device=r.device)
+    assert ref.empty_rows(1).tobytes() == empty.cpu().numpy().tobytes()
+    assert torch.equal(rows[0, :-1], empty.expand(n_labels - 1, 10)), "a row that no pixel shows is not the empty row"
+    assert rows[0, -1].tolist() == [1, 0, 0, 1, 1, z_bits, 0, 0, 0, 0]
+    assert counts.tolist() == [[0, 0]]
+    want, want_counts = ref.table(ids.cpu().numpy(), depth.cpu().numpy(), n_labels)
+    assert want[-1].tobytes() == rows[0, -1].cpu().numpy().tobytes() and want_counts.tolist() == [0, 0]
+    del rows
+    torch.cuda.empty_cache()
+
+
+def test_caller_supplied_stream(r, room):
+    """render_mesh_ids_batch and object_table issued on a non-default stream with nothing between them: the table of the default stream."""
+    import torch
+    cams = _cams(160, 120, 5)
+    ids0, depth0 = r.render_mesh_ids_batch(cams, room, return_depth=True)
+    rows0, counts0 = r.object_table(ids0, depth0, n_labels=12)
+    torch.cuda.synchronize(r.device)
+    side = torch.cuda.Stream(r.device)
+    assert side.cuda_stream != 0 and side.cuda_stream != torch.cuda.current_stream(r.device).cuda_stream
+    with torch.cuda.stream(side):
+        ids, depth = r.render_mesh_ids_batch(cams, room, return_depth=True)
+        rows, counts = r.object_table(ids, depth, n_labels=12)
+    side.synchronize()
+    assert torch.equal(ids, ids0) and torch.equal(depth.view(torch.int32), depth0.view(torch.int32))
+    assert torch.equal(rows, rows0) and torch.equal(counts, counts0)
+    assert int((rows0[:, :, 0] > 0).sum()) >= 15                                      # three labels or more in each of the five frames
 
 
 def _cams(w, h, n=16):
