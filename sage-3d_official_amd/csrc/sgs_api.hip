@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <utility>
@@ -25,18 +26,18 @@
 #include "sgs_png.h"
 #include "sgs_resize.h"
 #include "sgs_objects.h"
+#include "sgs_own.h"
 
 namespace {
 
 constexpr int kStatusRing = 256;
 thread_local std::string g_create_error;
 
-struct Scratch {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
 }  // namespace
+
+using sgs::DevBuf;
+using sgs::PinnedBuf;
+using sgs::Grow;
 
 // One Gaussian of a scene's PROBE (fine_shift_of): mean, 3-D covariance (+ its trace), ln(opacity), sampling weight — 512 of them, drawn at
 // upload (layout_scene) and kept on the host.  Half of the draws are uniform over the scene, half proportional to the Gaussian's squared size
@@ -51,10 +52,9 @@ struct sgs_scene {
     int sh_degree = 0, sh_rows = 0;     // sh_rows: 16-byte rows of SH per Gaussian (12 at degree 3; 4 when sh_packed)
     bool sh_packed = false;             // uploaded from the compressed payload: the 8-bit coefficients stay bytes in HBM (k_scene_layout<true>)
     int sh_decode = 0;                  // ... and are read as sage_gs.h SGS_SH_DECODE_* says
-    float4* geom = nullptr;
-    float4* shq = nullptr;
-    float4* cbound = nullptr;           // per chunk: bounding sphere of the means + largest scale (k_chunk_bounds)
-    unsigned* perm_host = nullptr;      // Z-order: layout position -> original index (nullptr = identity)
+    DevBuf<float4> geom, shq;
+    DevBuf<float4> cbound;              // per chunk: bounding sphere of the means + largest scale (k_chunk_bounds)
+    std::vector<unsigned> perm_host;    // Z-order: layout position -> original index (empty = identity)
 };
 
 // The intermediates of ONE frame in flight.  Lane 0 serves ordinary frames on the caller's stream; pipelined
@@ -62,37 +62,32 @@ struct sgs_scene {
 // few frames overlap: binning is latency- and imbalance-bound, the composite issue-bound, and together they
 // fill the chip better than back to back (measured +35 % frames/s with three lanes).
 struct Lane {
-    // per-Gaussian scratch
-    int64_t splat_cap = 0;
-    Splat* splats = nullptr;                 // one slot per Gaussian (slot == index)
-    unsigned long long* vismask = nullptr;   // per 64-Gaussian chunk: which slots are live this frame
-    unsigned long long* bigmask = nullptr;   //   ... and which of those went to the big-rect list
-    unsigned* big_list = nullptr;
-    uint4* binrec = nullptr;                 // per slot: depth bits, rect01, rect23 (dense copy for the binning kernels)
-    unsigned* live_list = nullptr;           // chunks that passed the per-chunk bounds this frame (k_chunk_cull)
-    // per-tile scratch
-    int tile_cap = 0;
-    unsigned *tile_count = nullptr, *tile_offset = nullptr;
-    uint4* tile_order = nullptr;                     // render order: (tile, first record, queue length) per position
-    unsigned long long* tile_prof = nullptr;         // profiling build: 8 words per tile
-    unsigned long long* bin_prof = nullptr;          // profiling build: 8 words per binning workgroup
+    // per-Gaussian scratch (ensure_splats)
+    DevBuf<Splat> splats;                        // one slot per Gaussian (slot == index)
+    DevBuf<unsigned long long> vismask;          // per 64-Gaussian chunk: which slots are live this frame
+    DevBuf<unsigned long long> bigmask;          //   ... and which of those went to the big-rect list
+    DevBuf<unsigned> big_list;
+    DevBuf<uint4> binrec;                        // per slot: depth bits, rect01, rect23 (dense copy for the binning kernels)
+    DevBuf<unsigned> live_list;                  // chunks that passed the per-chunk bounds this frame (k_chunk_cull)
+    // per-tile scratch (ensure_tiles)
+    DevBuf<unsigned> tile_count, tile_offset;
+    DevBuf<uint4> tile_order;                    // render order: (tile, first record, queue length) per position
+    DevBuf<unsigned long long> tile_prof;        // profiling build: 8 words per tile
+    DevBuf<unsigned long long> bin_prof;         // profiling build: 8 words per binning workgroup
     // binning scratch: per-workgroup (tile, base) lists
-    uint2* blk_list = nullptr;                       // per level-1 binning workgroup: (super-tile, base) of the super-tiles it touched
-    unsigned* blk_len = nullptr;
+    DevBuf<uint2> blk_list;                      // per level-1 binning workgroup: (super-tile, base) of the super-tiles it touched
+    DevBuf<unsigned> blk_len;
     // two-level binning: super-tile sub-counters / offsets (SGS_WT super-tiles at most), the level-2 job table and the jobs' bases
-    unsigned *stile_count = nullptr, *stile_offset = nullptr;
-    uint4* jobs = nullptr;
-    unsigned* job_base = nullptr;
-    int64_t job_cap = 0;
-    // per-record scratch
-    int64_t rec_cap = 0;
-    unsigned long long *rec = nullptr;                   // tile queues of (depth bits << 32 | slot) records
-    unsigned long long *alt = nullptr, *part = nullptr;  // scratch of the HBM radix path (oversized depth buckets only)
-    unsigned* sorted_out = nullptr;                      // SGS_FLAG_FULL_SORT (tests): fully ordered queues
-    int64_t sorted_cap = 0;
+    DevBuf<unsigned> stile_count, stile_offset;
+    DevBuf<uint4> jobs;
+    DevBuf<unsigned> job_base;
+    // per-record scratch (ensure_records): rec.cap is the lane's record capacity
+    DevBuf<unsigned long long> rec;              // tile queues of (depth bits << 32 | slot) records
+    DevBuf<unsigned long long> alt, part;        // scratch of the HBM radix path (oversized depth buckets only)
+    DevBuf<unsigned> sorted_out;                 // SGS_FLAG_FULL_SORT (tests): fully ordered queues
     // pipelined frames
-    hipStream_t stream = nullptr;            // internal, non-blocking
-    hipEvent_t fork = nullptr, done = nullptr;
+    sgs::Stream stream;                      // internal, non-blocking
+    sgs::Event fork, done;
     bool busy = false;                       // has pipelined work that no synchronisation has collected yet
 };
 
@@ -101,62 +96,53 @@ constexpr int64_t kMaxRecords = 0xfffffff0ll;   // record capacity: tile offsets
 
 // The collision-mesh depth path's own scratch (sgs_render_mesh_depth*): nothing of it is shared with the splat path's lanes.
 struct MeshScratch {
-    int64_t slot_cap = 0;                    // (triangle, frame) slots of the setup records
-    float4* rec = nullptr;
-    uint2* rect = nullptr;
-    unsigned* big = nullptr;
-    int64_t tile_cap = 0;                    // per-tile counters / offsets of a group
-    unsigned *counts = nullptr, *offs = nullptr;
-    int64_t list_cap = 0;                    // the record buffer: triangle ids of the per-tile lists
-    unsigned* list = nullptr;
+    DevBuf<float4> rec;                      // the setup records: four rows per (triangle, frame) slot
+    DevBuf<uint2> rect;                      //   ... and a rectangle and a big-list entry per slot
+    DevBuf<unsigned> big;
+    DevBuf<unsigned> counts, offs;           // per-tile counters / offsets of a group
+    DevBuf<unsigned> list;                   // the record buffer: triangle ids of the per-tile lists
     int64_t cap_wanted = 4ll << 20;          // sgs_mesh_set_record_capacity (4 Mi records, 16 MiB)
-    sgs::MeshStatus* d_st = nullptr;         // [SGS_MESH_MAX_GROUP] + the upload check's word
-    sgs::MeshStatus* h_st = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevBuf<sgs::MeshStatus> d_st;            // [SGS_MESH_MAX_GROUP] + the upload check's word (ensure_mesh_status)
+    PinnedBuf<sgs::MeshStatus> h_st;
+    sgs::Event ev[2];
 };
 
 // What every file encoder keeps for the placement of its files (csrc/sgs_encode.h): an offset per unit and the pinned status words.
 struct FileScratch {
-    long long* h_status = nullptr;           // pinned: [0] bytes needed, [1] capacity given, of the most recent call
-    int64_t offs_cap = 0;
-    long long* offs = nullptr;
+    PinnedBuf<long long> h_status;           // [0] bytes needed, [1] capacity given, of the most recent call
+    DevBuf<long long> offs;
 };
 
 // The JPEG encoder's scratch (sgs_encode_jpeg): per-interval lengths, the tables of the parameter sets seen so far (a table is never
 // rewritten: an encode still in flight on another stream keeps reading its own) and the files' placement.
 struct JpegScratch {
-    struct Entry { int width, height, quality, s420; sgs::JpegTables* dev; };
+    struct Entry { int width, height, quality, s420; DevBuf<sgs::JpegTables> dev; };
     std::vector<Entry> tables;
-    int64_t sizes_cap = 0;
-    unsigned* sizes = nullptr;
+    DevBuf<unsigned> sizes;
     FileScratch files;
 };
 
 // The PNG encoder's scratch (sgs_encode_png): a stored-size slot and a record per strip, an Adler-32 per frame, the files' placement.
 struct PngScratch {
-    int64_t rec_cap = 0;
-    sgs::PngStripRec* rec = nullptr;
-    int64_t slot_bytes = 0;
-    unsigned char* slots = nullptr;
-    int64_t frame_cap = 0;
-    unsigned* adler = nullptr;
+    DevBuf<sgs::PngStripRec> rec;
+    DevBuf<unsigned char> slots;
+    DevBuf<unsigned> adler;
     FileScratch files;
 };
 
 // The resize's scratch (sgs_resize): the horizontally resized frames of a call that runs both passes, and the tap tables of the axes
 // seen so far (a table is never rewritten: a resize still in flight keeps reading its own).
 struct ResizeScratch {
-    struct Entry { int in, out, filter, format, ksize; int* bounds; void* weights; };
+    struct Entry { int in, out, filter, format, ksize; DevBuf<int> bounds; DevBuf<unsigned char> weights; };
     std::vector<Entry> tables;
-    int64_t mid_cap = 0;
-    unsigned* mid = nullptr;
+    DevBuf<unsigned> mid;
 };
 
 struct sgs_mesh {
     int64_t n_verts = 0, n_tris = 0;
-    float* verts = nullptr;
-    int* tris = nullptr;
-    int* labels = nullptr;                   // sgs_mesh_set_labels: [n_tris], or nullptr: a triangle's label is its index
+    DevBuf<float> verts;
+    DevBuf<int> tris;
+    DevBuf<int> labels;                      // sgs_mesh_set_labels: [n_tris], or empty: a triangle's label is its index
 };
 
 struct sgs_ctx {
@@ -180,13 +166,13 @@ struct sgs_ctx {
     bool morton = true;                      // Z-order the scene at upload (sgs_tuning.morton = 0 keeps the caller's order): a chunk of 64
                                              // Gaussians is then a compact patch, which is what makes the per-chunk bounds
                                              // (k_chunk_bounds / chunk_outside) worth testing — trained scenes come in no spatial order
-    unsigned long long* row_acc = nullptr;   // records queued per frame tile row, summed over the frames since the last
+    DevBuf<unsigned long long> row_acc;      // records queued per frame tile row, summed over the frames since the last
                                              // sgs_row_records(reset) — what cost-balanced tile-row bands are cut from
     const sgs_scene* last_scene = nullptr;
     int64_t rec_cap_wanted = 16ll << 20;
     // status ring
-    FrameStatus* d_status = nullptr;
-    FrameStatus* h_status = nullptr;
+    DevBuf<FrameStatus> d_status;
+    PinnedBuf<FrameStatus> h_status;
     int next_slot = 0;
     // bookkeeping of the most recent frame
     int last_slot = -1;
@@ -198,8 +184,8 @@ struct sgs_ctx {
     hipStream_t last_stream = nullptr;
     // frames issued since the last synchronisation (ring slots pending_begin .. +pending_count)
     int pending_begin = 0, pending_count = 0;
-    // per-slot event sets for SGS_FLAG_TIMING, created on first use
-    hipEvent_t (*ev)[SGS_NUM_STAGES + 1] = nullptr;
+    // per-slot event sets for SGS_FLAG_TIMING, [kStatusRing][SGS_NUM_STAGES + 1], created on first use (ensure_timing_events)
+    std::unique_ptr<sgs::Event[]> ev;
     bool slot_timed[256] = {};
 };
 
@@ -221,104 +207,103 @@ struct sgs_ctx {
 
 namespace {
 
+// A counter array that the kernels keep zeroed from then on needs ONE clear, at its allocation.  hipMemset of device memory runs on the
+// NULL stream and may return before it has run; the frames use non-blocking streams that do not order with it — an unfinished clear would
+// land in the middle of a frame's counting — hence the synchronisation.  An array that could not be cleared is not kept.
 template <class T>
-int grow(sgs_ctx* ctx, T*& p, size_t count) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    if (count == 0) count = 1;
-    SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)));
+int grow_zeroed(sgs_ctx* ctx, DevBuf<T>& b, int64_t want) {
+    if (b.holds(want)) return SGS_OK;
+    SGS_HIP(ctx, b.grow(want));
+    hipError_t e = hipMemset(b.p, 0, (size_t)want * sizeof(T));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { b.reset(); SGS_FAIL(ctx, SGS_ERR_HIP, "clearing a counter array: %s", hipGetErrorString(e)); }
     return SGS_OK;
 }
 
-// A scratch array of the file encoders, of at least `want` elements: grows geometrically; hipFree waits for the encodes that still use
-// the old array.  The capacity reads 0 while the array is being replaced, so a failed allocation leaves a state the next call recovers from.
-template <class T>
-int reserve(sgs_ctx* ctx, T*& p, int64_t& cap, int64_t want) {
-    if (want <= cap) return SGS_OK;
-    const int64_t c = std::max<int64_t>(want, 2 * cap);
-    cap = 0;
-    const int rc = grow(ctx, p, (size_t)c);
-    if (rc == SGS_OK) cap = c;
-    return rc;
-}
-
-void free_file_scratch(FileScratch& F) {
-    if (F.offs) (void)hipFree(F.offs);
-    if (F.h_status) (void)hipHostFree(F.h_status);
-}
-
+// The ensure_* functions: every array of a set present at the capacity the frame needs.  Each growth decides by its own array (one
+// comparison when it is large enough), so an allocation that failed half-way through a set is simply made again by the next frame.
 int ensure_splats(sgs_ctx* ctx, Lane& L, int64_t n) {
-    if (n <= L.splat_cap && L.blk_len) return SGS_OK;
     const int64_t chunks = std::max<int64_t>(1, (n + 63) / 64);
     const int64_t cap = chunks * 64;
     int rc;
-    if ((rc = grow(ctx, L.splats, (size_t)cap)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.vismask, (size_t)chunks)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.bigmask, (size_t)chunks)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.binrec, (size_t)cap)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.live_list, (size_t)chunks * (1 + SGS_MAX_GROUP) + 2)) != SGS_OK) return rc;     // the list | a group's work list (sgs_work_list)
-    if (!L.big_list && (rc = grow(ctx, L.big_list, (size_t)SGS_BIG_CAP)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.blk_len, (size_t)SGS_BIN_BLOCKS * 2)) != SGS_OK) return rc;                      // list lengths | XCD ids
-    if (!L.blk_list && (rc = grow(ctx, L.blk_list, (size_t)SGS_BIN_BLOCKS * SGS_WT)) != SGS_OK) return rc;
-    if (!L.stile_count) {
-        if ((rc = grow(ctx, L.stile_count, (size_t)SGS_WT * SGS_XCDS)) != SGS_OK) return rc;
-        if ((rc = grow(ctx, L.stile_offset, (size_t)SGS_WT * SGS_XCDS + 1)) != SGS_OK) return rc;
-        // k_bin_emit zeroes every count k_stile_scan has consumed, so one memset at allocation suffices (see ensure_tiles)
-        SGS_HIP(ctx, hipMemset(L.stile_count, 0, (size_t)SGS_WT * SGS_XCDS * sizeof(unsigned)));
-        SGS_HIP(ctx, hipStreamSynchronize(nullptr));
-    }
-    if ((rc = grow(ctx, L.bin_prof, (size_t)SGS_BIN_BLOCKS * 8)) != SGS_OK) return rc;
-    L.splat_cap = cap;
+    SGS_HIP(ctx, L.splats.grow(cap));
+    SGS_HIP(ctx, L.vismask.grow(chunks));
+    SGS_HIP(ctx, L.bigmask.grow(chunks));
+    SGS_HIP(ctx, L.binrec.grow(cap));
+    SGS_HIP(ctx, L.live_list.grow(chunks * (1 + SGS_MAX_GROUP) + 2));       // the list | a group's work list (sgs_work_list)
+    SGS_HIP(ctx, L.big_list.grow(SGS_BIG_CAP));
+    SGS_HIP(ctx, L.blk_len.grow(SGS_BIN_BLOCKS * 2));                       // list lengths | XCD ids
+    SGS_HIP(ctx, L.blk_list.grow((int64_t)SGS_BIN_BLOCKS * SGS_WT));
+    // k_bin_emit zeroes every count k_stile_scan has consumed
+    if ((rc = grow_zeroed(ctx, L.stile_count, (int64_t)SGS_WT * SGS_XCDS)) != SGS_OK) return rc;
+    SGS_HIP(ctx, L.stile_offset.grow((int64_t)SGS_WT * SGS_XCDS + 1));
+    SGS_HIP(ctx, L.bin_prof.grow(SGS_BIN_BLOCKS * 8));
     return SGS_OK;
 }
 
 int ensure_tiles(sgs_ctx* ctx, Lane& L, int tiles) {
-    if (tiles <= L.tile_cap) return SGS_OK;
     int rc;
-    if ((rc = grow(ctx, L.tile_count, (size_t)tiles + 1)) != SGS_OK) return rc;          // level 2: one counter per tile
-    if ((rc = grow(ctx, L.tile_offset, (size_t)tiles + 1)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.tile_prof, (size_t)tiles * SGS_PROF_WORDS)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.tile_order, (size_t)tiles)) != SGS_OK) return rc;
-    // k_expand<true> zeroes every count k_tile_scan has consumed, so one memset at allocation suffices
-    SGS_HIP(ctx, hipMemset(L.tile_count, 0, ((size_t)tiles + 1) * sizeof(unsigned)));
-    // (hipMemset of device memory runs on the NULL stream and may return before it has run; the frames use non-blocking
-    //  streams that do not order with it — an unfinished clear would land in the middle of a frame's counting)
-    SGS_HIP(ctx, hipStreamSynchronize(nullptr));
-    L.tile_cap = tiles;
+    // level 2: one counter per tile; k_expand<true> zeroes every count k_tile_scan has consumed
+    if ((rc = grow_zeroed(ctx, L.tile_count, (int64_t)tiles + 1)) != SGS_OK) return rc;
+    SGS_HIP(ctx, L.tile_offset.grow((int64_t)tiles + 1));
+    SGS_HIP(ctx, L.tile_prof.grow((int64_t)tiles * SGS_PROF_WORDS));
+    SGS_HIP(ctx, L.tile_order.grow(tiles));
     return SGS_OK;
 }
 
-int ensure_records(sgs_ctx* ctx, Lane& L) {
-    if (L.rec_cap >= ctx->rec_cap_wanted && L.rec) return SGS_OK;
-    const int64_t cap = std::max<int64_t>(ctx->rec_cap_wanted, 1024);
-    if (cap > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "record capacity %lld exceeds 2^32", (long long)cap);
-    int rc;
-    if ((rc = grow(ctx, L.rec, (size_t)cap)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.alt, (size_t)cap)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.part, (size_t)cap)) != SGS_OK) return rc;
+// The record arrays of a lane share ONE capacity, rec.cap (what the kernels are told: fill_params), or are all empty.
+void release_records(Lane& L) { L.rec.reset(); L.alt.reset(); L.part.reset(); L.jobs.reset(); L.job_base.reset(); }
+
+int grow_records(sgs_ctx* ctx, Lane& L, int64_t cap) {
+    SGS_HIP(ctx, L.rec.grow(cap));
+    SGS_HIP(ctx, L.alt.grow(cap));
+    SGS_HIP(ctx, L.part.grow(cap));
     // level-2 jobs: the super-tile queues (cap / 2 records of 16 bytes, in `alt`) in segments of SGS_SEG, plus one ragged
     // segment per super-tile
     const int64_t jcap = cap / 2 / SGS_SEG + SGS_WT + 1;
-    if ((rc = grow(ctx, L.jobs, (size_t)jcap)) != SGS_OK) return rc;
-    if ((rc = grow(ctx, L.job_base, (size_t)jcap * (SGS_ST * SGS_ST))) != SGS_OK) return rc;
-    L.job_cap = jcap;
-    L.rec_cap = cap;
+    SGS_HIP(ctx, L.jobs.grow(jcap));
+    SGS_HIP(ctx, L.job_base.grow(jcap * (SGS_ST * SGS_ST)));
     return SGS_OK;
 }
 
+// ... at exactly the capacity wanted: sgs_set_record_capacity empties every lane's, growth does the rest.
+int ensure_records(sgs_ctx* ctx, Lane& L) {
+    const int64_t cap = std::max<int64_t>(ctx->rec_cap_wanted, 1024);
+    if (cap > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "record capacity %lld exceeds 2^32", (long long)cap);
+    const int rc = grow_records(ctx, L, cap);
+    if (rc != SGS_OK) release_records(L);
+    return rc;
+}
+
 int ensure_sorted_out(sgs_ctx* ctx, Lane& L) {
-    if (L.sorted_cap >= L.rec_cap && L.sorted_out) return SGS_OK;
-    int rc;
-    if ((rc = grow(ctx, L.sorted_out, (size_t)L.rec_cap)) != SGS_OK) return rc;
-    L.sorted_cap = L.rec_cap;
+    SGS_HIP(ctx, L.sorted_out.grow(L.rec.cap));
     return SGS_OK;
 }
 
 // A lane's stream and events exist from its first pipelined frame on.
 int ensure_lane_stream(sgs_ctx* ctx, Lane& L) {
-    if (L.stream) return SGS_OK;
-    SGS_HIP(ctx, hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-    SGS_HIP(ctx, hipEventCreateWithFlags(&L.fork, hipEventDisableTiming));
-    SGS_HIP(ctx, hipEventCreateWithFlags(&L.done, hipEventDisableTiming));
+    SGS_HIP(ctx, L.stream.create(hipStreamNonBlocking));
+    SGS_HIP(ctx, L.fork.create(hipEventDisableTiming));
+    SGS_HIP(ctx, L.done.create(hipEventDisableTiming));
+    return SGS_OK;
+}
+
+// The event sets of SGS_FLAG_TIMING: all of them or none.
+int ensure_timing_events(sgs_ctx* ctx) {
+    if (ctx->ev) return SGS_OK;
+    constexpr int n = kStatusRing * (SGS_NUM_STAGES + 1);
+    std::unique_ptr<sgs::Event[]> ev(new (std::nothrow) sgs::Event[n]);
+    if (!ev) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
+    for (int i = 0; i < n; ++i) SGS_HIP(ctx, ev[i].create());
+    ctx->ev = std::move(ev);
+    return SGS_OK;
+}
+const sgs::Event* slot_events(const sgs_ctx* ctx, int slot) { return &ctx->ev[(size_t)slot * (SGS_NUM_STAGES + 1)]; }
+
+// The mesh path's status words, on the device and pinned: made by the first mesh upload or mesh frame of a context.
+int ensure_mesh_status(sgs_ctx* ctx) {
+    SGS_HIP(ctx, ctx->mesh.d_st.grow(SGS_MESH_MAX_GROUP + 1));
+    SGS_HIP(ctx, ctx->mesh.h_st.grow(SGS_MESH_MAX_GROUP + 1));
     return SGS_OK;
 }
 
@@ -326,7 +311,7 @@ int ensure_lane_stream(sgs_ctx* ctx, Lane& L) {
 int drain_lanes(sgs_ctx* ctx) {
     for (int l = 0; l < kMaxLanes; ++l) {
         Lane& L = ctx->lanes[l];
-        if (L.busy) { SGS_HIP(ctx, hipEventSynchronize(L.done)); L.busy = false; }
+        if (L.busy) { SGS_HIP(ctx, hipEventSynchronize(L.done.e)); L.busy = false; }
     }
     return SGS_OK;
 }
@@ -403,12 +388,45 @@ int fine_shift_of(const sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* 
     return z;
 }
 
+// What every path asks of a camera (sage_gs.h): nullptr, or what is wrong with it (in `why`).
+const char* check_camera(const sgs_camera& cam, char* why, size_t n_why) {
+    if (cam.width <= 0 || cam.height <= 0 || cam.width > 65535 * SGS_TILE || cam.height > 65535 * SGS_TILE) {
+        snprintf(why, n_why, "bad resolution %dx%d", cam.width, cam.height); return why;
+    }
+    if (!(cam.fx > 0.f) || !(cam.fy > 0.f)) { snprintf(why, n_why, "focal lengths must be positive"); return why; }
+    // the view must be rigid: k_preprocess's fp32 screen-bound exclusion prices a Gaussian's footprint with |J|_F^2 s_max^2, which a
+    // scaled or sheared view would break silently (a USD xformOp:scale != 1 has to be applied to the Gaussians' means and scales by
+    // the caller), and the mesh path's depth is the camera-space z of a rigid view
+    const float* V = cam.view;
+    for (int r = 0; r < 3; ++r)
+        for (int c = r; c < 3; ++c) {
+            const double d = (double)V[4 * r] * V[4 * c] + (double)V[4 * r + 1] * V[4 * c + 1] + (double)V[4 * r + 2] * V[4 * c + 2];
+            // (fp32 pose matrices are orthonormal to ~1e-6; the per-chunk bounds and the footprint bound of k_preprocess
+            //  absorb ~1e-4 of non-rigidity, so the contract is an order of magnitude inside that)
+            if (!(std::fabs(d - (r == c ? 1.0 : 0.0)) < 1.0e-5)) {
+                snprintf(why, n_why, "view is not rigid: rows %d.%d of its 3x3 give %g", r, c, d); return why;
+            }
+        }
+    return nullptr;
+}
+
+// Pixel rows of a frame of `height` that the 16-pixel tile rows [row_begin, row_end) of a call cover, row k of the call being row
+// k * stride + phase of the frame (sgs_config.tile_row_stride / _phase).  The same count under fine tiles: a 16-pixel row is 2^z rows
+// of cells, clipped to the same height.
+int64_t band_pixel_rows(int height, int row_begin, int row_end, int stride, int phase) {
+    int64_t rows = 0;
+    for (int k = row_begin; k < row_end; ++k) {
+        const int y0 = (k * stride + phase) * SGS_TILE;
+        rows += std::max(0, std::min(y0 + SGS_TILE, height) - y0);
+    }
+    return rows;
+}
+
 int validate(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const sgs_config* cfg,
              int& row_begin, int& row_end, const float* out_rgb, int* fine_shift = nullptr) {
     if (!scene || !cam || !out_rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "null scene / camera / output");
-    if (cam->width <= 0 || cam->height <= 0 || cam->width > 65535 * SGS_TILE || cam->height > 65535 * SGS_TILE)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "bad resolution %dx%d", cam->width, cam->height);
-    if (!(cam->fx > 0.f) || !(cam->fy > 0.f)) SGS_FAIL(ctx, SGS_ERR_INVALID, "focal lengths must be positive");
+    char why[160];
+    if (check_camera(*cam, why, sizeof why)) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera: %s", why);
     const int stride = cfg && cfg->tile_row_stride > 1 ? cfg->tile_row_stride : 1, phase = cfg && stride > 1 ? cfg->tile_row_phase : 0;
     if (phase < 0 || phase >= stride) SGS_FAIL(ctx, SGS_ERR_INVALID, "tile_row_phase %d outside [0, stride %d)", phase, stride);
     const int gy_frame = (cam->height + SGS_TILE - 1) / SGS_TILE;
@@ -425,19 +443,6 @@ int validate(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const 
             SGS_FAIL(ctx, SGS_ERR_INVALID, "need 0 < alpha_min <= alpha_max < 1 (got %g, %g)", cfg->alpha_min, cfg->alpha_max);
         if (!(cfg->t_min > 0.f) || !(cfg->t_min < 1.f)) SGS_FAIL(ctx, SGS_ERR_INVALID, "need 0 < t_min < 1 (got %g)", cfg->t_min);
         if (!(cfg->dilation >= 0.f) || !(cfg->clamp > 0.f)) SGS_FAIL(ctx, SGS_ERR_INVALID, "need dilation >= 0 and clamp > 0");
-    }
-    {   // the view must be rigid (sage_gs.h): k_preprocess's fp32 screen-bound exclusion prices a Gaussian's footprint with
-        // |J|_F^2 s_max^2, which a scaled or sheared view would break silently (a USD xformOp:scale != 1 has to be applied
-        // to the Gaussians' means and scales by the caller)
-        const float* V = cam->view;
-        for (int r = 0; r < 3; ++r)
-            for (int c = r; c < 3; ++c) {
-                const double d = (double)V[4 * r] * V[4 * c] + (double)V[4 * r + 1] * V[4 * c + 1] + (double)V[4 * r + 2] * V[4 * c + 2];
-                // (fp32 pose matrices are orthonormal to ~1e-6; the per-chunk bounds and the footprint bound of k_preprocess
-                //  absorb ~1e-4 of non-rigidity, so the contract is an order of magnitude inside that)
-                if (!(std::fabs(d - (r == c ? 1.0 : 0.0)) < 1.0e-5))
-                    SGS_FAIL(ctx, SGS_ERR_INVALID, "camera view is not rigid: rows %d.%d of its 3x3 give %g", r, c, d);
-            }
     }
     if (gy_frame > SGS_MAX_ROWS) SGS_FAIL(ctx, SGS_ERR_INVALID, "height %d exceeds %d tile rows", cam->height, SGS_MAX_ROWS);
     // level 1 of the binning keeps one counter per super-tile of the band in LDS (the band's rows and tiles as the kernels count them:
@@ -482,8 +487,8 @@ void fill_params(FrameParams& P, const sgs_ctx* ctx, const Lane& L, const sgs_sc
     P.n_ranges = (int32_t)((scene->n + SGS_RANGE - 1) / SGS_RANGE);
     P.n_windows = 1;                                                              // (one window of super-tiles: sgs_kernels.h, level 1)
     P.limx = (double)P.clamp * (0.5 * (double)P.width / (double)P.fx); P.limy = (double)P.clamp * (0.5 * (double)P.height / (double)P.fy);
-    P.rec_capacity = L.rec_cap;
-    P.job_capacity = (int32_t)std::min<int64_t>(L.job_cap, 0x7fffffff);
+    P.rec_capacity = L.rec.cap;
+    P.job_capacity = (int32_t)std::min<int64_t>(L.jobs.cap, 0x7fffffff);
     P.flags = (cfg.flags & ~SGS_PFLAG_INTERNAL) | (scene->sh_packed ? SGS_PFLAG_SH_PACKED | ((uint32_t)scene->sh_decode << SGS_PFLAG_SH_MODE_SHIFT) : 0u) |
               ((uint32_t)z << SGS_PFLAG_FINE_SHIFT);
     {   // k_chunk_cull's planes (sgs_kernels.h chunk_outside: the derivation and why each constant is conservative)
@@ -596,7 +601,7 @@ int build_group(sgs_ctx* ctx, FrameGroup& G, const sgs_scene* scene, const sgs_c
     const int cp = SGS_TILE >> z;                 // (the frames of a group share a resolution, a configuration and the fine-tile shift)
     const int gx = (cams->width + cp - 1) / cp, gy = (cams->height + cp - 1) / cp;
     memset(&G, 0, sizeof G);
-    G.geom = scene->geom; G.shq = scene->shq; G.cbound = scene->cbound; G.row_acc = ctx->row_acc;
+    G.geom = scene->geom.p; G.shq = scene->shq.p; G.cbound = scene->cbound.p; G.row_acc = ctx->row_acc.p;
     for (int f = 0; f < nf; ++f) {
         Lane& A = ctx->lanes[set0 + f];
         if ((rc = ensure_splats(ctx, A, scene->n)) != SGS_OK) return rc;
@@ -605,35 +610,28 @@ int build_group(sgs_ctx* ctx, FrameGroup& G, const sgs_scene* scene, const sgs_c
         FrameSlot& S = G.s[f];
         fill_params(S.P, ctx, A, scene, &cams[f], cfg, row_begin, row_end, z);
         if ((S.P.flags & SGS_FLAG_FULL_SORT) && (rc = ensure_sorted_out(ctx, A)) != SGS_OK) return rc;
-        S.splats = A.splats; S.vismask = A.vismask; S.bigmask = A.bigmask; S.big_list = A.big_list; S.binrec = A.binrec;
-        S.live_list = A.live_list;
-        S.tile_count = A.tile_count; S.tile_offset = A.tile_offset; S.tile_order = A.tile_order;
-        S.blk_list = A.blk_list; S.blk_len = A.blk_len;
-        S.stile_count = A.stile_count; S.stile_offset = A.stile_offset; S.jobs = A.jobs; S.job_base = A.job_base;
-        S.rec = A.rec; S.alt = A.alt; S.part = A.part; S.sorted_out = A.sorted_out;
-        S.tile_prof = A.tile_prof; S.bin_prof = A.bin_prof;
-        S.out_rgb = outs[f]; S.out_aux = out_aux; S.st = ctx->d_status + slot0 + f;
+        S.splats = A.splats.p; S.vismask = A.vismask.p; S.bigmask = A.bigmask.p; S.big_list = A.big_list.p; S.binrec = A.binrec.p;
+        S.live_list = A.live_list.p;
+        S.tile_count = A.tile_count.p; S.tile_offset = A.tile_offset.p; S.tile_order = A.tile_order.p;
+        S.blk_list = A.blk_list.p; S.blk_len = A.blk_len.p;
+        S.stile_count = A.stile_count.p; S.stile_offset = A.stile_offset.p; S.jobs = A.jobs.p; S.job_base = A.job_base.p;
+        S.rec = A.rec.p; S.alt = A.alt.p; S.part = A.part.p; S.sorted_out = A.sorted_out.p;
+        S.tile_prof = A.tile_prof.p; S.bin_prof = A.bin_prof.p;
+        S.out_rgb = outs[f]; S.out_aux = out_aux; S.st = ctx->d_status.p + slot0 + f;
     }
     return SGS_OK;
 }
 
 // bookkeeping of "the most recent frame" (what sgs_frame_sync reports and sgs_debug_read looks at)
-void note_last(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const FrameParams& P, int slot, int lane, bool timed,
-               hipStream_t caller_stream) {
+void note_last(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const FrameParams& P, int row_begin16, int row_end16, int slot,
+               int lane, bool timed, hipStream_t caller_stream) {
     const int gx = P.gx, gy = P.gy, row_begin = P.row_begin, row_end = P.row_end;
     ctx->last_slot = slot; ctx->last_timed = timed; ctx->last_stream = caller_stream; ctx->last_lane = lane;
     ctx->last_n = scene->n; ctx->last_tiles = (row_end - row_begin) * gx; ctx->last_sh_rows = scene->sh_rows;
     ctx->last_T = gx * gy;
     ctx->last_t_lo = row_begin * gx; ctx->last_t_hi = row_end * gx;
     ctx->last_scene = scene;
-    int64_t pixel_rows = 0;                       // pixel rows of the frame this call wrote
-    const int z = (int)((P.flags >> SGS_PFLAG_FINE_SHIFT) & 3u), cp = SGS_TILE >> z;     // (rows of cells: sgs_common.h "Fine tiles")
-    for (int k = row_begin; k < row_end; ++k) {
-        const int k16 = k >> z;
-        const int y0 = (((k16 * P.row_stride + P.row_phase) << z) + (k - (k16 << z))) * cp;
-        pixel_rows += std::max(0, std::min(y0 + cp, cam->height) - y0);
-    }
-    ctx->last_pixels = pixel_rows * cam->width;
+    ctx->last_pixels = band_pixel_rows(cam->height, row_begin16, row_end16, P.row_stride, P.row_phase) * cam->width;     // pixels this call wrote
 }
 
 // Enqueue a GROUP of nf <= SGS_MAX_GROUP frames of one scene — same resolution, same tile rows, one camera each — as
@@ -656,50 +654,45 @@ int enqueue_group(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, 
     hipStream_t stream = caller_stream;
     if (pipelined) {
         if ((rc = ensure_lane_stream(ctx, L)) != SGS_OK) return rc;
-        stream = L.stream;
+        stream = L.stream.s;
     }
     FrameGroup G;
     if ((rc = build_group(ctx, G, scene, cams, nf, cfg, row_begin, row_end, outs, slot0, out_aux, set0, z)) != SGS_OK) return rc;
     const FrameParams& P = G.s[0].P;
     if (pipelined && !in_batch) {
         // start after whatever the caller already put on its stream (scene upload, consumers of the output buffer)
-        SGS_HIP(ctx, hipEventRecord(L.fork, caller_stream));
-        SGS_HIP(ctx, hipStreamWaitEvent(L.stream, L.fork, 0));
+        SGS_HIP(ctx, hipEventRecord(L.fork.e, caller_stream));
+        SGS_HIP(ctx, hipStreamWaitEvent(L.stream.s, L.fork.e, 0));
     } else if (!pipelined) {
         for (int f = 0; f < nf; ++f)               // these lanes' buffers may still be in use by a pipelined frame
-            if (ctx->lanes[set0 + f].busy) SGS_HIP(ctx, hipStreamWaitEvent(caller_stream, ctx->lanes[set0 + f].done, 0));
+            if (ctx->lanes[set0 + f].busy) SGS_HIP(ctx, hipStreamWaitEvent(caller_stream, ctx->lanes[set0 + f].done.e, 0));
     }
-    FrameStatus* st = ctx->d_status + slot0;
+    FrameStatus* st = ctx->d_status.p + slot0;
     if (!in_batch) SGS_HIP(ctx, hipMemsetAsync(st, 0, sizeof(FrameStatus) * (size_t)nf, stream));
-    hipEvent_t* ev = nullptr;
+    const sgs::Event* ev = nullptr;
     if (timed) {
-        if (!ctx->ev) {
-            ctx->ev = new (std::nothrow) hipEvent_t[kStatusRing][SGS_NUM_STAGES + 1];
-            if (!ctx->ev) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
-            for (int i = 0; i < kStatusRing; ++i)
-                for (int j = 0; j <= SGS_NUM_STAGES; ++j) SGS_HIP(ctx, hipEventCreate(&ctx->ev[i][j]));
-        }
-        ev = ctx->ev[slot0];
+        if ((rc = ensure_timing_events(ctx)) != SGS_OK) return rc;
+        ev = slot_events(ctx, slot0);
     }
     for (int f = 0; f < nf; ++f) ctx->slot_timed[slot0 + f] = timed && f == 0;
-    if (timed) SGS_HIP(ctx, hipEventRecord(ev[0], stream));
+    if (timed) SGS_HIP(ctx, hipEventRecord(ev[0].e, stream));
 
     launch_project(ctx, G, nf, stream);
-    if (timed) SGS_HIP(ctx, hipEventRecord(ev[1], stream));
-    launch_binning(ctx, G, nf, stream, timed ? ev[2] : nullptr);
-    if (timed) SGS_HIP(ctx, hipEventRecord(ev[3], stream));
+    if (timed) SGS_HIP(ctx, hipEventRecord(ev[1].e, stream));
+    launch_binning(ctx, G, nf, stream, timed ? ev[2].e : nullptr);
+    if (timed) SGS_HIP(ctx, hipEventRecord(ev[3].e, stream));
     launch_composite(G, nf, stream, out_aux != nullptr, (cfg.flags & SGS_FLAG_STATS) != 0, need_tf_of(cfg, out_aux));
-    if (timed) SGS_HIP(ctx, hipEventRecord(ev[4], stream));
+    if (timed) SGS_HIP(ctx, hipEventRecord(ev[4].e, stream));
     SGS_HIP(ctx, hipGetLastError());
     if (!in_batch) {
-        SGS_HIP(ctx, hipMemcpyAsync(ctx->h_status + slot0, st, sizeof(FrameStatus) * (size_t)nf, hipMemcpyDeviceToHost, stream));
+        SGS_HIP(ctx, hipMemcpyAsync(ctx->h_status.p + slot0, st, sizeof(FrameStatus) * (size_t)nf, hipMemcpyDeviceToHost, stream));
         if (pipelined) {
-            SGS_HIP(ctx, hipEventRecord(L.done, L.stream));
+            SGS_HIP(ctx, hipEventRecord(L.done.e, L.stream.s));
             L.busy = true;
         }
     }
 
-    note_last(ctx, scene, &cams[nf - 1], P, slot0 + nf - 1, set0 + nf - 1, timed, caller_stream);    // "the last frame" = the group's last
+    note_last(ctx, scene, &cams[nf - 1], P, row_begin, row_end, slot0 + nf - 1, set0 + nf - 1, timed, caller_stream);    // "the last frame" = the group's last
     return SGS_OK;
 }
 
@@ -711,7 +704,7 @@ int64_t records_needed(const FrameStatus& s) { return std::max<int64_t>((int64_t
 void collect(sgs_ctx* ctx, int slot, sgs_stats* stats, int64_t n, int ntiles, int64_t pixels, int sh_rows,
              bool timed) {
     if (!stats) return;
-    const FrameStatus& s = ctx->h_status[slot];
+    const FrameStatus& s = ctx->h_status.p[slot];
     memset(stats, 0, sizeof *stats);
     stats->n_gaussians = n;
     stats->n_visible = s.n_visible;
@@ -734,13 +727,13 @@ void collect(sgs_ctx* ctx, int slot, sgs_stats* stats, int64_t n, int ntiles, in
     stats->bytes[SGS_STAGE_EMIT] = 2 * 16 * Ds + 8 * D + 8 * ((int64_t)ctx->last_T + 1);
     stats->bytes[SGS_STAGE_RENDER] = 8 * D + 36 * Df + 12 * pixels;               // every record seen once, D_f splats blended
     if (timed && ctx->ev) {
-        hipEvent_t* ev = ctx->ev[slot];
+        const sgs::Event* ev = slot_events(ctx, slot);
         for (int i = 0; i < SGS_NUM_STAGES; ++i) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) stats->ms[i] = ms;
+            if (hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e) == hipSuccess) stats->ms[i] = ms;
         }
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ev[0], ev[SGS_NUM_STAGES]) == hipSuccess) stats->ms_total = ms;
+        if (hipEventElapsedTime(&ms, ev[0].e, ev[SGS_NUM_STAGES].e) == hipSuccess) stats->ms_total = ms;
     }
 }
 
@@ -790,10 +783,10 @@ int sgs_create(int device_id, int backend, sgs_ctx** out) {
         return SGS_ERR_HIP;
     };
     if ((e = hipSetDevice(device_id)) != hipSuccess) return fail("hipSetDevice", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->d_status), sizeof(FrameStatus) * kStatusRing)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_status), sizeof(FrameStatus) * kStatusRing, 0)) != hipSuccess) return fail("hipHostMalloc", e);
-    if ((e = hipMalloc(reinterpret_cast<void**>(&ctx->row_acc), sizeof(unsigned long long) * SGS_MAX_ROWS)) != hipSuccess) return fail("hipMalloc", e);
-    if ((e = hipMemset(ctx->row_acc, 0, sizeof(unsigned long long) * SGS_MAX_ROWS)) != hipSuccess) return fail("hipMemset", e);
+    if ((e = ctx->d_status.grow(kStatusRing)) != hipSuccess) return fail("the status ring", e);
+    if ((e = ctx->h_status.grow(kStatusRing)) != hipSuccess) return fail("the pinned status ring", e);
+    if ((e = ctx->row_acc.grow(SGS_MAX_ROWS)) != hipSuccess) return fail("the row counters", e);
+    if ((e = hipMemset(ctx->row_acc.p, 0, sizeof(unsigned long long) * SGS_MAX_ROWS)) != hipSuccess) return fail("hipMemset", e);
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail("hipStreamSynchronize", e);
     // (nothing is read from the environment: sgs_set_tuning is the library's whole tuning surface)
     *out = ctx;
@@ -804,42 +797,6 @@ int sgs_destroy(sgs_ctx* ctx) {
     if (!ctx) return SGS_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    for (Lane& L : ctx->lanes) {
-        void* bufs[] = {L.splats, L.vismask, L.bigmask, L.big_list, L.binrec, L.live_list, L.tile_count, L.tile_offset, L.tile_order,
-                        L.tile_prof, L.bin_prof, L.blk_list, L.blk_len, L.rec, L.alt, L.part, L.sorted_out,
-                        L.stile_count, L.stile_offset, L.jobs, L.job_base};
-        for (void* b : bufs) if (b) (void)hipFree(b);
-        if (L.stream) (void)hipStreamDestroy(L.stream);
-        if (L.fork) (void)hipEventDestroy(L.fork);
-        if (L.done) (void)hipEventDestroy(L.done);
-    }
-    {
-        MeshScratch& M = ctx->mesh;
-        void* bufs[] = {M.rec, M.rect, M.big, M.counts, M.offs, M.list, M.d_st};
-        for (void* b : bufs) if (b) (void)hipFree(b);
-        if (M.h_st) (void)hipHostFree(M.h_st);
-        for (hipEvent_t e : M.ev) if (e) (void)hipEventDestroy(e);
-    }
-    {
-        for (JpegScratch::Entry& e : ctx->jpeg.tables) if (e.dev) (void)hipFree(e.dev);
-        void* bufs[] = {ctx->jpeg.sizes, ctx->png.rec, ctx->png.slots, ctx->png.adler};
-        for (void* b : bufs) if (b) (void)hipFree(b);
-        free_file_scratch(ctx->jpeg.files);
-        free_file_scratch(ctx->png.files);
-        for (ResizeScratch::Entry& e : ctx->resize.tables) {
-            if (e.bounds) (void)hipFree(e.bounds);
-            if (e.weights) (void)hipFree(e.weights);
-        }
-        if (ctx->resize.mid) (void)hipFree(ctx->resize.mid);
-    }
-    if (ctx->d_status) (void)hipFree(ctx->d_status);
-    if (ctx->row_acc) (void)hipFree(ctx->row_acc);
-    if (ctx->h_status) (void)hipHostFree(ctx->h_status);
-    if (ctx->ev) {
-        for (int i = 0; i < kStatusRing; ++i)
-            for (int j = 0; j <= SGS_NUM_STAGES; ++j) (void)hipEventDestroy(ctx->ev[i][j]);
-        delete[] ctx->ev;
-    }
     delete ctx;
     return SGS_OK;
 }
@@ -888,12 +845,7 @@ int sgs_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
     SGS_HIP(ctx, hipDeviceSynchronize());
     const int64_t prev = ctx->rec_cap_wanted;
     ctx->rec_cap_wanted = max_records;
-    for (Lane& L : ctx->lanes) {      // force reallocation at the requested size (lanes other than 0: on next use)
-        L.rec_cap = 0;
-        if (&L != &ctx->lanes[0]) {
-            for (unsigned long long** q : {&L.rec, &L.alt, &L.part}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        }
-    }
+    for (Lane& L : ctx->lanes) release_records(L);      // reallocated at the requested size (lanes other than 0: on next use)
     // the new capacity holds only once lane 0's buffers exist; a failed allocation leaves the previous one wanted (every lane
     // reallocates at it on its next frame)
     const int rc = ensure_records(ctx, ctx->lanes[0]);
@@ -909,85 +861,77 @@ int layout_scene(sgs_ctx* ctx, sgs_scene* sc, const float* const* src, const sgs
     const int64_t n = sc->n;
     const int nf = 3 * (sc->sh_degree + 1) * (sc->sh_degree + 1);
     const size_t npad = (size_t)std::max<int64_t>(sc->n_chunks, 1) * 64;
-    hipError_t e;
+    DevBuf<unsigned long long> own_keys[2];       // the sort's buffers: released when this returns, however it returns
+    DevBuf<unsigned> own_idx[2], own_hist, own_bounds;
     unsigned long long* keys[2] = {nullptr, nullptr};
     unsigned* idx[2] = {nullptr, nullptr};
-    unsigned *hist = nullptr, *bounds = nullptr;
     const unsigned* d_perm = nullptr;
-    int rc = SGS_OK;
-    auto fail = [&](const char* what, hipError_t err) {
-        ctx->err = std::string("scene layout: ") + what + ": " + hipGetErrorString(err);
-        rc = err == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP;
-    };
     const float* means = packed ? nullptr : src[0];
     if (ctx->morton && n > SGS_WAVE) {
         // Z-order (Morton) permutation of the means, once per scene: 64 consecutive Gaussians then occupy a compact cell, so a chunk is
         // visible or culled as a whole (no half-used SH cache lines in k_preprocess) and its splats overlap on screen (binning)
         const unsigned nblocks = (unsigned)((n + SGS_RSORT_TILE - 1) / SGS_RSORT_TILE);
-        for (int k = 0; k < 2 && rc == SGS_OK; ++k) {
-            if ((e = hipMalloc(reinterpret_cast<void**>(&keys[k]), (size_t)n * 8)) != hipSuccess) fail("hipMalloc", e);
-            else if ((e = hipMalloc(reinterpret_cast<void**>(&idx[k]), (size_t)n * 4)) != hipSuccess) fail("hipMalloc", e);
+        for (int k = 0; k < 2; ++k) {
+            SGS_HIP(ctx, own_keys[k].grow(n));
+            SGS_HIP(ctx, own_idx[k].grow(n));
+            keys[k] = own_keys[k].p; idx[k] = own_idx[k].p;
         }
         const unsigned nscan = (256u * nblocks + SGS_RSCAN_SPAN - 1) / SGS_RSCAN_SPAN;          // (hist, then k_radix_scan's span sums)
-        if (rc == SGS_OK && (e = hipMalloc(reinterpret_cast<void**>(&hist), ((size_t)256 * nblocks + nscan) * 4)) != hipSuccess) fail("hipMalloc", e);
-        if (rc == SGS_OK && (e = hipMalloc(reinterpret_cast<void**>(&bounds), 6 * 4)) != hipSuccess) fail("hipMalloc", e);
-        if (rc == SGS_OK) {
-            const unsigned init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
-            if ((e = hipMemcpy(bounds, init, sizeof init, hipMemcpyHostToDevice)) != hipSuccess) fail("hipMemcpy", e);
+        SGS_HIP(ctx, own_hist.grow((int64_t)256 * nblocks + nscan));
+        SGS_HIP(ctx, own_bounds.grow(6));
+        unsigned* const hist = own_hist.p;
+        unsigned* const bounds = own_bounds.p;
+        const unsigned init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
+        SGS_HIP(ctx, hipMemcpy(bounds, init, sizeof init, hipMemcpyHostToDevice));
+        const unsigned g1 = (unsigned)std::min<int64_t>(512, (n + 255) / 256), gn = (unsigned)((n + 255) / 256);
+        if (packed) {
+            hipLaunchKernelGGL((sgs::k_mean_bounds<true>), dim3(g1), dim3(256), 0, 0, (long long)n, means, Z, bounds);
+            hipLaunchKernelGGL((sgs::k_morton_keys<true>), dim3(gn), dim3(256), 0, 0, (long long)n, means, Z, bounds, keys[0], idx[0]);
+        } else {
+            hipLaunchKernelGGL((sgs::k_mean_bounds<false>), dim3(g1), dim3(256), 0, 0, (long long)n, means, Z, bounds);
+            hipLaunchKernelGGL((sgs::k_morton_keys<false>), dim3(gn), dim3(256), 0, 0, (long long)n, means, Z, bounds, keys[0], idx[0]);
         }
-        if (rc == SGS_OK) {
-            const unsigned g1 = (unsigned)std::min<int64_t>(512, (n + 255) / 256), gn = (unsigned)((n + 255) / 256);
-            if (packed) {
-                hipLaunchKernelGGL((sgs::k_mean_bounds<true>), dim3(g1), dim3(256), 0, 0, (long long)n, means, Z, bounds);
-                hipLaunchKernelGGL((sgs::k_morton_keys<true>), dim3(gn), dim3(256), 0, 0, (long long)n, means, Z, bounds, keys[0], idx[0]);
-            } else {
-                hipLaunchKernelGGL((sgs::k_mean_bounds<false>), dim3(g1), dim3(256), 0, 0, (long long)n, means, Z, bounds);
-                hipLaunchKernelGGL((sgs::k_morton_keys<false>), dim3(gn), dim3(256), 0, 0, (long long)n, means, Z, bounds, keys[0], idx[0]);
-            }
-            int cur = 0;
-            for (int shift = 0; shift < 64; shift += 8, cur ^= 1) {      // 63 key bits: eight stable passes
-                hipLaunchKernelGGL(sgs::k_radix_count, dim3(nblocks), dim3(256), 0, 0, (long long)n, keys[cur], shift, nblocks, hist);
-                hipLaunchKernelGGL(sgs::k_radix_scan, dim3(nscan), dim3(1024), 0, 0, 256u * nblocks, hist, hist + (size_t)256 * nblocks);
-                hipLaunchKernelGGL(sgs::k_radix_scatter, dim3(nblocks), dim3(256), 0, 0, (long long)n, keys[cur], idx[cur], keys[cur ^ 1], idx[cur ^ 1],
-                                   shift, nblocks, hist, hist + (size_t)256 * nblocks);
-            }
-            d_perm = idx[cur];               // (an even number of passes: back in buffer 0)
-            sc->perm_host = (unsigned*)malloc((size_t)n * 4);
-            if (!sc->perm_host) { ctx->err = "scene layout: out of host memory"; rc = SGS_ERR_OOM; }
-            else if ((e = hipMemcpy(sc->perm_host, d_perm, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) fail("reading the permutation", e);
+        int cur = 0;
+        for (int shift = 0; shift < 64; shift += 8, cur ^= 1) {      // 63 key bits: eight stable passes
+            hipLaunchKernelGGL(sgs::k_radix_count, dim3(nblocks), dim3(256), 0, 0, (long long)n, keys[cur], shift, nblocks, hist);
+            hipLaunchKernelGGL(sgs::k_radix_scan, dim3(nscan), dim3(1024), 0, 0, 256u * nblocks, hist, hist + (size_t)256 * nblocks);
+            hipLaunchKernelGGL(sgs::k_radix_scatter, dim3(nblocks), dim3(256), 0, 0, (long long)n, keys[cur], idx[cur], keys[cur ^ 1], idx[cur ^ 1],
+                               shift, nblocks, hist, hist + (size_t)256 * nblocks);
         }
+        d_perm = idx[cur];                 // (an even number of passes: back in buffer 0)
+        sc->perm_host.resize((size_t)n);
+        SGS_HIP(ctx, hipMemcpy(sc->perm_host.data(), d_perm, (size_t)n * 4, hipMemcpyDeviceToHost));
     }
-    if (rc == SGS_OK) {
+    {
         const unsigned grid = (unsigned)((npad + 255) / 256);
         if (packed)
             hipLaunchKernelGGL((sgs::k_scene_layout<true>), dim3(grid), dim3(256), 0, 0, (long long)n, nf, sc->sh_rows, d_perm,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, Z, sc->geom, sc->shq);
+                               nullptr, nullptr, nullptr, nullptr, nullptr, Z, sc->geom.p, sc->shq.p);
         else
             hipLaunchKernelGGL((sgs::k_scene_layout<false>), dim3(grid), dim3(256), 0, 0, (long long)n, nf, sc->sh_rows, d_perm,
-                               src[0], src[1], src[2], src[3], src[4], Z, sc->geom, sc->shq);
+                               src[0], src[1], src[2], src[3], src[4], Z, sc->geom.p, sc->shq.p);
         hipLaunchKernelGGL(sgs::k_chunk_bounds, dim3((unsigned)((sc->n_chunks + 3) / 4)), dim3(256), 0, 0, (long long)n,
-                           (long long)sc->n_chunks, sc->geom, sc->cbound);
-        if ((e = hipDeviceSynchronize()) != hipSuccess) fail("k_scene_layout / k_chunk_bounds", e);
+                           (long long)sc->n_chunks, sc->geom.p, sc->cbound.p);
+        SGS_HIP(ctx, hipDeviceSynchronize());
     }
-    if (rc == SGS_OK && n > 0) {
+    if (n > 0) {
         // the probe (fine_shift_of): a pre-sample of up to 64 Ki Gaussians at even strides through the caller's order comes to the host (through
         // the inverse of the Z-order permutation, in the sort's spare index buffer); 512 of them are drawn from it — systematically, with
         // probability 1/2 (1 / M0 + trace_i / sum of traces) each — and their covariances formed once
         const int M0 = (int)std::min<int64_t>(n, 65536), M = std::min(M0, 512);
-        float4* d_probe = nullptr;
+        DevBuf<float4> own_probe;
         unsigned* d_inv = nullptr;
         if (d_perm) {
             d_inv = idx[d_perm == idx[0] ? 1 : 0];
             hipLaunchKernelGGL(sgs::k_invert_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (long long)n, d_perm, d_inv);
         }
         std::vector<float4> rows((size_t)M0 * SGS_GEOM_ROWS);
-        if ((e = hipMalloc(reinterpret_cast<void**>(&d_probe), rows.size() * sizeof(float4))) != hipSuccess) fail("hipMalloc", e);
-        else {
-            hipLaunchKernelGGL(sgs::k_probe_gather, dim3((unsigned)((M0 + 255) / 256)), dim3(256), 0, 0, (long long)n, M0, d_inv, sc->geom, d_probe);
-            if ((e = hipMemcpy(rows.data(), d_probe, rows.size() * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) fail("reading the probe", e);
-            (void)hipFree(d_probe);
-        }
-        if (rc == SGS_OK) {
+        SGS_HIP(ctx, own_probe.grow((int64_t)rows.size()));
+        float4* const d_probe = own_probe.p;
+        hipLaunchKernelGGL(sgs::k_probe_gather, dim3((unsigned)((M0 + 255) / 256)), dim3(256), 0, 0, (long long)n, M0, d_inv, sc->geom.p, d_probe);
+        SGS_HIP(ctx, hipMemcpy(rows.data(), d_probe, rows.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        own_probe.reset();
+        {
             std::vector<double> tr((size_t)M0);
             double T = 0.0;
             for (int i = 0; i < M0; ++i) {
@@ -1027,43 +971,31 @@ int layout_scene(sgs_ctx* ctx, sgs_scene* sc, const float* const* src, const sgs
             }
         }
     }
-    for (int k = 0; k < 2; ++k) { if (keys[k]) (void)hipFree(keys[k]); if (idx[k]) (void)hipFree(idx[k]); }
-    if (hist) (void)hipFree(hist);
-    if (bounds) (void)hipFree(bounds);
-    return rc;
+    return SGS_OK;
 }
 
 // a new scene object with its device buffers
-int new_scene(sgs_ctx* ctx, int64_t n, int sh_degree, bool sh_packed, sgs_scene** out) {
-    sgs_scene* sc = new (std::nothrow) sgs_scene;
+int new_scene(sgs_ctx* ctx, int64_t n, int sh_degree, bool sh_packed, std::unique_ptr<sgs_scene>& out) {
+    std::unique_ptr<sgs_scene> sc(new (std::nothrow) sgs_scene);
     if (!sc) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
     const int nf = 3 * (sh_degree + 1) * (sh_degree + 1);
     sc->n = n; sc->n_chunks = (n + 63) / 64; sc->sh_degree = sh_degree; sc->sh_packed = sh_packed;
     sc->sh_rows = sh_packed ? (12 + (nf - 3) + 15) / 16 : (nf + 3) / 4;      // packed: 12 B of fp32 DC + one byte per higher coefficient
     const size_t npad = (size_t)std::max<int64_t>(sc->n_chunks, 1) * 64;
-    hipError_t e;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&sc->geom), npad * SGS_GEOM_ROWS * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&sc->shq), npad * sc->sh_rows * sizeof(float4))) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&sc->cbound), (npad / 64) * 2 * sizeof(float4))) != hipSuccess) {
-        ctx->err = std::string("scene upload: hipMalloc: ") + hipGetErrorString(e);
-        sgs_scene_free(ctx, sc);
-        return e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP;
-    }
-    *out = sc;
+    SGS_HIP(ctx, sc->geom.grow((int64_t)(npad * SGS_GEOM_ROWS)));
+    SGS_HIP(ctx, sc->shq.grow((int64_t)(npad * sc->sh_rows)));
+    SGS_HIP(ctx, sc->cbound.grow((int64_t)(npad / 64) * 2));
+    out = std::move(sc);
     return SGS_OK;
 }
 
-// host arrays -> device copies (on_device: the caller's pointers as they are).  staged[] holds what must be freed.
-int stage(sgs_ctx* ctx, int on_device, const void* const* src, const size_t* bytes, int count, const void** dev, void** staged) {
+// host arrays -> device copies (on_device: the caller's pointers as they are).  staged[] owns the copies.
+int stage(sgs_ctx* ctx, int on_device, const void* const* src, const size_t* bytes, int count, const void** dev, DevBuf<unsigned char>* staged) {
     for (int i = 0; i < count; ++i) {
-        staged[i] = nullptr;
         if (on_device || !src[i] || bytes[i] == 0) { dev[i] = src[i]; continue; }
-        hipError_t e;
-        if ((e = hipMalloc(&staged[i], bytes[i])) != hipSuccess || (e = hipMemcpy(staged[i], src[i], bytes[i], hipMemcpyHostToDevice)) != hipSuccess) {
-            ctx->err = std::string("scene upload: staging: ") + hipGetErrorString(e);
-            return e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP;
-        }
-        dev[i] = staged[i];
+        SGS_HIP(ctx, staged[i].grow((int64_t)bytes[i]));
+        SGS_HIP(ctx, hipMemcpy(staged[i].p, src[i], bytes[i], hipMemcpyHostToDevice));
+        dev[i] = staged[i].p;
     }
     return SGS_OK;
 }
@@ -1080,24 +1012,20 @@ int sgs_scene_upload(sgs_ctx* ctx, int64_t n, int sh_degree, const float* means,
     if (sh_degree < 0 || sh_degree > 3) SGS_FAIL(ctx, SGS_ERR_INVALID, "sh_degree %d not in 0..3", sh_degree);
     if (n > 0 && (!means || !scales || !quats || !opacities || !sh)) SGS_FAIL(ctx, SGS_ERR_INVALID, "null input array");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
-    sgs_scene* sc = nullptr;
+    std::unique_ptr<sgs_scene> sc;            // (released with its buffers by any return before *out)
     int rc;
-    if ((rc = new_scene(ctx, n, sh_degree, false, &sc)) != SGS_OK) return rc;
+    if ((rc = new_scene(ctx, n, sh_degree, false, sc)) != SGS_OK) return rc;
     if (n > 0) {
         const int nf = 3 * (sh_degree + 1) * (sh_degree + 1);
         const void* src[5] = {means, scales, quats, opacities, sh};
         const size_t bytes[5] = {(size_t)n * 12, (size_t)n * 12, (size_t)n * 16, (size_t)n * 4, (size_t)n * nf * 4};
-        const void* dev[5]; void* staged[5] = {};
-        rc = stage(ctx, on_device, src, bytes, 5, dev, staged);
-        if (rc == SGS_OK) {
-            const float* f[5] = {(const float*)dev[0], (const float*)dev[1], (const float*)dev[2], (const float*)dev[3], (const float*)dev[4]};
-            sgs::PackedScene Z = {nullptr, nullptr, nullptr, 0};
-            rc = layout_scene(ctx, sc, f, Z, false);
-        }
-        for (void* q : staged) if (q) (void)hipFree(q);
-        if (rc != SGS_OK) { sgs_scene_free(ctx, sc); return rc; }
+        const void* dev[5]; DevBuf<unsigned char> staged[5];
+        if ((rc = stage(ctx, on_device, src, bytes, 5, dev, staged)) != SGS_OK) return rc;
+        const float* f[5] = {(const float*)dev[0], (const float*)dev[1], (const float*)dev[2], (const float*)dev[3], (const float*)dev[4]};
+        sgs::PackedScene Z = {nullptr, nullptr, nullptr, 0};
+        if ((rc = layout_scene(ctx, sc.get(), f, Z, false)) != SGS_OK) return rc;
     }
-    *out = sc;
+    *out = sc.release();
     return SGS_OK;
 }
 
@@ -1116,34 +1044,26 @@ int sgs_scene_upload_compressed(sgs_ctx* ctx, const sgs_compressed_scene* z, int
     if (n > 0 && (!z->chunks || !z->packed || (k_rest > 0 && !z->sh))) SGS_FAIL(ctx, SGS_ERR_INVALID, "null input array");
     if (z->n_chunks != (n + 255) / 256) SGS_FAIL(ctx, SGS_ERR_INVALID, "n_chunks %lld is not ceil(n / 256)", (long long)z->n_chunks);
     SGS_HIP(ctx, hipSetDevice(ctx->device));
-    sgs_scene* sc = nullptr;
+    std::unique_ptr<sgs_scene> sc;
     int rc;
-    if ((rc = new_scene(ctx, n, z->sh_degree, true, &sc)) != SGS_OK) return rc;
+    if ((rc = new_scene(ctx, n, z->sh_degree, true, sc)) != SGS_OK) return rc;
     // (the kernels' mode: 0 = bin centre — one exact fma —, 1 = linear255, 2 = bin centre with exact ends)
     sc->sh_decode = (z->sh_decode == SGS_SH_DECODE_BIN_CENTRE || z->sh_decode == SGS_SH_DECODE_UNSPECIFIED) ? 0 : z->sh_decode;
     if (n > 0) {
         const void* src[3] = {z->chunks, z->packed, z->sh};
         const size_t bytes[3] = {(size_t)z->n_chunks * 18 * 4, (size_t)n * 16, (size_t)n * 3 * k_rest};
-        const void* dev[3]; void* staged[3] = {};
-        rc = stage(ctx, on_device, src, bytes, 3, dev, staged);
-        if (rc == SGS_OK) {
-            sgs::PackedScene Z = {(const float*)dev[0], (const uint4*)dev[1], (const unsigned char*)dev[2], k_rest};
-            rc = layout_scene(ctx, sc, nullptr, Z, true);
-        }
-        for (void* q : staged) if (q) (void)hipFree(q);
-        if (rc != SGS_OK) { sgs_scene_free(ctx, sc); return rc; }
+        const void* dev[3]; DevBuf<unsigned char> staged[3];
+        if ((rc = stage(ctx, on_device, src, bytes, 3, dev, staged)) != SGS_OK) return rc;
+        sgs::PackedScene Z = {(const float*)dev[0], (const uint4*)dev[1], (const unsigned char*)dev[2], k_rest};
+        if ((rc = layout_scene(ctx, sc.get(), nullptr, Z, true)) != SGS_OK) return rc;
     }
-    *out = sc;
+    *out = sc.release();
     return SGS_OK;
 }
 
 int sgs_scene_free(sgs_ctx* ctx, sgs_scene* scene) {
     if (!scene) return SGS_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipDeviceSynchronize(); }
-    if (scene->geom) (void)hipFree(scene->geom);
-    if (scene->shq) (void)hipFree(scene->shq);
-    if (scene->cbound) (void)hipFree(scene->cbound);
-    if (scene->perm_host) free(scene->perm_host);
     if (ctx && ctx->last_scene == scene) ctx->last_scene = nullptr;
     delete scene;
     return SGS_OK;
@@ -1162,12 +1082,13 @@ int sgs_frame_sync(sgs_ctx* ctx, sgs_stats* stats) {
     int n_timed = 0;
     for (int k = 0; k < ctx->pending_count; ++k) {
         const int slot = (ctx->pending_begin + k) % kStatusRing;
-        if (ctx->h_status[slot].overflow) { bad = slot; ++n_bad; }
+        if (ctx->h_status.p[slot].overflow) { bad = slot; ++n_bad; }
         if (ctx->slot_timed[slot] && ctx->ev) {
+            const sgs::Event* ev = slot_events(ctx, slot);
             float ms = 0.f;
             for (int i = 0; i < SGS_NUM_STAGES; ++i)
-                if (hipEventElapsedTime(&ms, ctx->ev[slot][i], ctx->ev[slot][i + 1]) == hipSuccess) ms_sum[i] += ms;
-            if (hipEventElapsedTime(&ms, ctx->ev[slot][0], ctx->ev[slot][SGS_NUM_STAGES]) == hipSuccess) ms_sum[SGS_NUM_STAGES] += ms;
+                if (hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e) == hipSuccess) ms_sum[i] += ms;
+            if (hipEventElapsedTime(&ms, ev[0].e, ev[SGS_NUM_STAGES].e) == hipSuccess) ms_sum[SGS_NUM_STAGES] += ms;
             ++n_timed;
         }
     }
@@ -1179,7 +1100,7 @@ int sgs_frame_sync(sgs_ctx* ctx, sgs_stats* stats) {
     if (n_bad)
         SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "%d frame(s) overflowed the record capacity %lld (one needs at least %lld records: D = %u, D_s = %u "
                  "super-tile records of which the capacity holds half as many); call sgs_set_record_capacity", n_bad,
-                 (long long)ctx->lanes[0].rec_cap, (long long)records_needed(ctx->h_status[bad]), ctx->h_status[bad].d_total, ctx->h_status[bad].ds_total);
+                 (long long)ctx->lanes[0].rec.cap, (long long)records_needed(ctx->h_status.p[bad]), ctx->h_status.p[bad].d_total, ctx->h_status.p[bad].ds_total);
     return SGS_OK;
 }
 
@@ -1220,9 +1141,8 @@ int sgs_render_rgbd(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam,
         if (rc != SGS_ERR_OVERFLOW) return rc;
         // synchronous path: grow the queues to fit and render again.  A frame can overflow at level 1 of the binning (the super-tile
         // queues hold rec_cap / 2 records of 16 bytes): level 2 then never ran and d_total is 0 — what is known is D_s
-        const int64_t need = records_needed(ctx->h_status[slot]);
-        ctx->rec_cap_wanted = std::max<int64_t>(need + need / 4, ctx->lanes[0].rec_cap * 2);
-        ctx->lanes[0].rec_cap = 0;
+        const int64_t need = records_needed(ctx->h_status.p[slot]);
+        ctx->rec_cap_wanted = std::max<int64_t>(need + need / 4, ctx->lanes[0].rec.cap * 2);
         if ((rc = ensure_records(ctx, ctx->lanes[0])) != SGS_OK) return rc;
         if (++ctx->last_retries > 4) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "record capacity still too small after 4 retries");
     }
@@ -1262,11 +1182,7 @@ int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_cam
     }
     if (n_cams > 1) {
         const int stride_t = cfg.tile_row_stride > 1 ? cfg.tile_row_stride : 1, phase_t = stride_t > 1 ? cfg.tile_row_phase : 0;
-        int64_t rows = 0;                           // pixel rows one frame of the batch writes
-        for (int k = rb0; k < re0; ++k) {
-            const int y0 = (k * stride_t + phase_t) * SGS_TILE;
-            rows += std::max(0, std::min(y0 + SGS_TILE, cams[0].height) - y0);
-        }
+        const int64_t rows = band_pixel_rows(cams[0].height, rb0, re0, stride_t, phase_t);     // pixel rows one frame of the batch writes
         if (frame_stride < rows * (int64_t)cams[0].width * 3)
             SGS_FAIL(ctx, SGS_ERR_INVALID, "frame_stride %lld is smaller than the band a frame writes (%lld floats)",
                      (long long)frame_stride, (long long)(rows * (int64_t)cams[0].width * 3));
@@ -1275,13 +1191,13 @@ int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_cam
         const int cn = std::min(kStatusRing, n_cams - c0);
         int64_t px[kStatusRing]; int tl[kStatusRing];
         // once per chunk of frames, not once per frame: zero the status slots, fork the group streams from the caller's
-        SGS_HIP(ctx, hipMemsetAsync(ctx->d_status, 0, sizeof(FrameStatus) * (size_t)cn, stream));
+        SGS_HIP(ctx, hipMemsetAsync(ctx->d_status.p, 0, sizeof(FrameStatus) * (size_t)cn, stream));
         if (lanes) {
             if ((rc = ensure_lane_stream(ctx, ctx->lanes[0])) != SGS_OK) return rc;
-            SGS_HIP(ctx, hipEventRecord(ctx->lanes[0].fork, stream));
+            SGS_HIP(ctx, hipEventRecord(ctx->lanes[0].fork.e, stream));
             for (int gl = 0; gl < GL; ++gl) {
                 if ((rc = ensure_lane_stream(ctx, ctx->lanes[gl])) != SGS_OK) return rc;
-                SGS_HIP(ctx, hipStreamWaitEvent(ctx->lanes[gl].stream, ctx->lanes[0].fork, 0));
+                SGS_HIP(ctx, hipStreamWaitEvent(ctx->lanes[gl].stream.s, ctx->lanes[0].fork.e, 0));
             }
         }
         // The chunk's frames are dealt to the group streams in EQUAL shares (the stream with an extra group finished it alone, without a
@@ -1313,16 +1229,16 @@ int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_cam
             i += nf;
         }
         // ... wait for the lanes and fetch every frame's status in one copy
-        if (lanes) for (int gl = 0; gl < GL; ++gl) SGS_HIP(ctx, hipStreamSynchronize(ctx->lanes[gl].stream));
+        if (lanes) for (int gl = 0; gl < GL; ++gl) SGS_HIP(ctx, hipStreamSynchronize(ctx->lanes[gl].stream.s));
         SGS_HIP(ctx, hipStreamSynchronize(stream));
         if ((rc = drain_lanes(ctx)) != SGS_OK) return rc;           // (frames issued outside this call)
-        SGS_HIP(ctx, hipMemcpy(ctx->h_status, ctx->d_status, sizeof(FrameStatus) * (size_t)cn, hipMemcpyDeviceToHost));
+        SGS_HIP(ctx, hipMemcpy(ctx->h_status.p, ctx->d_status.p, sizeof(FrameStatus) * (size_t)cn, hipMemcpyDeviceToHost));
         // The redo below goes through sgs_render, which takes ring slots of its own (from next_slot, two or more per
         // grow-and-retry) — i.e. slots of frames of THIS chunk that have not been looked at yet.  So every frame's
         // verdict and statistics are taken out of the ring before anything is re-rendered.
         bool over[kStatusRing];
         for (int i = 0; i < cn; ++i) {
-            over[i] = ctx->h_status[i].overflow != 0;
+            over[i] = ctx->h_status.p[i].overflow != 0;
             if (stats) collect(ctx, i, stats + c0 + i, scene->n, tl[i], px[i], scene->sh_rows, false);
         }
         ctx->next_slot = 0; ctx->pending_begin = 0; ctx->pending_count = 0;
@@ -1360,9 +1276,9 @@ int sgs_row_records(sgs_ctx* ctx, int64_t* out, int n_rows, int reset) {
     // (no device-wide synchronisation: a sweep's framebuffer exchange may be in flight on another stream and must not
     //  be waited for here; the frames the caller has synchronised are complete, and that is the contract)
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "row counters");
-    if (n_rows > 0) SGS_HIP(ctx, hipMemcpy(out, ctx->row_acc, sizeof(int64_t) * (size_t)n_rows, hipMemcpyDeviceToHost));
+    if (n_rows > 0) SGS_HIP(ctx, hipMemcpy(out, ctx->row_acc.p, sizeof(int64_t) * (size_t)n_rows, hipMemcpyDeviceToHost));
     if (reset) {
-        SGS_HIP(ctx, hipMemset(ctx->row_acc, 0, sizeof(unsigned long long) * SGS_MAX_ROWS));
+        SGS_HIP(ctx, hipMemset(ctx->row_acc.p, 0, sizeof(unsigned long long) * SGS_MAX_ROWS));
         SGS_HIP(ctx, hipStreamSynchronize(nullptr));      // (see ensure_tiles: the clear must not race later frames)
     }
     return SGS_OK;
@@ -1384,22 +1300,25 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     if (ctx->last_slot < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "no frame has been rendered");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     SGS_HIP(ctx, hipDeviceSynchronize());
-    const FrameStatus& s = ctx->h_status[ctx->last_slot];
+    const FrameStatus& s = ctx->h_status.p[ctx->last_slot];
     const Lane& L = ctx->lanes[ctx->last_lane];
     const int64_t n_chunks = (ctx->last_n + 63) / 64;
     const int64_t n_slots = n_chunks * 64;
+    // (a growth that failed since that frame has emptied what it was replacing)
+    if (!L.splats.holds(n_slots) || !L.vismask.holds(n_chunks) || !L.bigmask.holds(n_chunks) || !L.tile_offset.holds((int64_t)ctx->last_T + 1))
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "the last frame's intermediates are gone: an allocation has failed since");
     const void* src = nullptr;
     int64_t have = 0, elem = 0;
     switch (what) {
         case SGS_BUF_TILE_OFFSETS: have = ((int64_t)ctx->last_T + 1) * 4; break;       // every 8th sub-queue offset
-        case SGS_BUF_SORTED_SLOTS: src = L.sorted_out; have = (s.overflow || !L.sorted_out) ? 0 : (int64_t)s.d_total * 4; break;
+        case SGS_BUF_SORTED_SLOTS: src = L.sorted_out.p; have = (s.overflow || !L.sorted_out.p) ? 0 : (int64_t)s.d_total * 4; break;
         case SGS_BUF_SLOT_IDS: elem = 4; have = n_slots * elem; break;
         case SGS_BUF_SPLATS: elem = 48; have = n_slots * elem; break;          // the 12-word view documented in sage_gs.h
         case SGS_BUF_CHUNK_SKIPPED: have = n_chunks; break;
         case SGS_BUF_SCENE_GEOM: have = ctx->last_scene ? ctx->last_n * 11 * 4 : 0; break;
         case SGS_BUF_SCENE_SH: have = ctx->last_scene ? ctx->last_n * 3 * (ctx->last_scene->sh_degree + 1) * (ctx->last_scene->sh_degree + 1) * 4 : 0; break;
-        case 100: src = L.tile_prof; have = (int64_t)ctx->last_T * 8 * SGS_PROF_WORDS; break;    // profiling build only
-        case 101: src = L.bin_prof; have = (int64_t)SGS_BIN_BLOCKS * 64; break;  // profiling build only
+        case 100: src = L.tile_prof.p; have = (int64_t)ctx->last_T * 8 * SGS_PROF_WORDS; break;    // profiling build only
+        case 101: src = L.bin_prof.p; have = (int64_t)SGS_BIN_BLOCKS * 64; break;  // profiling build only
         default: SGS_FAIL(ctx, SGS_ERR_INVALID, "unknown buffer id %d", what);
     }
     const int64_t n = std::min(have, bytes);
@@ -1407,19 +1326,16 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     if (src) SGS_HIP(ctx, hipMemcpy(host_dst, src, (size_t)n, hipMemcpyDeviceToHost));
     if (what == SGS_BUF_TILE_OFFSETS) {
         const size_t cnt = (size_t)ctx->last_T + 1;
-        unsigned* tmp = (unsigned*)malloc(cnt * 4);
-        if (!tmp) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
-        hipError_t e = hipMemcpy(tmp, L.tile_offset, cnt * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(tmp); SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e)); }
+        std::vector<unsigned> tmp(cnt);
+        SGS_HIP(ctx, hipMemcpy(tmp.data(), L.tile_offset.p, cnt * 4, hipMemcpyDeviceToHost));
         // k_tile_scan writes the offsets of the band it rendered (and the band's end); outside it they are constant
         const unsigned total = tmp[(size_t)ctx->last_t_hi];
         for (int64_t i = 0; (i + 1) * 4 <= n; ++i)
             ((unsigned*)host_dst)[i] = i < ctx->last_t_lo ? 0u : i >= ctx->last_t_hi ? total : tmp[(size_t)i];
-        free(tmp);
     }
     if (what == SGS_BUF_SCENE_GEOM) {
         std::vector<float4> rows((size_t)n_slots * SGS_GEOM_ROWS);
-        hipError_t e = hipMemcpy(rows.data(), ctx->last_scene->geom, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(rows.data(), ctx->last_scene->geom.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
         if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
         float* dst = (float*)host_dst;
         for (int64_t p = 0; p < ctx->last_n; ++p) {
@@ -1436,10 +1352,10 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
         const sgs_scene* sc = ctx->last_scene;
         const int nf = 3 * (sc->sh_degree + 1) * (sc->sh_degree + 1), rows_n = sc->sh_rows;
         std::vector<float4> rows((size_t)n_slots * rows_n), g2((size_t)n_slots);
-        hipError_t e = hipMemcpy(rows.data(), sc->shq, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(rows.data(), sc->shq.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
         if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
         std::vector<float4> geo((size_t)n_slots * SGS_GEOM_ROWS);
-        if ((e = hipMemcpy(geo.data(), sc->geom, geo.size() * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
+        if ((e = hipMemcpy(geo.data(), sc->geom.p, geo.size() * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
         float* dst = (float*)host_dst;
         std::vector<unsigned> w((size_t)rows_n * 4);
         for (int64_t p = 0; p < ctx->last_n; ++p) {
@@ -1463,8 +1379,8 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     }
     if (what == SGS_BUF_CHUNK_SKIPPED) {
         std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks)), bm(vm.size());
-        hipError_t e = hipMemcpy(vm.data(), L.vismask, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(bm.data(), L.bigmask, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(bm.data(), L.bigmask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
         if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
         for (int64_t i = 0; i < n; ++i) ((unsigned char*)host_dst)[i] = vm[(size_t)i] == 0ull && bm[(size_t)i] == ~0ull;
     }
@@ -1472,7 +1388,7 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
         // device records (sgs_common.h: 64 B, conic pre-scaled for the composite, opacity also as an exponent offset) -> x,y,conic a,b | c,opacity,r,g | b,depth,rect01,rect23
         const int64_t cnt = n / elem;
         std::vector<Splat> tmp((size_t)std::max<int64_t>(1, cnt));
-        hipError_t e = hipMemcpy(tmp.data(), L.splats, (size_t)cnt * sizeof(Splat), hipMemcpyDeviceToHost);
+        hipError_t e = hipMemcpy(tmp.data(), L.splats.p, (size_t)cnt * sizeof(Splat), hipMemcpyDeviceToHost);
         if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
         const double l2e = 1.4426950408889634;
         for (int64_t i = 0; i < cnt; ++i) {
@@ -1491,13 +1407,11 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     if (elem) {
         // a splat lives at its Gaussian's index; the per-chunk visibility masks say which are live.
         // Dead slots are blanked (slot ids -> 0xFFFFFFFF, splats -> 0) so stale data cannot pass for live.
-        unsigned long long* vm = (unsigned long long*)malloc((size_t)std::max<int64_t>(1, n_chunks) * 8);
-        if (!vm) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
-        hipError_t e = hipMemcpy(vm, L.vismask, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(vm); SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e)); }
+        std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks));
+        SGS_HIP(ctx, hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost));
         char* dst = (char*)host_dst;
         // vismask is indexed by layout position; slots by original index
-        const unsigned* perm = ctx->last_scene ? ctx->last_scene->perm_host : nullptr;
+        const unsigned* perm = ctx->last_scene && !ctx->last_scene->perm_host.empty() ? ctx->last_scene->perm_host.data() : nullptr;
         std::vector<unsigned char> live((size_t)n_slots, 0);
         for (int64_t p = 0; p < ctx->last_n; ++p)
             if ((vm[p >> 6] >> (p & 63)) & 1ull) live[perm ? perm[p] : (size_t)p] = 1;
@@ -1505,7 +1419,6 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
             if (what == SGS_BUF_SLOT_IDS) ((unsigned*)dst)[i] = live[(size_t)i] ? (unsigned)i : 0xFFFFFFFFu;
             else if (!live[(size_t)i]) memset(dst + i * elem, 0, (size_t)elem);
         }
-        free(vm);
     }
     return have;
 }
@@ -1522,49 +1435,39 @@ int sgs_mesh_upload(sgs_ctx* ctx, int64_t n_vertices, const float* vertices, int
     if ((n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles)) SGS_FAIL(ctx, SGS_ERR_INVALID, "null input array");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     MeshScratch& M = ctx->mesh;
-    if (!M.d_st) {
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1)));
-        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&M.h_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1), 0));
-    }
-    sgs_mesh* m = new (std::nothrow) sgs_mesh;
+    int rc;
+    if ((rc = ensure_mesh_status(ctx)) != SGS_OK) return rc;
+    std::unique_ptr<sgs_mesh> m(new (std::nothrow) sgs_mesh);      // (released with its buffers by any return before *out)
     if (!m) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
     m->n_verts = n_vertices; m->n_tris = n_triangles;
     const size_t vb = (size_t)n_vertices * 12, tb = (size_t)n_triangles * 12;
-    hipError_t e = hipSuccess;
-    if ((e = hipMalloc(reinterpret_cast<void**>(&m->verts), vb ? vb : 16)) != hipSuccess ||
-        (e = hipMalloc(reinterpret_cast<void**>(&m->tris), tb ? tb : 16)) != hipSuccess ||
-        (vb && (e = hipMemcpy(m->verts, vertices, vb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess) ||
-        (tb && (e = hipMemcpy(m->tris, triangles, tb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess)) {
-        sgs_mesh_free(ctx, m);
-        SGS_FAIL(ctx, e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "mesh upload: %s", hipGetErrorString(e));
-    }
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    SGS_HIP(ctx, m->verts.grow(std::max<int64_t>(3 * n_vertices, 4)));
+    SGS_HIP(ctx, m->tris.grow(std::max<int64_t>(3 * n_triangles, 4)));
+    if (vb) SGS_HIP(ctx, hipMemcpy(m->verts.p, vertices, vb, kind));
+    if (tb) SGS_HIP(ctx, hipMemcpy(m->tris.p, triangles, tb, kind));
     // the checks run on the device (the caller's arrays may live there): a status word, read back once
-    unsigned* bad = &M.d_st[SGS_MESH_MAX_GROUP].n_visible;
+    unsigned* bad = &M.d_st.p[SGS_MESH_MAX_GROUP].n_visible;
     SGS_HIP(ctx, hipMemset(bad, 0, sizeof(unsigned)));
     const long long work = 3 * std::max<long long>(n_vertices, n_triangles);
+    const float* const d_verts = m->verts.p;
+    const int* const d_tris = m->tris.p;
     if (work > 0)
         hipLaunchKernelGGL(sgs::k_mesh_validate, dim3((unsigned)std::min<long long>((work + 255) / 256, 4096)), dim3(256), 0, nullptr,
-                           (long long)n_vertices, (const float*)m->verts, (long long)n_triangles, (const int*)m->tris, bad);
+                           (long long)n_vertices, d_verts, (long long)n_triangles, d_tris, bad);
     unsigned flags = 0;
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost)) != hipSuccess) {
-        sgs_mesh_free(ctx, m);
-        SGS_FAIL(ctx, SGS_ERR_HIP, "mesh upload: %s", hipGetErrorString(e));
-    }
-    if (flags) {
-        sgs_mesh_free(ctx, m);
+    SGS_HIP(ctx, hipGetLastError());
+    SGS_HIP(ctx, hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost));
+    if (flags)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh upload: %s%s", (flags & 1u) ? "non-finite vertex coordinates " : "",
                  (flags & 2u) ? "triangle indices outside [0, n_vertices)" : "");
-    }
-    *out = m;
+    *out = m.release();
     return SGS_OK;
 }
 
 int sgs_mesh_free(sgs_ctx* ctx, sgs_mesh* mesh) {
     if (!mesh) return SGS_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipDeviceSynchronize(); }
-    if (mesh->verts) (void)hipFree(mesh->verts);
-    if (mesh->tris) (void)hipFree(mesh->tris);
-    if (mesh->labels) (void)hipFree(mesh->labels);
     delete mesh;
     return SGS_OK;
 }
@@ -1574,32 +1477,23 @@ int sgs_mesh_set_labels(sgs_ctx* ctx, sgs_mesh* mesh, const int32_t* labels, int
     if (!mesh) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh is NULL");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     SGS_HIP(ctx, hipDeviceSynchronize());                    // no frame still reads the labels that are replaced
-    int* fresh = nullptr;
+    DevBuf<int> fresh;                                       // (the mesh keeps its previous labels unless these pass)
     if (labels && mesh->n_tris > 0) {
-        const size_t lb = (size_t)mesh->n_tris * sizeof(int);
-        hipError_t e = hipSuccess;
-        if ((e = hipMalloc(reinterpret_cast<void**>(&fresh), lb)) != hipSuccess ||
-            (e = hipMemcpy(fresh, labels, lb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice)) != hipSuccess) {
-            if (fresh) (void)hipFree(fresh);
-            SGS_FAIL(ctx, e == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "mesh labels: %s", hipGetErrorString(e));
-        }
+        SGS_HIP(ctx, fresh.grow(mesh->n_tris));
+        SGS_HIP(ctx, hipMemcpy(fresh.p, labels, (size_t)mesh->n_tris * sizeof(int), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         // checked on the device (the caller's array may live there), through the upload's status word
-        if (!ctx->mesh.d_st) { (void)hipFree(fresh); SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: the mesh was not uploaded through this context"); }
-        unsigned* bad = &ctx->mesh.d_st[SGS_MESH_MAX_GROUP].n_visible;
+        if (!ctx->mesh.d_st.p) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: the mesh was not uploaded through this context");
+        unsigned* bad = &ctx->mesh.d_st.p[SGS_MESH_MAX_GROUP].n_visible;
         unsigned flags = 0;
-        if ((e = hipMemset(bad, 0, sizeof(unsigned))) == hipSuccess) {
-            hipLaunchKernelGGL(sgs::k_mesh_validate_labels, dim3((unsigned)std::min<long long>((mesh->n_tris + 255) / 256, 4096)), dim3(256), 0,
-                               nullptr, (long long)mesh->n_tris, (const int*)fresh, bad);
-            if ((e = hipGetLastError()) == hipSuccess) e = hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess || flags) {
-            (void)hipFree(fresh);
-            if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "mesh labels: %s", hipGetErrorString(e));
-            SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: labels outside [0, INT32_MAX - 1] (the mesh keeps its previous labels)");
-        }
+        SGS_HIP(ctx, hipMemset(bad, 0, sizeof(unsigned)));
+        const int* const d_labels = fresh.p;
+        hipLaunchKernelGGL(sgs::k_mesh_validate_labels, dim3((unsigned)std::min<long long>((mesh->n_tris + 255) / 256, 4096)), dim3(256), 0,
+                           nullptr, (long long)mesh->n_tris, d_labels, bad);
+        SGS_HIP(ctx, hipGetLastError());
+        SGS_HIP(ctx, hipMemcpy(&flags, bad, sizeof flags, hipMemcpyDeviceToHost));
+        if (flags) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh labels: labels outside [0, INT32_MAX - 1] (the mesh keeps its previous labels)");
     }
-    if (mesh->labels) (void)hipFree(mesh->labels);
-    mesh->labels = fresh;
+    mesh->labels = std::move(fresh);
     return SGS_OK;
 }
 
@@ -1608,11 +1502,10 @@ int sgs_mesh_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
     if (max_records < 1 || max_records > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh record capacity %lld outside [1, 2^32)", (long long)max_records);
     MeshScratch& M = ctx->mesh;
     M.cap_wanted = max_records;
-    if (M.list && M.list_cap != max_records) {               // reallocated at the requested size by the next mesh frame
+    if (M.list.p && M.list.cap != max_records) {             // reallocated at the requested size by the next mesh frame
         SGS_HIP(ctx, hipSetDevice(ctx->device));
         SGS_HIP(ctx, hipDeviceSynchronize());
-        (void)hipFree(M.list);
-        M.list = nullptr; M.list_cap = 0;
+        M.list.reset();
     }
     return SGS_OK;
 }
@@ -1620,16 +1513,6 @@ int sgs_mesh_set_record_capacity(sgs_ctx* ctx, int64_t max_records) {
 }  // extern "C"
 
 namespace {
-
-template <class T>
-int mesh_grow(sgs_ctx* ctx, T*& p, int64_t& cap, int64_t want, int64_t count_per) {
-    if (want <= cap && p) return SGS_OK;
-    const int64_t c = std::max<int64_t>(want, 1);
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&p), (size_t)c * (size_t)count_per * sizeof(T)));
-    cap = c;
-    return SGS_OK;
-}
 
 // Frames [0, n) of cams: groups of up to SGS_MESH_MAX_GROUP frames, each five launches and one synchronisation; frame i is written at
 // out + i * frame_stride.  stats: n entries (nullable).  out_id != nullptr: the id frames (sgs_render_mesh_ids*: k_mesh_ids as the last
@@ -1644,21 +1527,14 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
     if (cfg.flags & (SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED)) SGS_FAIL(ctx, SGS_ERR_INVALID, "mesh depth is synchronous only: SGS_FLAG_ASYNC / SGS_FLAG_PIPELINED are refused");
     if (!(cfg.near_z > 0.f) || !(cfg.far_z > cfg.near_z)) SGS_FAIL(ctx, SGS_ERR_INVALID, "need 0 < near_z < far_z (got %g, %g)", cfg.near_z, cfg.far_z);
     const int W = cams[0].width, H = cams[0].height;
-    if (W <= 0 || H <= 0 || W > 65535 * SGS_TILE || H > 65535 * SGS_TILE) SGS_FAIL(ctx, SGS_ERR_INVALID, "bad resolution %dx%d", W, H);
     for (int i = 0; i < n; ++i) {
         const sgs_camera* c = &cams[i];
         if (c->width != W || c->height != H) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: %dx%d, camera 0: %dx%d (one resolution per call)", i, c->width, c->height, W, H);
-        if (!(c->fx > 0.f) || !(c->fy > 0.f)) SGS_FAIL(ctx, SGS_ERR_INVALID, "focal lengths must be positive");
         if (!std::isfinite(c->cx) || !std::isfinite(c->cy)) SGS_FAIL(ctx, SGS_ERR_INVALID, "principal point must be finite");
-        const float* V = c->view;
         for (int k = 0; k < 12; ++k)
-            if (!std::isfinite(V[k])) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: non-finite view", i);
-        for (int r = 0; r < 3; ++r)
-            for (int q = r; q < 3; ++q) {
-                const double d = (double)V[4 * r] * V[4 * q] + (double)V[4 * r + 1] * V[4 * q + 1] + (double)V[4 * r + 2] * V[4 * q + 2];
-                if (!(std::fabs(d - (r == q ? 1.0 : 0.0)) < 1.0e-5))
-                    SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: view is not rigid: rows %d.%d of its 3x3 give %g", i, r, q, d);
-            }
+            if (!std::isfinite(c->view[k])) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: non-finite view", i);
+        char why[160];
+        if (check_camera(*c, why, sizeof why)) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera %d: %s", i, why);
     }
     const int gy = (H + SGS_TILE - 1) / SGS_TILE, gx = (W + SGS_TILE - 1) / SGS_TILE;
     if (row_end < 0 || row_end > gy) row_end = gy;
@@ -1666,41 +1542,24 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
     if (row_begin > row_end) SGS_FAIL(ctx, SGS_ERR_INVALID, "tile_row_begin %d > tile_row_end %d", row_begin, row_end);
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     MeshScratch& M = ctx->mesh;
-    if (!M.d_st) {
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.d_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1)));
-        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&M.h_st), sizeof(sgs::MeshStatus) * (SGS_MESH_MAX_GROUP + 1), 0));
-    }
+    int rc;
+    if ((rc = ensure_mesh_status(ctx)) != SGS_OK) return rc;
     const bool timed = (cfg.flags & SGS_FLAG_TIMING) != 0;
-    if (timed && !M.ev[0]) { SGS_HIP(ctx, hipEventCreate(&M.ev[0])); SGS_HIP(ctx, hipEventCreate(&M.ev[1])); }
+    if (timed) { SGS_HIP(ctx, M.ev[0].create()); SGS_HIP(ctx, M.ev[1].create()); }
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const int n_tiles = (row_end - row_begin) * gx;
     const int64_t F = mesh->n_tris;
     for (int g0 = 0; g0 < n; g0 += SGS_MESH_MAX_GROUP) {
         const int nf = std::min(SGS_MESH_MAX_GROUP, n - g0);
-        int64_t dummy = 0;
-        int rc;
-        if (M.slot_cap < F * nf || !M.rec) {
-            if ((rc = mesh_grow(ctx, M.rec, dummy, F * nf, 4)) != SGS_OK) return rc;
-            dummy = 0;
-            if ((rc = mesh_grow(ctx, M.rect, dummy, F * nf, 1)) != SGS_OK) return rc;
-            dummy = 0;
-            if ((rc = mesh_grow(ctx, M.big, dummy, F * nf, 1)) != SGS_OK) return rc;
-            M.slot_cap = std::max<int64_t>(F * nf, 1);
-        }
-        if (M.tile_cap < (int64_t)n_tiles * nf + nf || !M.counts) {
-            dummy = 0;
-            if ((rc = mesh_grow(ctx, M.counts, dummy, (int64_t)n_tiles * nf + nf, 1)) != SGS_OK) return rc;
-            dummy = 0;
-            if ((rc = mesh_grow(ctx, M.offs, dummy, (int64_t)n_tiles * nf + nf, 1)) != SGS_OK) return rc;
-            M.tile_cap = (int64_t)n_tiles * nf + nf;
-        }
+        const int64_t slots = std::max<int64_t>(F * nf, 1), tiles = (int64_t)n_tiles * nf + nf;
+        SGS_HIP(ctx, M.rec.grow(4 * slots));
+        SGS_HIP(ctx, M.rect.grow(slots));
+        SGS_HIP(ctx, M.big.grow(slots));
+        SGS_HIP(ctx, M.counts.grow(tiles));
+        SGS_HIP(ctx, M.offs.grow(tiles));
         int retries = 0;
         for (;;) {
-            if (M.list_cap < M.cap_wanted || !M.list) {
-                if (M.list) { (void)hipFree(M.list); M.list = nullptr; M.list_cap = 0; }
-                SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&M.list), (size_t)M.cap_wanted * sizeof(unsigned)));
-                M.list_cap = M.cap_wanted;
-            }
+            SGS_HIP(ctx, M.list.grow(M.cap_wanted));
             sgs::MeshGroup G;
             memset(&G, 0, sizeof G);
             for (int f = 0; f < nf; ++f) {
@@ -1712,13 +1571,13 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
                 P.out = out ? out + (int64_t)(g0 + f) * frame_stride : nullptr;
                 P.out_id = ids ? out_id + (int64_t)(g0 + f) * frame_stride : nullptr;
             }
-            G.nf = nf; G.n_tiles = n_tiles; G.n_tris = F; G.cap = M.list_cap;
-            G.verts = mesh->verts; G.tris = mesh->tris; G.labels = mesh->labels;
-            G.rec = M.rec; G.rect = M.rect; G.big = M.big; G.counts = M.counts; G.offs = M.offs; G.list = M.list; G.st = M.d_st;
-            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[0], stream));
-            SGS_HIP(ctx, hipMemsetAsync(M.d_st, 0, sizeof(sgs::MeshStatus) * nf, stream));
+            G.nf = nf; G.n_tiles = n_tiles; G.n_tris = F; G.cap = M.list.cap;
+            G.verts = mesh->verts.p; G.tris = mesh->tris.p; G.labels = mesh->labels.p;
+            G.rec = M.rec.p; G.rect = M.rect.p; G.big = M.big.p; G.counts = M.counts.p; G.offs = M.offs.p; G.list = M.list.p; G.st = M.d_st.p;
+            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[0].e, stream));
+            SGS_HIP(ctx, hipMemsetAsync(M.d_st.p, 0, sizeof(sgs::MeshStatus) * nf, stream));
             if (n_tiles > 0) {
-                SGS_HIP(ctx, hipMemsetAsync(M.counts, 0, sizeof(unsigned) * (size_t)n_tiles * nf, stream));
+                SGS_HIP(ctx, hipMemsetAsync(M.counts.p, 0, sizeof(unsigned) * (size_t)n_tiles * nf, stream));
                 if (F > 0) {
                     hipLaunchKernelGGL(sgs::k_mesh_setup, dim3((unsigned)((F + 255) / 256), (unsigned)nf), dim3(256), 0, stream, G);
                     const unsigned bin_grid = (unsigned)std::min<int64_t>((F + 255) / 256, SGS_MESH_BIN_BLOCKS);
@@ -1731,21 +1590,21 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
                 if (ids) hipLaunchKernelGGL(sgs::k_mesh_ids, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
                 else hipLaunchKernelGGL(sgs::k_mesh_depth, dim3((unsigned)n_tiles, (unsigned)nf), dim3(256), 0, stream, G);
             }
-            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[1], stream));
+            if (timed) SGS_HIP(ctx, hipEventRecord(M.ev[1].e, stream));
             SGS_HIP(ctx, hipGetLastError());
-            SGS_HIP(ctx, hipMemcpyAsync(M.h_st, M.d_st, sizeof(sgs::MeshStatus) * nf, hipMemcpyDeviceToHost, stream));
+            SGS_HIP(ctx, hipMemcpyAsync(M.h_st.p, M.d_st.p, sizeof(sgs::MeshStatus) * nf, hipMemcpyDeviceToHost, stream));
             SGS_HIP(ctx, hipStreamSynchronize(stream));
             int64_t total = 0;
-            for (int f = 0; f < nf; ++f) total += M.h_st[f].d_total;
-            if (total <= M.list_cap) {
+            for (int f = 0; f < nf; ++f) total += M.h_st.p[f].d_total;
+            if (total <= M.list.cap) {
                 float ms = 0.f;
-                if (timed) SGS_HIP(ctx, hipEventElapsedTime(&ms, M.ev[0], M.ev[1]));
+                if (timed) SGS_HIP(ctx, hipEventElapsedTime(&ms, M.ev[0].e, M.ev[1].e));
                 for (int f = 0; f < nf && stats; ++f) {
                     sgs_stats& s = stats[g0 + f];
                     memset(&s, 0, sizeof s);
-                    s.n_visible = M.h_st[f].n_visible;
-                    s.d_total = M.h_st[f].d_total;
-                    s.max_tile_len = (int32_t)M.h_st[f].max_tile_len;
+                    s.n_visible = M.h_st.p[f].n_visible;
+                    s.d_total = M.h_st.p[f].d_total;
+                    s.max_tile_len = (int32_t)M.h_st.p[f].max_tile_len;
                     s.n_tiles = n_tiles;
                     s.n_pixels = (int64_t)W * (std::min(H, SGS_TILE * row_end) - SGS_TILE * row_begin);
                     s.retries = retries;
@@ -1755,7 +1614,7 @@ int mesh_frames(sgs_ctx* ctx, const sgs_mesh* mesh, const sgs_camera* cams, int 
             }
             // the record buffer overflowed: grow it to fit and render the group again
             if (++retries > 4) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "mesh record buffer still too small after 4 retries");
-            M.cap_wanted = std::min<int64_t>(std::max<int64_t>(total + total / 4, M.list_cap * 2), kMaxRecords);
+            M.cap_wanted = std::min<int64_t>(std::max<int64_t>(total + total / 4, M.list.cap * 2), kMaxRecords);
             if (total > kMaxRecords) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "mesh depth: %lld records exceed 2^32", (long long)total);
         }
     }
@@ -1822,24 +1681,24 @@ int check_file_args(sgs_ctx* ctx, const char* who, const char* bad_params, int n
 int ready_file_sink(sgs_ctx* ctx, FileScratch& F, int64_t n_units, uint8_t* out, int64_t out_capacity, int64_t* out_offsets, int64_t* out_sizes,
                     sgs::FileSink& K) {
     SGS_HIP(ctx, hipSetDevice(ctx->device));
-    if (!F.h_status) {
-        SGS_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&F.h_status), 2 * sizeof(long long), 0));
-        F.h_status[0] = F.h_status[1] = 0;
+    if (!F.h_status.p) {
+        SGS_HIP(ctx, F.h_status.grow(2));
+        F.h_status.p[0] = F.h_status.p[1] = 0;
     }
     if (n_units == 0) {
-        F.h_status[0] = 0; F.h_status[1] = out_capacity;
+        F.h_status.p[0] = 0; F.h_status.p[1] = out_capacity;
         return SGS_OK;
     }
-    const int rc = reserve(ctx, F.offs, F.offs_cap, n_units + 1);
-    if (rc != SGS_OK) return rc;
-    K = {F.offs, out, out_capacity, reinterpret_cast<long long*>(out_offsets), reinterpret_cast<long long*>(out_sizes), F.h_status};
+    // (the scratch arrays of the encoders and the resize grow geometrically; releasing the old array waits for the work that still uses it)
+    SGS_HIP(ctx, F.offs.grow(n_units + 1, Grow::geometric));
+    K = {F.offs.p, out, out_capacity, reinterpret_cast<long long*>(out_offsets), reinterpret_cast<long long*>(out_sizes), F.h_status.p};
     return SGS_OK;
 }
 
 // sgs_jpeg_status / sgs_png_status: the status words of the encoder's most recent call (F: nullptr without a context).
 int file_status(sgs_ctx* ctx, const char* who, const FileScratch* F, int64_t* bytes_needed) {
     if (!ctx) return SGS_ERR_INVALID;
-    const long long need = F->h_status ? F->h_status[0] : 0, cap = F->h_status ? F->h_status[1] : 0;
+    const long long need = F->h_status.p ? F->h_status.p[0] : 0, cap = F->h_status.p ? F->h_status.p[1] : 0;
     if (bytes_needed) *bytes_needed = need;
     if (need > cap) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "%s: the files take %lld bytes, out_capacity was %lld", who, need, cap);
     return SGS_OK;
@@ -1896,25 +1755,23 @@ int sgs_encode_jpeg(sgs_ctx* ctx, const float* rgb, int width, int height, int n
     if ((rc = ready_file_sink(ctx, Z.files, n, out, out_capacity, out_offsets, out_sizes, J.sink)) != SGS_OK || n == 0) return rc;
     sgs::JpegTables* tab = nullptr;
     for (const JpegScratch::Entry& e : Z.tables)
-        if (e.width == width && e.height == height && e.quality == params->quality && e.s420 == g.s420) tab = e.dev;
+        if (e.width == width && e.height == height && e.quality == params->quality && e.s420 == g.s420) tab = e.dev.p;
     if (!tab) {
         sgs::JpegTables T;
         memset(&T, 0, sizeof T);
         sgs::jpeg::build_tables(T, width, height, params->quality, g.s420 != 0, g.ri);
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&tab), sizeof T));
-        const hipError_t e = hipMemcpy(tab, &T, sizeof T, hipMemcpyHostToDevice);      // (synchronous: T is on this stack)
-        if (e != hipSuccess) {
-            (void)hipFree(tab);
-            SGS_FAIL(ctx, SGS_ERR_HIP, "sgs_encode_jpeg: copying the tables: %s", hipGetErrorString(e));
-        }
+        DevBuf<sgs::JpegTables> fresh;
+        SGS_HIP(ctx, fresh.grow(1));
+        SGS_HIP(ctx, hipMemcpy(fresh.p, &T, sizeof T, hipMemcpyHostToDevice));         // (synchronous: T is on this stack)
+        tab = fresh.p;
         // only a filled table is remembered.  The list is never trimmed: 4.3 KB of device memory per distinct (width, height, quality,
         // subsampling) a context has encoded, until sgs_destroy — a handful in any real caller
-        Z.tables.push_back({width, height, params->quality, g.s420, tab});
+        Z.tables.push_back({width, height, params->quality, g.s420, std::move(fresh)});
     }
-    if ((rc = reserve(ctx, Z.sizes, Z.sizes_cap, n)) != SGS_OK) return rc;
+    SGS_HIP(ctx, Z.sizes.grow(n, Grow::geometric));
     J.rgb = rgb; J.frame_stride = rgb_frame_stride; J.width = width; J.height = height; J.s420 = g.s420;
     J.mcus_x = g.mcus_x; J.n_mcu = g.n_mcu; J.ri = g.ri; J.n_int = g.n_int; J.n_frames = n_frames;
-    J.tab = tab; J.sizes = Z.sizes;
+    J.tab = tab; J.sizes = Z.sizes.p;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipLaunchKernelGGL(sgs::k_jpeg_intervals<false>, dim3((unsigned)n), dim3(64), 0, st, J);
     hipLaunchKernelGGL(sgs::k_jpeg_scan, dim3(1), dim3(SGS_JPEG_SCAN_THREADS), 0, st, J);
@@ -1992,13 +1849,13 @@ int sgs_encode_png(sgs_ctx* ctx, const float* src, int width, int height, int n_
     memset(&J, 0, sizeof J);
     if ((rc = ready_file_sink(ctx, Z.files, n, out, out_capacity, out_offsets, out_sizes, J.sink)) != SGS_OK || n == 0) return rc;
     const int64_t slot = (((int64_t)std::min(g.rows_per_strip, height) * (g.row_bytes + 1) + 16) + 15) & ~(int64_t)15;
-    if ((rc = reserve(ctx, Z.rec, Z.rec_cap, n)) != SGS_OK) return rc;
-    if ((rc = reserve(ctx, Z.slots, Z.slot_bytes, n * slot)) != SGS_OK) return rc;
-    if ((rc = reserve(ctx, Z.adler, Z.frame_cap, n_frames)) != SGS_OK) return rc;
+    SGS_HIP(ctx, Z.rec.grow(n, Grow::geometric));
+    SGS_HIP(ctx, Z.slots.grow(n * slot, Grow::geometric));
+    SGS_HIP(ctx, Z.adler.grow(n_frames, Grow::geometric));
     J.src = src; J.frame_stride = src_frame_stride; J.width = width; J.height = height; J.depth16 = g.depth16;
     J.scale = params->depth_scale; J.dmax = params->depth_max; J.bpp = g.bpp; J.row_bytes = g.row_bytes;
     J.rows_per_strip = g.rows_per_strip; J.n_strips = g.n_strips; J.n_frames = n_frames;
-    J.slot = slot; J.slots = Z.slots; J.rec = Z.rec; J.adler = Z.adler;
+    J.slot = slot; J.slots = Z.slots.p; J.rec = Z.rec.p; J.adler = Z.adler.p;
     sgs::png::build_head(J.head, width, height, g.depth16 != 0);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipLaunchKernelGGL(sgs::k_png_strips, dim3((unsigned)n), dim3(64), 0, st, J);
@@ -2028,24 +1885,19 @@ int resize_axis(sgs_ctx* ctx, int in, int out, int filter, int format, sgs::Resi
         const bool fixed = format == SGS_RESIZE_RGB8;
         sgs::resize::AxisTable T;
         sgs::resize::build_axis(in, out, fixed, T);
-        ResizeScratch::Entry e = {in, out, filter, format, T.ksize, nullptr, nullptr};
+        ResizeScratch::Entry e = {in, out, filter, format, T.ksize, {}, {}};
         const void* w = fixed ? static_cast<const void*>(T.ki.data()) : static_cast<const void*>(T.kd.data());
-        const size_t w_bytes = fixed ? T.ki.size() * sizeof(int) : T.kd.size() * sizeof(double), b_bytes = T.bounds.size() * sizeof(int);
-        SGS_HIP(ctx, hipMalloc(reinterpret_cast<void**>(&e.bounds), b_bytes));
-        hipError_t err = hipMalloc(&e.weights, w_bytes);
-        if (err == hipSuccess) err = hipMemcpy(e.bounds, T.bounds.data(), b_bytes, hipMemcpyHostToDevice);
-        if (err == hipSuccess) err = hipMemcpy(e.weights, w, w_bytes, hipMemcpyHostToDevice);
-        if (err != hipSuccess) {
-            (void)hipFree(e.bounds);
-            if (e.weights) (void)hipFree(e.weights);
-            SGS_FAIL(ctx, err == hipErrorOutOfMemory ? SGS_ERR_OOM : SGS_ERR_HIP, "sgs_resize: the tap table of %d -> %d: %s", in, out, hipGetErrorString(err));
-        }
-        Z.tables.push_back(e);                 // only a filled table is remembered; never trimmed: a few KB per pair of sizes a context has seen
+        const size_t w_bytes = fixed ? T.ki.size() * sizeof(int) : T.kd.size() * sizeof(double);
+        SGS_HIP(ctx, e.bounds.grow((int64_t)T.bounds.size()));
+        SGS_HIP(ctx, e.weights.grow((int64_t)w_bytes));
+        SGS_HIP(ctx, hipMemcpy(e.bounds.p, T.bounds.data(), T.bounds.size() * sizeof(int), hipMemcpyHostToDevice));
+        SGS_HIP(ctx, hipMemcpy(e.weights.p, w, w_bytes, hipMemcpyHostToDevice));
+        Z.tables.push_back(std::move(e));      // only a filled table is remembered; never trimmed: a few KB per pair of sizes a context has seen
         hit = &Z.tables.back();
     }
-    A.bounds = hit->bounds; A.ksize = hit->ksize;
-    A.ki = format == SGS_RESIZE_RGB8 ? static_cast<const int*>(hit->weights) : nullptr;
-    A.kd = format == SGS_RESIZE_RGB8 ? nullptr : static_cast<const double*>(hit->weights);
+    A.bounds = hit->bounds.p; A.ksize = hit->ksize;
+    A.ki = format == SGS_RESIZE_RGB8 ? reinterpret_cast<const int*>(hit->weights.p) : nullptr;
+    A.kd = format == SGS_RESIZE_RGB8 ? nullptr : reinterpret_cast<const double*>(hit->weights.p);
     return SGS_OK;
 }
 
@@ -2115,8 +1967,8 @@ int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_fram
     if (do_h && (rc = resize_axis(ctx, J.W, J.w, p->filter, p->format, J.ax)) != SGS_OK) return rc;
     if (do_v && (rc = resize_axis(ctx, J.H, J.h, p->filter, p->format, J.ay)) != SGS_OK) return rc;
     const int kMaxFrames = 65535;              // gridDim.y
-    if (do_h && do_v && (rc = reserve(ctx, ctx->resize.mid, ctx->resize.mid_cap, (int64_t)std::min(n_frames, kMaxFrames) * J.H * J.w)) != SGS_OK) return rc;
-    J.mid = ctx->resize.mid;
+    if (do_h && do_v) SGS_HIP(ctx, ctx->resize.mid.grow((int64_t)std::min(n_frames, kMaxFrames) * J.H * J.w, Grow::geometric));
+    J.mid = ctx->resize.mid.p;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     for (int f0 = 0; f0 < n_frames; f0 += kMaxFrames) {
         J.src = src + (int64_t)f0 * src_frame_stride; J.dst = dst + (int64_t)f0 * dst_frame_stride;

@@ -12,7 +12,8 @@ mkdir -p $TMP/pkg/csrc $TMP/include
 if [ "$REV" = WORK ]; then
   cp $ROOT/sage-3d_official_amd/csrc/* $TMP/pkg/csrc/; cp $ROOT/include/sage_gs.h $TMP/include/
 else
-  for f in sgs_api.hip sgs_kernels.h sgs_common.h; do git -C $ROOT show $REV:sage-3d_official_amd/csrc/$f > $TMP/pkg/csrc/$f; done
+  # (every file the revision has there: sgs_api.hip, the kernel headers, sgs_own.h from the revision that introduced it on)
+  for f in $(git -C $ROOT ls-tree --name-only $REV sage-3d_official_amd/csrc/ | xargs -n1 basename); do git -C $ROOT show $REV:sage-3d_official_amd/csrc/$f > $TMP/pkg/csrc/$f; done
   git -C $ROOT show $REV:include/sage_gs.h > $TMP/include/sage_gs.h
 fi
 (cd $TMP/pkg && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -fno-slp-vectorize "$@" -shared csrc/sgs_api.hip -o $OUT/$NAME.so)

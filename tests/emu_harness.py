@@ -19,7 +19,7 @@ PKG = os.path.join(ROOT, "sage-3d_official_amd")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 EMU_LIB = os.path.join(EMU_DIR, "_build", "libsage_gs_emu.so")
 KERNEL_SRCS = ("sgs_api.hip", "sgs_kernels.h", "sgs_mesh.h", "sgs_jpeg.h", "sgs_png.h", "sgs_encode.h", "sgs_resize.h", "sgs_objects.h",
-               "sgs_common.h")                                                 # csrc/ files the library is built from
+               "sgs_common.h", "sgs_own.h")                                                 # csrc/ files the library is built from
 SRCS = [os.path.join(PKG, "csrc", n) for n in KERNEL_SRCS] + \
        [os.path.join(EMU_DIR, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "sage_gs.h")]
 

@@ -358,13 +358,28 @@ static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipGetLastError() { return hipSuccess; }
+// Test-only allocation-failure hook (tests/host_alloc_walk.cpp): hipMalloc and hipHostMalloc count themselves, and the alloc_fail_in-th
+// of them from now (0 = the next one) returns hipErrorOutOfMemory, once; -1 = never.  Only the emulator has it.
+namespace hipemu {
+inline long long alloc_fail_in = -1;
+inline long long alloc_count = 0;
+inline bool alloc_refused() {
+    ++alloc_count;
+    return alloc_fail_in >= 0 && alloc_fail_in-- == 0;
+}
+}  // namespace hipemu
 static inline hipError_t hipMalloc(void** p, size_t n) {
+    if (hipemu::alloc_refused()) { *p = nullptr; return hipErrorOutOfMemory; }
     *p = aligned_alloc(256, ((n + 255) / 256) * 256);
     if (*p) memset(*p, 0xCD, n);            // poison: uninitialised reads show up
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) {
+    if (hipemu::alloc_refused()) { *p = nullptr; return hipErrorOutOfMemory; }
+    *p = calloc(1, n ? n : 1);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }

@@ -1220,3 +1220,81 @@ def test_compressed_payload_known_answer_vectors_on_the_device(drv):
     with pytest.raises(ValueError, match="sh_decode"):
         drv.r.upload_compressed(chunks, packed, shb, 3)
     drv.r.upload_compressed(chunks, packed, None, 0).free()            # degree 0: no coefficient bytes, nothing to specify
+
+
+# ---- regrowth of the library's own buffers: a frame does not depend on what its context rendered before ------------------------------
+def test_regrown_intermediates_leave_frames_unchanged():
+    """One Renderer through every regrowth of a lane's intermediates — the tile arrays (64x48 -> 320x240), the splat arrays (2 000 ->
+    20 000 Gaussians), the records (a capacity the larger frame overflows: the synchronous retry grows them) — and back to the first
+    frame, which must be bit for bit what it was, and what a fresh Renderer renders."""
+    from sage_gs import Renderer, scenes
+    small, large = scenes.make_room(2_000, seed=5), scenes.make_room(20_000, seed=6)
+    cam_a = scenes.room_cameras(small, 64, 48, n_positions=1, n_yaw=1, seed=5)[0]
+    cam_b = scenes.room_cameras(small, 320, 240, n_positions=1, n_yaw=1, seed=5)[0]
+    cam_c = scenes.room_cameras(large, 64, 48, n_positions=1, n_yaw=1, seed=6)[0]
+    r = Renderer("cuda:0")
+    try:
+        s_small, s_large = r.upload(scenes.to_gaussians(small, "cuda:0")), r.upload(scenes.to_gaussians(large, "cuda:0"))
+        a0 = r.render(cam_a, s_small).cpu().numpy()
+        b0 = r.render(cam_b, s_small, stats=True).cpu().numpy()
+        d_b = int(r.last_stats["d_total"])
+        assert d_b > 2048, d_b                                   # (frame B's records do not fit the capacity set below)
+        c0 = r.render(cam_c, s_large).cpu().numpy()
+        r.set_record_capacity(2048)
+        b1 = r.render(cam_b, s_small, stats=True).cpu().numpy()
+        assert r.last_stats["retries"] >= 1, r.last_stats
+        a1 = r.render(cam_a, s_small).cpu().numpy()
+        c1 = r.render(cam_c, s_large).cpu().numpy()
+        assert np.isfinite(a0).all() and a0.max() > 0.0
+        assert (a1 == a0).all() and (b1 == b0).all() and (c1 == c0).all()
+    finally:
+        r.close()
+    fresh = Renderer("cuda:0")
+    try:
+        assert (fresh.render(cam_a, fresh.upload(scenes.to_gaussians(small, "cuda:0"))).cpu().numpy() == a0).all()
+    finally:
+        fresh.close()
+
+
+def test_regrown_scratch_of_the_mesh_path_the_encoders_and_the_resize():
+    """The same for the other owners of scratch: mesh depth and ids through 64x48 -> 320x240 -> 64x48 and a record buffer of one entry
+    (the retry grows it); JPEG and PNG files of 1, then 5, then 1 frames (the first file's bytes stay); a both-pass resize at two sizes."""
+    import torch
+    from sage_gs import Renderer, scenes
+    v, t, part = scenes.make_room_mesh_parts(2_000, seed=3)
+    room = scenes.make_room(2_000, seed=5)
+    cam_a = scenes.room_cameras(room, 64, 48, n_positions=1, n_yaw=1, seed=5)[0]
+    cam_b = scenes.room_cameras(room, 320, 240, n_positions=1, n_yaw=1, seed=5)[0]
+    r = Renderer("cuda:0")
+    try:
+        mesh = r.upload_mesh(v, t, labels=part)
+        d0 = r.render_mesh_depth(cam_a, mesh).cpu().numpy()
+        i0, e0 = [x.cpu().numpy() for x in r.render_mesh_ids(cam_a, mesh, return_depth=True)]
+        D0 = r.render_mesh_depth(cam_b, mesh).cpu().numpy()
+        I0 = r.render_mesh_ids(cam_b, mesh).cpu().numpy()
+        r.set_mesh_record_capacity(1)
+        D1 = r.render_mesh_depth(cam_b, mesh).cpu().numpy()
+        assert r.last_stats["retries"] >= 1, r.last_stats
+        I1 = r.render_mesh_ids(cam_b, mesh).cpu().numpy()
+        d1 = r.render_mesh_depth(cam_a, mesh).cpu().numpy()
+        i1 = r.render_mesh_ids(cam_a, mesh).cpu().numpy()
+        assert np.isfinite(d0).any() and (i0 >= 0).any()
+        for got, want in ((d1, d0), (e0, d0), (i1, i0), (D1, D0), (I1, I0)):
+            assert got.tobytes() == want.tobytes()
+
+        scene = r.upload(scenes.to_gaussians(room, "cuda:0"))
+        frames = torch.stack([r.render(c, scene).clone() for c in scenes.room_cameras(room, 64, 48, n_positions=1, n_yaw=5, seed=5)])
+        depth = torch.from_numpy(np.where(np.isfinite(d0), d0, 0.0).astype(np.float32)).to("cuda:0").expand(5, -1, -1).contiguous()
+        for enc in (r.encode_jpeg, r.encode_png):
+            one, five, again = enc(frames[:1]), enc(frames), enc(frames[:1])
+            assert len(five) == 5 and one[0] == five[0] == again[0] and len(one[0]) > 100
+        one, five, again = [r.encode_png(depth[:k], format="depth16") for k in (1, 5, 1)]
+        assert len(five) == 5 and one[0] == five[0] == again[0]
+
+        big = torch.stack([r.render(cam_b, scene)] * 3)
+        s0 = r.resize(frames[0], (40, 30)).cpu().numpy()
+        s_big = r.resize(big, (100, 70)).cpu().numpy()
+        s1 = r.resize(frames, (40, 30)).cpu().numpy()
+        assert (s1[0] == s0).all() and (s_big[0] == s_big[2]).all() and (r.resize(big[1], (100, 70)).cpu().numpy() == s_big[1]).all()
+    finally:
+        r.close()
