@@ -552,6 +552,52 @@ typedef struct sgs_object_row {      /* 40 bytes, 8-byte aligned; row k of a fra
 int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n_frames, int height, int width, int64_t frame_stride,
                      int32_t n_labels, sgs_object_row* out_rows, uint32_t* out_counts, void* hip_stream);
 
+/* ---- Image similarity — windowed SSIM and squared error of rendered frames against a target picture, reduced on the device to one
+ * 64-byte row per frame.  The reference names the measure and implements none: ImgNav's success is "current view similar to target
+ * image" (task_types.py:183-208) and the function behind it returns a placeholder.  So, like the id channel and the object table,
+ * this is THIS PROJECT'S OWN definition.  It works in integers up to one fp64 quotient per window: a frame's row depends on its pixels
+ * alone — not on the batch, the frame's place in it, the strides, or how the kernel cuts the frame.  No new version: no existing
+ * struct changes.
+ *
+ *   Levels   every channel of the fp32 frame [H,W,3] first becomes the 8-bit level sgs_pack_rgba8 writes: clamp to [0,1], then
+ *            (unsigned)(x * 255 + 0.5).  The target is uint8 [H,W,3], levels already: what a PIL image holds.
+ *   Window   11 x 11, separable; 1-D integer taps w = {2, 16, 74, 224, 436, 544, 436, 224, 74, 16, 2}, sum 2048: Wang et al.'s
+ *            Gaussian of sigma 1.5 scaled by 2048 and rounded, the centre tap lowered by 1 so that the sum is exact.  A window's
+ *            weight is w[j] w[i], total T = 2^22.  Only windows that lie wholly inside the frame count: (H - 10)(W - 10) per channel,
+ *            no padding.
+ *   Moments  per window and channel, exact integers, x the frame's level and y the target's:
+ *            A = sum w x, B = sum w y, Cxx = sum w x^2, Cyy = sum w y^2, Cxy = sum w x y.
+ *   Terms    in int64:  n1 = 2 A B + c1               d1 = A^2 + B^2 + c1
+ *                       n2 = 2 (T Cxy - A B) + c2     d2 = (T Cxx - A^2) + (T Cyy - B^2) + c2
+ *            c1 = 114393189753815 and c2 = 1029538707784335: (0.01 * 255)^2 2^44 and (0.03 * 255)^2 2^44, rounded.  All four stay
+ *            below 2^63 (A^2 <= 1.15e18); d1 and d2 are positive, n2 may be negative.
+ *   Value    s = ((double)n1 * (double)n2) / ((double)d1 * (double)d2): four int64 -> fp64 conversions, two products, one division,
+ *            each rounded once (no sum, so nothing can be contracted); q = (int64)floor(s * 2^30 + 0.5) (s * 2^30 is exact).
+ *   Row      ssim_q[c] = sum of q over the windows of channel c; sse[c] = sum of (x - y)^2 over ALL pixels of channel c;
+ *            n_windows = (H - 10)(W - 10); n_pixels = H W.  The score is sum_c ssim_q[c] / (3 n_windows 2^30), the mean squared
+ *            error sum_c sse[c] / (3 n_pixels) in levels^2: host divisions, left to the caller.  Identical pictures give exactly
+ *            n_windows 2^30 per channel.
+ *   Kernels  sage-3d_official_amd/csrc/sgs_similarity.h: one workgroup per frame and tile of SGS_SIM_TILE_W x SGS_SIM_TILE_H windows. */
+#define SGS_SIM_WINDOW 11
+#define SGS_SIM_TILE_W 32
+#define SGS_SIM_TILE_H 32
+typedef struct sgs_similarity_row {  /* 64 bytes, 8-byte aligned; one per frame */
+    int64_t  ssim_q[3];              /* per channel: sum over the windows of q (30 fractional bits) */
+    uint64_t sse[3];                 /* per channel: sum over all pixels of (x - y)^2, in levels^2 */
+    uint64_t n_windows;              /* (H - 10)(W - 10) */
+    uint64_t n_pixels;               /* H W */
+} sgs_similarity_row;
+/* n_frames frames of width x height: frame f's fp32 [H,W,3] at rgb + f * rgb_frame_stride (floats) against the uint8 [H,W,3] at
+ * target + f * target_frame_stride (bytes); target_frame_stride == 0 compares every frame with the one target.  rgb, target and
+ * out_rows [n_frames] are DEVICE buffers: the rows are updated with 64-bit atomics, which a link to pinned host memory need not
+ * carry.  Every row is written whole; what out_rows held before does not matter.  Stream-ordered and asynchronous: the call never
+ * synchronises, owns no scratch and leaves none behind.  A clear of the rows, then one reduction over frames x tiles.
+ * SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument: null rgb, target or out_rows;
+ * n_frames < 1; width or height below 11 (no window) or above 65535; rgb_frame_stride < 3 width height; a non-zero
+ * target_frame_stride < 3 width height; out_rows not 8-byte aligned; rgb not 4-byte aligned. */
+int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
+                         const uint8_t* target, int64_t target_frame_stride, sgs_similarity_row* out_rows, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@
 #include "sgs_png.h"
 #include "sgs_resize.h"
 #include "sgs_objects.h"
+#include "sgs_similarity.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2021,6 +2022,53 @@ int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n
         K.rows = J.rows + (int64_t)f0 * n_labels; K.counts = out_counts + 2ll * f0;
         K.n_frames = std::min(SGS_OBJ_MAX_FRAMES, n_frames - f0);
         hipLaunchKernelGGL(sgs::k_obj_reduce, dim3(regions, (unsigned)K.n_frames), dim3(SGS_OBJ_THREADS), 0, st, K);
+    }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_image_similarity (csrc/sgs_similarity.h) --------------------------------------------------------------------------------------
+static_assert(sizeof(sgs_similarity_row) == sizeof(sgs::SimRow) && alignof(sgs_similarity_row) == 8, "sgs_similarity_row is 64 bytes, 8-byte aligned");
+
+extern "C" {
+
+int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
+                         const uint8_t* target, int64_t target_frame_stride, sgs_similarity_row* out_rows, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_image_similarity";
+    if (!rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null rgb", who);
+    if (!target) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null target", who);
+    if (!out_rows) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_rows", who);
+    if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
+    if (width < SGS_SIM_WINDOW || width > 65535) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: width %d is outside %d..65535 (a window is %d pixels wide)", who, width, SGS_SIM_WINDOW, SGS_SIM_WINDOW);
+    if (height < SGS_SIM_WINDOW || height > 65535) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: height %d is outside %d..65535 (a window is %d pixels high)", who, height, SGS_SIM_WINDOW, SGS_SIM_WINDOW);
+    const int64_t frame = 3ll * width * height;
+    if (rgb_frame_stride < frame)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rgb_frame_stride %lld floats is smaller than a frame (%lld)", who, (long long)rgb_frame_stride, (long long)frame);
+    if (target_frame_stride != 0 && target_frame_stride < frame)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: target_frame_stride %lld bytes is neither 0 nor a frame (%lld) or more", who, (long long)target_frame_stride, (long long)frame);
+    // the rows are updated with 64-bit atomics; a misaligned one must never reach the device
+    const uintptr_t rows_at = reinterpret_cast<uintptr_t>(out_rows), rgb_at = reinterpret_cast<uintptr_t>(rgb);
+    if (rows_at % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_rows %p is not 8-byte aligned", who, (const void*)out_rows);
+    if (rgb_at % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rgb %p is not 4-byte aligned", who, (const void*)rgb);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::SimJob J;
+    J.rgb = rgb; J.target = target; J.rows = reinterpret_cast<sgs::SimRow*>(out_rows);
+    J.rgb_stride = rgb_frame_stride; J.target_stride = target_frame_stride; J.W = width; J.H = height; J.n_frames = n_frames;
+    const int nwx = width - (SGS_SIM_WINDOW - 1), nwy = height - (SGS_SIM_WINDOW - 1);
+    const int tiles_x = (nwx + SGS_SIM_TILE_W - 1) / SGS_SIM_TILE_W;
+    const int tiles_y = (nwy + SGS_SIM_TILE_H - 1) / SGS_SIM_TILE_H;
+    J.tiles_x = tiles_x;
+    const unsigned clear_blocks = (unsigned)std::min<int64_t>(((int64_t)n_frames + SGS_SIM_THREADS - 1) / SGS_SIM_THREADS, 65536);
+    hipLaunchKernelGGL(sgs::k_sim_clear, dim3(clear_blocks), dim3(SGS_SIM_THREADS), 0, st, J);
+    for (int f0 = 0; f0 < n_frames; f0 += SGS_SIM_MAX_FRAMES) {
+        sgs::SimJob K = J;
+        K.rgb = rgb + (int64_t)f0 * rgb_frame_stride; K.target = target + (int64_t)f0 * target_frame_stride; K.rows = J.rows + f0;
+        K.n_frames = std::min(SGS_SIM_MAX_FRAMES, n_frames - f0);
+        hipLaunchKernelGGL(sgs::k_sim_reduce, dim3((unsigned)(tiles_x * tiles_y), (unsigned)K.n_frames), dim3(SGS_SIM_THREADS), 0, st, K);
     }
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;

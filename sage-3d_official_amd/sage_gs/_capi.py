@@ -36,7 +36,7 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_mesh_set_labels", "sgs_render_mesh_ids", "sgs_render_mesh_ids_batch",
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
-           "sgs_resize_params_default", "sgs_resize", "sgs_object_table")
+           "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity")
 
 
 class SgsError(RuntimeError):
@@ -147,6 +147,19 @@ VISIBLE_OBJECT_DTYPE = __import__("numpy").dtype([("label", "<i4")] + [(n, OBJEC
 assert OBJECT_ROW_DTYPE.itemsize == C.sizeof(SgsObjectRow) == 4 * OBJECT_ROW_WORDS
 
 
+class SgsSimilarityRow(C.Structure):
+    """include/sage_gs.h sgs_similarity_row: one frame's sums against its target."""
+    _fields_ = [("ssim_q", C.c_int64 * 3), ("sse", C.c_uint64 * 3), ("n_windows", C.c_uint64), ("n_pixels", C.c_uint64)]
+
+
+SIMILARITY_ROW_DTYPE = __import__("numpy").dtype([("ssim_q", "<i8", (3,)), ("sse", "<u8", (3,)), ("n_windows", "<u8"), ("n_pixels", "<u8")])
+SIMILARITY_Q_BITS = 30                       # fractional bits of ssim_q
+SIMILARITY_WINDOW, SIMILARITY_TILE_W, SIMILARITY_TILE_H = 11, 32, 32      # include/sage_gs.h SGS_SIM_WINDOW, SGS_SIM_TILE_W, SGS_SIM_TILE_H
+# Renderer.image_similarity's record: the raw row, then the host divisions
+SIMILARITY_DTYPE = __import__("numpy").dtype(SIMILARITY_ROW_DTYPE.descr + [("ssim", "<f8"), ("ssim_rgb", "<f8", (3,)), ("mse", "<f8"), ("psnr", "<f8")])
+assert SIMILARITY_ROW_DTYPE.itemsize == C.sizeof(SgsSimilarityRow) == 64
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -233,6 +246,7 @@ class Lib:
         lib.sgs_resize_params_default.argtypes = [C.POINTER(SgsResizeParams)]; lib.sgs_resize_params_default.restype = None
         lib.sgs_resize.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsResizeParams), vp, i64, vp]
         lib.sgs_object_table.argtypes = [vp, vp, vp, i32, i32, i32, i64, C.c_int32, vp, vp, vp]
+        lib.sgs_image_similarity.argtypes = [vp, vp, i32, i32, i32, i64, vp, i64, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

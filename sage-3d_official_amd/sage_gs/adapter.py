@@ -50,6 +50,7 @@ class GsCamera:
         self._instance_paths = None if instance_paths is None else [str(p) for p in instance_paths]
         self._instance_in_frame = False
         self._boxes_in_frame = False
+        self._target = None                                               # set_target_image: uint8 [h,w,3] on the device, at get_output_size()
         self._w, self._h = int(resolution[0]), int(resolution[1])         # Isaac resolution = (width, height)
         self._pos = np.zeros(3, np.float32)
         self._orient = np.array([1.0, 0.0, 0.0, 0.0], np.float32)         # (w, x, y, z)
@@ -109,6 +110,39 @@ class GsCamera:
         else:
             img = self._r.render_rgba8_host(self._camera(), self._scene, config=self._config, output_size=self._out, resample=self._resample)
         return img.copy() if copy else img
+
+    # -- similarity to a target picture (Renderer.image_similarity: this project's own definition) ---------------------------------
+    def set_target_image(self, img):
+        """The picture get_image_similarity() compares the view with: a PIL image, or uint8 [h,w,3] / [h,w,4] (get_rgba()'s; alpha is
+        dropped) as a NumPy array or a tensor.  It is brought to get_output_size() ONCE, here, when its size differs — with the
+        camera's own resample through Renderer.resize, on the device — and stays there as uint8 levels.  None forgets it.  The goal
+        image of an ImgNav episode (task_types.py:183-208)."""
+        if img is None:
+            self._target = None
+            return
+        import torch
+        if isinstance(img, torch.Tensor):
+            img = img.detach().cpu().numpy()
+        elif hasattr(img, "convert") and hasattr(img, "size"):
+            img = np.asarray(img.convert("RGB"))
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] not in (3, 4):
+            raise ValueError("the target image must be uint8 [h,w,3] or [h,w,4]")
+        img = np.ascontiguousarray(img[..., :3])
+        w, h = self.get_output_size()
+        if (img.shape[1], img.shape[0]) == (w, h):
+            self._target = torch.from_numpy(img).to(self._r.device)
+            return
+        frame = torch.from_numpy(img.astype(np.float32) / np.float32(255.0)).to(self._r.device)      # on the levels: k / 255
+        resized = self._r.resize(frame, (w, h), filter=self._resample)
+        self._target = self._r.pack_rgba8(resized)[..., :3].contiguous()
+
+    def get_image_similarity(self):
+        """One record of Renderer.image_similarity (ssim, ssim_rgb, mse, psnr and the exact sums) for the picture get_rgba() would
+        show now against the target image: the view is rendered, resized with output_size, and compared on the device."""
+        if self._target is None:
+            raise RuntimeError("no target image: call set_target_image first")
+        return self._r.image_similarity(self.get_rgb_tensor(), self._target)[0]
 
     def get_jpeg(self, quality: int = 75) -> bytes:
         """The current view as the bytes of a baseline JPEG file — the picture get_rgba() returns, encoded on the GPU

@@ -960,6 +960,63 @@ class Renderer:
         cuts = np.searchsorted(where_h[:, 0], np.arange(rows.shape[0] + 1))
         return [out[cuts[f]:cuts[f + 1]] for f in range(rows.shape[0])]
 
+    # -- image similarity of frames against a target picture (include/sage_gs.h sgs_image_similarity: this project's own definition) --
+    def _target_levels(self, target) -> torch.Tensor:
+        """`target` as uint8 [H,W,3] or [B,H,W,3] on the device: a tensor there already, or a NumPy array or PIL image, uploaded."""
+        if not isinstance(target, torch.Tensor):
+            if hasattr(target, "convert") and hasattr(target, "size"):                # a PIL image
+                target = np.asarray(target.convert("RGB"))
+            target = np.asarray(target)
+            if target.dtype != np.uint8:
+                raise ValueError(f"target must hold uint8 levels, not {target.dtype}")
+            target = torch.from_numpy(np.array(target, order="C")).to(self.device)                  # (a copy: PIL's arrays are read-only)
+        if target.dtype != torch.uint8:
+            raise ValueError(f"target must hold uint8 levels, not {target.dtype}")
+        if target.device != self.device or target.dim() not in (3, 4) or target.shape[-1] != 3 or not target[(0,) * (target.dim() - 3)].is_contiguous():
+            raise ValueError("target must be uint8 [H,W,3] or [B,H,W,3] on the renderer's device with contiguous pictures")
+        return target
+
+    def image_similarity(self, frames: torch.Tensor, target) -> np.ndarray:
+        """Windowed SSIM and squared error of float32 frames [H,W,3] or [B,H,W,3] on the device against `target`: uint8 levels
+        [H,W,3] (one picture for every frame) or [B,H,W,3] (frame f against picture f) as a tensor on the device, or a NumPy array
+        or PIL image, which is uploaded.  One launch for the whole batch; 64 bytes per frame come back.  Returns a NumPy structured
+        array with one record per frame (_capi.SIMILARITY_DTYPE): sgs_similarity_row's fields — ssim_q[3], sse[3], n_windows,
+        n_pixels, exact integers — and the host divisions ssim (the mean over the three channels, 1.0 for identical pictures),
+        ssim_rgb[3], mse (in levels squared) and psnr (dB, inf at zero error).  The frame's levels are the ones get_rgba() shows.
+        ValueError on a size or dtype mismatch: nothing is ever resized here.  This project's own definition: the reference names
+        the measure for ImgNav (task_types.py:183-208) and returns a placeholder."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
+            raise ValueError("frames must be a float32 tensor")
+        if frames.dim() == 3:
+            frames = frames.unsqueeze(0)
+        if frames.device != self.device or frames.dim() != 4 or frames.shape[-1] != 3 or frames.shape[0] < 1 or not frames[0].is_contiguous():
+            raise ValueError("frames must be float32 [H,W,3] or [B,H,W,3] on the renderer's device with contiguous frames")
+        b, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        target = self._target_levels(target)
+        if tuple(target.shape[-3:]) != (h, w, 3):
+            raise ValueError(f"target is {int(target.shape[-2])} x {int(target.shape[-3])}, the frames are {w} x {h}: resize one of them first")
+        if target.dim() == 4 and int(target.shape[0]) != b:
+            raise ValueError(f"{int(target.shape[0])} targets for {b} frames")
+        if w < _capi.SIMILARITY_WINDOW or h < _capi.SIMILARITY_WINDOW:
+            raise ValueError(f"frames of {w} x {h} hold no {_capi.SIMILARITY_WINDOW} x {_capi.SIMILARITY_WINDOW} window")
+        size = 3 * h * w
+        t_stride = 0 if target.dim() == 3 else (int(target.stride(0)) if b > 1 else size)
+        rows = torch.empty((b, 8), dtype=torch.int64, device=self.device)
+        self._lib.check(self._lib.sgs_image_similarity(self._ctx, frames.data_ptr(), w, h, b, int(frames.stride(0)) if b > 1 else size,
+                                                       target.data_ptr(), t_stride, rows.data_ptr(), self._stream()), self._ctx)
+        raw = np.ascontiguousarray(rows.cpu().numpy()).view(_capi.SIMILARITY_ROW_DTYPE).reshape(b)
+        out = np.zeros(b, _capi.SIMILARITY_DTYPE)
+        for name in _capi.SIMILARITY_ROW_DTYPE.names:
+            out[name] = raw[name]
+        one = float(1 << _capi.SIMILARITY_Q_BITS)
+        n_win, n_pix = raw["n_windows"].astype(np.float64), raw["n_pixels"].astype(np.float64)
+        out["ssim_rgb"] = raw["ssim_q"].astype(np.float64) / (n_win[:, None] * one)
+        out["ssim"] = np.array([float(int(q.sum())) for q in raw["ssim_q"]]) / (3.0 * n_win * one)
+        out["mse"] = np.array([float(int(e.sum())) for e in raw["sse"]]) / (3.0 * n_pix)
+        with np.errstate(divide="ignore"):
+            out["psnr"] = np.where(out["mse"] > 0, 10.0 * np.log10(255.0 * 255.0 / np.where(out["mse"] > 0, out["mse"], 1.0)), np.inf)
+        return out
+
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
         self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)
