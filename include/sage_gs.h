@@ -302,9 +302,16 @@ enum {
     SGS_BUF_SPLATS       = 3,      /* S x 12 words: x,y,conic a,b | c,opacity,r,g | b,depth bits,rect01,rect23 (dead = 0) */
     SGS_BUF_SCENE_GEOM   = 5,      /* float[N][11] of the LAST RENDERED scene as the device holds it, by original index: mean xyz, opacity, scale xyz,
                                     * quaternion wxyz (as uploaded / as dequantised from a compressed payload) */
-    SGS_BUF_SCENE_SH     = 6       /* float[N][3 (d+1)^2] of the LAST RENDERED scene, by original index, [coefficient][channel]: the SH coefficients the
+    SGS_BUF_SCENE_SH     = 6,      /* float[N][3 (d+1)^2] of the LAST RENDERED scene, by original index, [coefficient][channel]: the SH coefficients the
                                     * projection kernel evaluates — the fp32 rows as uploaded, or (a scene uploaded from the compressed payload, which
                                     * keeps its 8-bit coefficients as bytes in HBM) those bytes dequantised exactly as the kernel does */
+    SGS_BUF_SCENE_PERM   = 7,      /* uint32[N] of the LAST RENDERED scene: layout position p holds the Gaussian of original index perm[p] — the
+                                    * Z-order the upload's radix sort made; the identity when the scene was not sorted (sgs_tuning.morton = 0,
+                                    * or N <= 64).  Read from the host copy the upload keeps: no per-frame work */
+    SGS_BUF_CHUNK_BOUNDS = 8       /* float[ceil(N/64)][8] of the LAST RENDERED scene, in layout order: per 64-Gaussian chunk the bounding sphere
+                                    * of its means (cx, cy, cz, R; R = +inf: never skipped) and (s_max, 0, 0, 0), its largest scale — what the
+                                    * projection kernel tests a chunk against before it loads it.  Both are new VALUES of `what`, no struct
+                                    * changes: SGS_VERSION stays 114 */
 };
 int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes);
 

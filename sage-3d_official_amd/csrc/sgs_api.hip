@@ -1318,6 +1318,8 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
         case SGS_BUF_CHUNK_SKIPPED: have = n_chunks; break;
         case SGS_BUF_SCENE_GEOM: have = ctx->last_scene ? ctx->last_n * 11 * 4 : 0; break;
         case SGS_BUF_SCENE_SH: have = ctx->last_scene ? ctx->last_n * 3 * (ctx->last_scene->sh_degree + 1) * (ctx->last_scene->sh_degree + 1) * 4 : 0; break;
+        case SGS_BUF_SCENE_PERM: have = ctx->last_scene ? ctx->last_n * 4 : 0; break;
+        case SGS_BUF_CHUNK_BOUNDS: src = ctx->last_scene ? ctx->last_scene->cbound.p : nullptr; have = src ? n_chunks * 32 : 0; break;
         case 100: src = L.tile_prof.p; have = (int64_t)ctx->last_T * 8 * SGS_PROF_WORDS; break;    // profiling build only
         case 101: src = L.bin_prof.p; have = (int64_t)SGS_BIN_BLOCKS * 64; break;  // profiling build only
         default: SGS_FAIL(ctx, SGS_ERR_INVALID, "unknown buffer id %d", what);
@@ -1333,6 +1335,10 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
         const unsigned total = tmp[(size_t)ctx->last_t_hi];
         for (int64_t i = 0; (i + 1) * 4 <= n; ++i)
             ((unsigned*)host_dst)[i] = i < ctx->last_t_lo ? 0u : i >= ctx->last_t_hi ? total : tmp[(size_t)i];
+    }
+    if (what == SGS_BUF_SCENE_PERM) {      // the host copy layout_scene kept (empty: the scene is in the caller's order)
+        const std::vector<unsigned>& perm = ctx->last_scene->perm_host;
+        for (int64_t p = 0; (p + 1) * 4 <= n; ++p) ((unsigned*)host_dst)[p] = perm.empty() ? (unsigned)p : perm[(size_t)p];
     }
     if (what == SGS_BUF_SCENE_GEOM) {
         std::vector<float4> rows((size_t)n_slots * SGS_GEOM_ROWS);

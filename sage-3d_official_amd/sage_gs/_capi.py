@@ -20,6 +20,7 @@ FLAG_NO_FINE_TILES = 512
 BACKEND_CPU, BACKEND_HIP = 0, 1
 ID_NONE = -1             # include/sage_gs.h SGS_ID_NONE: sgs_render_mesh_ids* where nothing is hit
 BUF_TILE_OFFSETS, BUF_SORTED_SLOTS, BUF_SLOT_IDS, BUF_SPLATS, BUF_CHUNK_SKIPPED, BUF_SCENE_GEOM, BUF_SCENE_SH = 0, 1, 2, 3, 4, 5, 6
+BUF_SCENE_PERM, BUF_CHUNK_BOUNDS = 7, 8       # the upload's results: uint32 [N] layout position -> original index; float [ceil(N/64), 8]
 
 ERR_NAMES = {-1: "SGS_ERR_INVALID", -2: "SGS_ERR_HIP", -3: "SGS_ERR_OOM", -4: "SGS_ERR_OVERFLOW",
              -5: "SGS_ERR_BACKEND"}

@@ -538,21 +538,26 @@ def case_interleaved_rows(drv, stride, n=2500, res=(208, 150)):
             assert d_sum == st_full["d_total"] and d_ref_sum == st_full_ref["d_total"]
 
 
+def chunk_bounds_scene(n=6000, res=(208, 150)):
+    """case_chunk_bounds' scene and camera: a wall 24 m x 12 m facing the camera at ~6 m (the view covers a tenth of it) and a cloud behind
+    the camera, in random order."""
+    means, scales, quats, opac, sh, deg = random_scene(n, 17, 1, box=((-12, 12), (-6, 6), (5.9, 6.1)), scale=(0.02, 0.12))
+    rng = np.random.default_rng(18)
+    back = rng.random(n) < 0.3
+    means[back, 2] = rng.uniform(-10.0, -2.0, int(back.sum())).astype(np.float32)
+    w, h = res
+    view = look_at_view((0.3, -0.2, -1.0), (0.5, 0.4, 6.0))
+    return (means, scales, quats, opac, sh, deg), onp.Camera(w, h, 0.9 * w, 0.9 * w, w / 2.0 + 3.3, h / 2.0 - 2.1, view)
+
+
 def case_chunk_bounds(drv, n=6000, res=(208, 150)):
     """Per-chunk bounds (k_chunk_bounds / chunk_outside): a scene much wider than the view, so most 64-Gaussian chunks
     (Z-ordered at upload) lie outside the image or behind the camera.  The skipped chunks must hold no visible Gaussian
     — N_v, D, queues and frames equal the oracle's and the no-culling run's, for the full frame and for bands of tile
     rows (where chunks above and below the band are skipped too) — and a good share of the chunks must actually be
-    skipped, or the test would prove nothing."""
-    # a wall 24 m x 12 m facing the camera at ~6 m (the view covers a tenth of it) and a cloud behind the camera
-    means, scales, quats, opac, sh, deg = random_scene(n, 17, 1, box=((-12, 12), (-6, 6), (5.9, 6.1)), scale=(0.02, 0.12))
-    rng = np.random.default_rng(18)
-    back = rng.random(n) < 0.3
-    means[back, 2] = rng.uniform(-10.0, -2.0, int(back.sum())).astype(np.float32)
-    scene = (means, scales, quats, opac, sh, deg)
+    skipped, or the test would prove nothing.  (That the bounds are TIGHT, and the order they are cut from, is upload_cases' matter.)"""
+    scene, cam = chunk_bounds_scene(n, res)
     w, h = res
-    view = look_at_view((0.3, -0.2, -1.0), (0.5, 0.4, 6.0))
-    cam = onp.Camera(w, h, 0.9 * w, 0.9 * w, w / 2.0 + 3.3, h / 2.0 - 2.1, view)
     gy = (h + 15) // 16
     n_chunks = (n + 63) // 64
     skipped = {}
