@@ -146,6 +146,49 @@ struct sgs_mesh {
     DevBuf<int> labels;                      // sgs_mesh_set_labels: [n_tris], or empty: a triangle's label is its index
 };
 
+// A frame's band, decided once per call by validate(): the 16-pixel tile rows [row_begin, row_end) the call owns (clamped), row k of them
+// being row k * stride + phase of the frame (sgs_config.tile_row_stride / _phase), the frame's fine-tile shift z (fine_shift_of) and
+// the pixel rows the call writes (band_pixel_rows).
+struct Band {
+    int row_begin = 0, row_end = 0, stride = 1, phase = 0, z = 0;
+    int64_t pixel_rows = 0;
+};
+
+// One issued frame: where its verdict lands and its intermediates live, and what the statistics and sgs_debug_read need of it.
+struct FrameRec {
+    int slot = -1, lane = 0;                 // status ring slot (-1: no frame yet); the lane whose intermediates it used
+    hipStream_t stream = nullptr;            // the caller's
+    bool timed = false;
+    int retries = 0;                         // renders it took beyond the first (synchronous frames grow the record buffers and render again)
+    const sgs_scene* scene = nullptr;        // (nulled by sgs_scene_free)
+    int64_t n = 0, pixels = 0;               // Gaussians; pixels the call wrote
+    int sh_rows = 0;
+    int T = 0, t_lo = 0, t_hi = 0, tiles = 0;    // the grid: all its tiles, the band [t_lo, t_hi) rendered (k_tile_scan fills only those), their count
+};
+
+// The status ring: a FrameStatus per frame in flight on the device, its pinned copy, and which slots are PENDING — issued since the
+// last synchronisation and not looked at yet.  INVARIANT: a slot is pending only once the copy of its status word has been enqueued
+// (issued() follows a successful enqueue; a slot whose enqueue failed was never taken).  The indices are nobody else's business.
+class StatusRing {
+    int next = 0, count = 0;                 // the pending slots: the `count` before `next` (mod kStatusRing)
+public:
+    DevBuf<FrameStatus> d_status;
+    PinnedBuf<FrameStatus> h_status;
+    std::unique_ptr<sgs::Event[]> ev;        // per-slot event sets for SGS_FLAG_TIMING, [kStatusRing][SGS_NUM_STAGES + 1] (ensure_timing_events)
+    bool timed[kStatusRing] = {};            // the slot's frame recorded its events
+
+    const sgs::Event* events(int slot) const { return &ev[(size_t)slot * (SGS_NUM_STAGES + 1)]; }
+    bool full() const { return count == kStatusRing; }
+    bool idle() const { return count == 0; }
+    int slot() const { return next; }                                    // the slot of the next single frame (while !full()) ...
+    void issued() { next = (next + 1) % kStatusRing; ++count; }         // ... pending from here on
+    template <class F> void for_pending(F&& f) const { for (int k = count; k > 0; --k) f((next - k + kStatusRing) % kStatusRing); }
+    void seen() { count = 0; }                                           // every pending verdict has been looked at
+    // A batch chunk uses slots [0, cn) from the slot returned: cleared, copied back and read by the batch itself, hence never pending
+    // (nothing else may be); the ring starts over.
+    int take_chunk() { next = count = 0; return 0; }
+};
+
 struct sgs_ctx {
     int device = 0;
     MeshScratch mesh;
@@ -157,7 +200,6 @@ struct sgs_ctx {
     int n_lanes = 3, next_lane = 0;          // sgs_tuning.lanes: lanes that SGS_FLAG_PIPELINED single frames rotate over
     int group = 8, group_lanes = 2;          // sgs_tuning.group x .group_lanes <= kMaxLanes: sgs_render_batch* issues `group` frames per
                                              // set of launches (blockIdx.y = frame), groups rotating over `group_lanes` streams
-    int last_lane = 0;
     int exp_grid = SGS_EXP_GRID;             // level-2 binning workgroups per launch (settled by A/B: r03, r04)
     int bin_grid = SGS_BIN_BLOCKS;           // binning workgroups per launch (<= SGS_BIN_BLOCKS)
     int pre_grid = 8192;                     // k_preprocess workgroups per launch of a frame GROUP: its waves loop over the live list (r03y)
@@ -169,25 +211,9 @@ struct sgs_ctx {
                                              // (k_chunk_bounds / chunk_outside) worth testing — trained scenes come in no spatial order
     DevBuf<unsigned long long> row_acc;      // records queued per frame tile row, summed over the frames since the last
                                              // sgs_row_records(reset) — what cost-balanced tile-row bands are cut from
-    const sgs_scene* last_scene = nullptr;
     int64_t rec_cap_wanted = 16ll << 20;
-    // status ring
-    DevBuf<FrameStatus> d_status;
-    PinnedBuf<FrameStatus> h_status;
-    int next_slot = 0;
-    // bookkeeping of the most recent frame
-    int last_slot = -1;
-    bool last_timed = false;
-    int64_t last_n = 0, last_pixels = 0;
-    int last_tiles = 0, last_sh_rows = 0, last_T = 0;
-    int last_t_lo = 0, last_t_hi = 0;         // the band of tiles the last frame rendered (k_tile_scan fills only those)
-    int last_retries = 0;
-    hipStream_t last_stream = nullptr;
-    // frames issued since the last synchronisation (ring slots pending_begin .. +pending_count)
-    int pending_begin = 0, pending_count = 0;
-    // per-slot event sets for SGS_FLAG_TIMING, [kStatusRing][SGS_NUM_STAGES + 1], created on first use (ensure_timing_events)
-    std::unique_ptr<sgs::Event[]> ev;
-    bool slot_timed[256] = {};
+    StatusRing ring;
+    FrameRec last;                           // the most recent frame issued: what sgs_frame_sync reports and sgs_debug_read looks at
 };
 
 #define SGS_FAIL(ctx, code, ...)                                  \
@@ -291,15 +317,14 @@ int ensure_lane_stream(sgs_ctx* ctx, Lane& L) {
 
 // The event sets of SGS_FLAG_TIMING: all of them or none.
 int ensure_timing_events(sgs_ctx* ctx) {
-    if (ctx->ev) return SGS_OK;
+    if (ctx->ring.ev) return SGS_OK;
     constexpr int n = kStatusRing * (SGS_NUM_STAGES + 1);
     std::unique_ptr<sgs::Event[]> ev(new (std::nothrow) sgs::Event[n]);
     if (!ev) SGS_FAIL(ctx, SGS_ERR_OOM, "out of host memory");
     for (int i = 0; i < n; ++i) SGS_HIP(ctx, ev[i].create());
-    ctx->ev = std::move(ev);
+    ctx->ring.ev = std::move(ev);
     return SGS_OK;
 }
-const sgs::Event* slot_events(const sgs_ctx* ctx, int slot) { return &ctx->ev[(size_t)slot * (SGS_NUM_STAGES + 1)]; }
 
 // The mesh path's status words, on the device and pinned: made by the first mesh upload or mesh frame of a context.
 int ensure_mesh_status(sgs_ctx* ctx) {
@@ -423,8 +448,9 @@ int64_t band_pixel_rows(int height, int row_begin, int row_end, int stride, int 
     return rows;
 }
 
+// The checks every frame passes before anything is enqueued, and the frame's band (rows as the caller gave them: negative = open end).
 int validate(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const sgs_config* cfg,
-             int& row_begin, int& row_end, const float* out_rgb, int* fine_shift = nullptr) {
+             int row_begin, int row_end, const float* out_rgb, Band& band) {
     if (!scene || !cam || !out_rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "null scene / camera / output");
     char why[160];
     if (check_camera(*cam, why, sizeof why)) SGS_FAIL(ctx, SGS_ERR_INVALID, "camera: %s", why);
@@ -451,15 +477,16 @@ int validate(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const 
     sgs_config cfg_d;
     if (!cfg) sgs_config_default(&cfg_d);
     const int z = fine_shift_of(ctx, scene, cam, cfg ? *cfg : cfg_d), cp = SGS_TILE >> z;
-    if (fine_shift) *fine_shift = z;
     const int gx = (cam->width + cp - 1) / cp, rb = row_begin << z, re = row_end << z;
     const int64_t ns = (int64_t)((gx + SGS_ST - 1) / SGS_ST) * (((re + SGS_ST - 1) / SGS_ST) - rb / SGS_ST);
     if (ns > SGS_WT) SGS_FAIL(ctx, SGS_ERR_INVALID, "band of %d tile rows x %d tiles exceeds %d super-tiles", re - rb, gx, SGS_WT);
+    band.row_begin = row_begin; band.row_end = row_end; band.stride = stride; band.phase = phase; band.z = z;
+    band.pixel_rows = band_pixel_rows(cam->height, row_begin, row_end, stride, phase);
     return SGS_OK;
 }
 
 void fill_params(FrameParams& P, const sgs_ctx* ctx, const Lane& L, const sgs_scene* scene, const sgs_camera* cam,
-                 const sgs_config& cfg, int row_begin, int row_end, int z) {
+                 const sgs_config& cfg, const Band& band) {
     memset(&P, 0, sizeof P);
     for (int i = 0; i < 12; ++i) P.view[i] = cam->view[i];
     const float* V = cam->view;
@@ -472,11 +499,10 @@ void fill_params(FrameParams& P, const sgs_ctx* ctx, const Lane& L, const sgs_sc
     P.width = cam->width; P.height = cam->height;
     // Fine tiles (sgs_common.h): the grid, the band and every tile index the kernels see count CELLS of (16 >> z)^2 pixels; row_begin / row_end
     // arrive in 16-pixel rows (the C ABI's unit), each of which is 2^z rows of cells — but for the frame's last one when the height leaves it short
-    const int cp = SGS_TILE >> z;                 // (z: fine_shift_of, decided once per call by validate)
+    const int row_begin = band.row_begin, row_end = band.row_end, z = band.z, cp = SGS_TILE >> z;
     const int gx16 = (cam->width + SGS_TILE - 1) / SGS_TILE, gy16 = (cam->height + SGS_TILE - 1) / SGS_TILE;
     P.gx = (cam->width + cp - 1) / cp; P.gy = (cam->height + cp - 1) / cp;
-    P.row_stride = cfg.tile_row_stride > 1 ? cfg.tile_row_stride : 1;
-    P.row_phase = P.row_stride > 1 ? cfg.tile_row_phase : 0;
+    P.row_stride = band.stride; P.row_phase = band.phase;
     P.row_begin = row_begin << z; P.row_end = row_end << z;
     if (row_end > row_begin && (row_end - 1) * P.row_stride + P.row_phase == gy16 - 1) P.row_end -= (gy16 << z) - P.gy;
     // a contiguous band ignores what projects outside its pixel rows; interleaved rows span the frame
@@ -594,22 +620,46 @@ void launch_composite(const FrameGroup& G, int nf, hipStream_t stream, bool aux,
     }
 }
 
-// The FrameGroup of nf frames of one scene: frame f uses the intermediates of lane set0 + f (grown here if need be) and status slot
-// slot0 + f.
-int build_group(sgs_ctx* ctx, FrameGroup& G, const sgs_scene* scene, const sgs_camera* cams, int nf, const sgs_config& cfg,
-                int row_begin, int row_end, float* const* outs, int slot0, float* out_aux, int set0, int z) {
+// How a group of frames is issued: which stream its launches go to, and who does the runtime calls around them.
+//                   stream                       forked from the caller's by   status slots cleared / copied back by   `done` recorded
+//   caller          the caller's                 -                             enqueue_group                            -
+//   lane            lane `lane0`'s own           enqueue_group                 enqueue_group                            by enqueue_group, on the lane's stream
+//   batch_lanes     lane `stream_lane`'s own     the batch, once per chunk     the batch, once per chunk                - (the batch waits for the streams)
+//   batch_caller    the caller's                 -                             the batch, once per chunk                -
+// On the caller's stream (caller, batch_caller) the group first waits for the `done` of every lane it uses that is still busy with a
+// pipelined frame.  caller: ordinary frames; lane: SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED single frames; batch_lanes: sgs_render_batch*;
+// batch_caller: sgs_render_batch* under the SGS_FLAG_FULL_SORT test hook.  (The per-frame runtime calls around the launches were ~40 us,
+// as long as a light band of tile rows takes on the GPU: hence once per chunk in a batch.)
+enum class Issue { caller, lane, batch_lanes, batch_caller };
+
+// A GROUP of nf <= SGS_MAX_GROUP frames of one scene — same resolution, same band, one camera each — issued as ONE set of launches
+// (blockIdx.y = frame; sgs_common.h FrameGroup).  Frame f uses the intermediates of lane lane0 + f and status slot slot0 + f, and
+// writes outs[f].  nf = 1 and lane0 = 0 for Issue::caller, nf = 1 for Issue::lane; timed and out_aux are single-frame facilities.
+struct Group {
+    const sgs_scene* scene; const sgs_camera* cams; int nf; const sgs_config* cfg; Band band;
+    float* const* outs; float* out_aux;
+    int slot0, lane0;
+    int stream_lane;                         // Issue::batch_lanes: the lane whose stream the group runs on
+    hipStream_t caller_stream;
+    bool timed;
+    Issue mode;
+};
+
+// The FrameGroup of g: the lanes' intermediates are grown here if need be.
+int build_group(sgs_ctx* ctx, FrameGroup& G, const Group& g) {
     int rc;
-    const int cp = SGS_TILE >> z;                 // (the frames of a group share a resolution, a configuration and the fine-tile shift)
-    const int gx = (cams->width + cp - 1) / cp, gy = (cams->height + cp - 1) / cp;
+    const sgs_scene* scene = g.scene;
+    const int cp = SGS_TILE >> g.band.z;          // (the frames of a group share a resolution, a configuration and the fine-tile shift)
+    const int gx = (g.cams->width + cp - 1) / cp, gy = (g.cams->height + cp - 1) / cp;
     memset(&G, 0, sizeof G);
     G.geom = scene->geom.p; G.shq = scene->shq.p; G.cbound = scene->cbound.p; G.row_acc = ctx->row_acc.p;
-    for (int f = 0; f < nf; ++f) {
-        Lane& A = ctx->lanes[set0 + f];
+    for (int f = 0; f < g.nf; ++f) {
+        Lane& A = ctx->lanes[g.lane0 + f];
         if ((rc = ensure_splats(ctx, A, scene->n)) != SGS_OK) return rc;
         if ((rc = ensure_tiles(ctx, A, gx * gy)) != SGS_OK) return rc;
         if ((rc = ensure_records(ctx, A)) != SGS_OK) return rc;
         FrameSlot& S = G.s[f];
-        fill_params(S.P, ctx, A, scene, &cams[f], cfg, row_begin, row_end, z);
+        fill_params(S.P, ctx, A, scene, &g.cams[f], *g.cfg, g.band);
         if ((S.P.flags & SGS_FLAG_FULL_SORT) && (rc = ensure_sorted_out(ctx, A)) != SGS_OK) return rc;
         S.splats = A.splats.p; S.vismask = A.vismask.p; S.bigmask = A.bigmask.p; S.big_list = A.big_list.p; S.binrec = A.binrec.p;
         S.live_list = A.live_list.p;
@@ -618,82 +668,71 @@ int build_group(sgs_ctx* ctx, FrameGroup& G, const sgs_scene* scene, const sgs_c
         S.stile_count = A.stile_count.p; S.stile_offset = A.stile_offset.p; S.jobs = A.jobs.p; S.job_base = A.job_base.p;
         S.rec = A.rec.p; S.alt = A.alt.p; S.part = A.part.p; S.sorted_out = A.sorted_out.p;
         S.tile_prof = A.tile_prof.p; S.bin_prof = A.bin_prof.p;
-        S.out_rgb = outs[f]; S.out_aux = out_aux; S.st = ctx->d_status.p + slot0 + f;
+        S.out_rgb = g.outs[f]; S.out_aux = g.out_aux; S.st = ctx->ring.d_status.p + g.slot0 + f;
     }
     return SGS_OK;
 }
 
-// bookkeeping of "the most recent frame" (what sgs_frame_sync reports and sgs_debug_read looks at)
-void note_last(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, const FrameParams& P, int row_begin16, int row_end16, int slot,
-               int lane, bool timed, hipStream_t caller_stream) {
-    const int gx = P.gx, gy = P.gy, row_begin = P.row_begin, row_end = P.row_end;
-    ctx->last_slot = slot; ctx->last_timed = timed; ctx->last_stream = caller_stream; ctx->last_lane = lane;
-    ctx->last_n = scene->n; ctx->last_tiles = (row_end - row_begin) * gx; ctx->last_sh_rows = scene->sh_rows;
-    ctx->last_T = gx * gy;
-    ctx->last_t_lo = row_begin * gx; ctx->last_t_hi = row_end * gx;
-    ctx->last_scene = scene;
-    ctx->last_pixels = band_pixel_rows(cam->height, row_begin16, row_end16, P.row_stride, P.row_phase) * cam->width;     // pixels this call wrote
-}
-
-// Enqueue a GROUP of nf <= SGS_MAX_GROUP frames of one scene — same resolution, same tile rows, one camera each — as
-// ONE set of five launches (blockIdx.y = frame; sgs_common.h FrameGroup).  Frame f uses the intermediates of lane
-// set0 + f and status slot slot0 + f; the launches go to `stream`.
-//   * ordinary frames: nf = 1, set0 = 0, stream = the caller's;
-//   * SGS_FLAG_PIPELINED frames: nf = 1, the next lane and its own stream, forked from the caller's stream;
-//   * sgs_render_batch*: groups of ctx->group frames rotating over ctx->group_lanes streams (in_batch: the caller forks
-//     the streams, zeroes and collects the status slots and waits ONCE per batch — the per-frame runtime calls around the
-//     launches were ~40 us, as long as a light band of tile rows takes on the GPU).
-int enqueue_group(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, int nf, const sgs_config& cfg,
-                  int row_begin, int row_end, float* const* outs, int slot0, hipStream_t caller_stream, bool timed,
-                  float* out_aux, bool pipelined, bool in_batch, int set0, int z, int stream_lane = -1) {
+// Enqueue the group g (Issue says on which stream and with which calls around the launches).  `first` = the record of its frame 0; frame
+// f's differs by slot + f and lane + f alone.
+int enqueue_group(sgs_ctx* ctx, const Group& g, FrameRec& first) {
     int rc;
+    const bool own_stream = g.mode == Issue::lane || g.mode == Issue::batch_lanes;
+    const bool in_batch = g.mode == Issue::batch_lanes || g.mode == Issue::batch_caller;
+    const int nf = g.nf;
     // The stream: a pipelined frame's own lane's; a batch's groups rotate over the streams of lanes 0 .. group_lanes-1 — the
     // SAME streams single pipelined frames use.  (r03y: the groups used to run on the streams of lanes 0 and 4; a process that
     // had issued one batch and then pipelined single frames owned four lane streams + the caller's, the runtime maps streams onto
     // four hardware queues, two lanes shared one and the sweep was 11 % slower — 4180 vs 3750 frames/s — for the rest of the process.)
-    Lane& L = ctx->lanes[stream_lane >= 0 ? stream_lane : set0];
-    hipStream_t stream = caller_stream;
-    if (pipelined) {
+    Lane& L = ctx->lanes[g.mode == Issue::batch_lanes ? g.stream_lane : g.lane0];
+    hipStream_t stream = g.caller_stream;
+    if (own_stream) {
         if ((rc = ensure_lane_stream(ctx, L)) != SGS_OK) return rc;
         stream = L.stream.s;
     }
     FrameGroup G;
-    if ((rc = build_group(ctx, G, scene, cams, nf, cfg, row_begin, row_end, outs, slot0, out_aux, set0, z)) != SGS_OK) return rc;
+    if ((rc = build_group(ctx, G, g)) != SGS_OK) return rc;
     const FrameParams& P = G.s[0].P;
-    if (pipelined && !in_batch) {
+    if (g.mode == Issue::lane) {
         // start after whatever the caller already put on its stream (scene upload, consumers of the output buffer)
-        SGS_HIP(ctx, hipEventRecord(L.fork.e, caller_stream));
+        SGS_HIP(ctx, hipEventRecord(L.fork.e, g.caller_stream));
         SGS_HIP(ctx, hipStreamWaitEvent(L.stream.s, L.fork.e, 0));
-    } else if (!pipelined) {
+    } else if (!own_stream) {
         for (int f = 0; f < nf; ++f)               // these lanes' buffers may still be in use by a pipelined frame
-            if (ctx->lanes[set0 + f].busy) SGS_HIP(ctx, hipStreamWaitEvent(caller_stream, ctx->lanes[set0 + f].done.e, 0));
+            if (ctx->lanes[g.lane0 + f].busy) SGS_HIP(ctx, hipStreamWaitEvent(g.caller_stream, ctx->lanes[g.lane0 + f].done.e, 0));
     }
-    FrameStatus* st = ctx->d_status.p + slot0;
+    StatusRing& R = ctx->ring;
+    FrameStatus* st = R.d_status.p + g.slot0;
     if (!in_batch) SGS_HIP(ctx, hipMemsetAsync(st, 0, sizeof(FrameStatus) * (size_t)nf, stream));
+    const bool timed = g.timed;
     const sgs::Event* ev = nullptr;
     if (timed) {
         if ((rc = ensure_timing_events(ctx)) != SGS_OK) return rc;
-        ev = slot_events(ctx, slot0);
+        ev = R.events(g.slot0);
     }
-    for (int f = 0; f < nf; ++f) ctx->slot_timed[slot0 + f] = timed && f == 0;
+    for (int f = 0; f < nf; ++f) R.timed[g.slot0 + f] = timed && f == 0;
     if (timed) SGS_HIP(ctx, hipEventRecord(ev[0].e, stream));
 
     launch_project(ctx, G, nf, stream);
     if (timed) SGS_HIP(ctx, hipEventRecord(ev[1].e, stream));
     launch_binning(ctx, G, nf, stream, timed ? ev[2].e : nullptr);
     if (timed) SGS_HIP(ctx, hipEventRecord(ev[3].e, stream));
-    launch_composite(G, nf, stream, out_aux != nullptr, (cfg.flags & SGS_FLAG_STATS) != 0, need_tf_of(cfg, out_aux));
+    launch_composite(G, nf, stream, g.out_aux != nullptr, (g.cfg->flags & SGS_FLAG_STATS) != 0, need_tf_of(*g.cfg, g.out_aux));
     if (timed) SGS_HIP(ctx, hipEventRecord(ev[4].e, stream));
     SGS_HIP(ctx, hipGetLastError());
     if (!in_batch) {
-        SGS_HIP(ctx, hipMemcpyAsync(ctx->h_status.p + slot0, st, sizeof(FrameStatus) * (size_t)nf, hipMemcpyDeviceToHost, stream));
-        if (pipelined) {
+        SGS_HIP(ctx, hipMemcpyAsync(R.h_status.p + g.slot0, st, sizeof(FrameStatus) * (size_t)nf, hipMemcpyDeviceToHost, stream));
+        if (g.mode == Issue::lane) {
             SGS_HIP(ctx, hipEventRecord(L.done.e, L.stream.s));
             L.busy = true;
         }
     }
 
-    note_last(ctx, scene, &cams[nf - 1], P, row_begin, row_end, slot0 + nf - 1, set0 + nf - 1, timed, caller_stream);    // "the last frame" = the group's last
+    first = FrameRec();
+    first.slot = g.slot0; first.lane = g.lane0; first.stream = g.caller_stream; first.timed = timed;
+    first.scene = g.scene; first.n = g.scene->n; first.sh_rows = g.scene->sh_rows;
+    first.pixels = g.band.pixel_rows * g.cams->width;
+    first.T = P.gx * P.gy; first.t_lo = P.row_begin * P.gx; first.t_hi = P.row_end * P.gx; first.tiles = first.t_hi - first.t_lo;
     return SGS_OK;
 }
 
@@ -701,22 +740,23 @@ int enqueue_group(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, 
 // super-tile queues take half the capacity) — an overflow at level 1 leaves d_total at 0.
 int64_t records_needed(const FrameStatus& s) { return std::max<int64_t>((int64_t)s.d_total, 2 * (int64_t)s.ds_total); }
 
-// Fill `stats` from the (already synchronised) status of ring slot `slot`.
-void collect(sgs_ctx* ctx, int slot, sgs_stats* stats, int64_t n, int ntiles, int64_t pixels, int sh_rows,
-             bool timed) {
+// Fill `stats` from the (already synchronised) status of the frame r.
+void collect(const StatusRing& R, const FrameRec& r, sgs_stats* stats) {
     if (!stats) return;
-    const FrameStatus& s = ctx->h_status.p[slot];
+    const FrameStatus& s = R.h_status.p[r.slot];
+    const int64_t n = r.n, pixels = r.pixels;
+    const int sh_rows = r.sh_rows;
     memset(stats, 0, sizeof *stats);
     stats->n_gaussians = n;
     stats->n_visible = s.n_visible;
     stats->d_total = s.d_total;
     stats->d_fetched = (int64_t)s.d_fetched;
     stats->n_pixels = pixels;
-    stats->n_tiles = ntiles;
+    stats->n_tiles = r.tiles;
     stats->max_tile_len = (int32_t)s.max_tile_len;
     stats->n_spill_tiles = (int32_t)s.class_count[3];
     stats->n_deep_windows = (int64_t)s.n_deep;
-    stats->retries = ctx->last_retries;
+    stats->retries = r.retries;
     // Algorithmic bytes per stage — DESIGN.md §4 (what the stage must move, not what it happens to).
     const int64_t nv = s.n_visible, D = s.d_total, Df = (int64_t)s.d_fetched;
     stats->bytes[SGS_STAGE_PREPROCESS] = 16 * n + (32 + 16 * (int64_t)sh_rows + 64 + 16) * nv;   // rows read; splat + binning record written
@@ -725,10 +765,10 @@ void collect(sgs_ctx* ctx, int slot, sgs_stats* stats, int64_t n, int ntiles, in
     const int64_t Ds = s.ds_total;
     stats->d_super = Ds;
     stats->bytes[SGS_STAGE_COUNT] = 2 * 16 * nv + 16 * Ds;
-    stats->bytes[SGS_STAGE_EMIT] = 2 * 16 * Ds + 8 * D + 8 * ((int64_t)ctx->last_T + 1);
+    stats->bytes[SGS_STAGE_EMIT] = 2 * 16 * Ds + 8 * D + 8 * ((int64_t)r.T + 1);
     stats->bytes[SGS_STAGE_RENDER] = 8 * D + 36 * Df + 12 * pixels;               // every record seen once, D_f splats blended
-    if (timed && ctx->ev) {
-        const sgs::Event* ev = slot_events(ctx, slot);
+    if (r.timed && R.ev) {
+        const sgs::Event* ev = R.events(r.slot);
         for (int i = 0; i < SGS_NUM_STAGES; ++i) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e) == hipSuccess) stats->ms[i] = ms;
@@ -784,8 +824,8 @@ int sgs_create(int device_id, int backend, sgs_ctx** out) {
         return SGS_ERR_HIP;
     };
     if ((e = hipSetDevice(device_id)) != hipSuccess) return fail("hipSetDevice", e);
-    if ((e = ctx->d_status.grow(kStatusRing)) != hipSuccess) return fail("the status ring", e);
-    if ((e = ctx->h_status.grow(kStatusRing)) != hipSuccess) return fail("the pinned status ring", e);
+    if ((e = ctx->ring.d_status.grow(kStatusRing)) != hipSuccess) return fail("the status ring", e);
+    if ((e = ctx->ring.h_status.grow(kStatusRing)) != hipSuccess) return fail("the pinned status ring", e);
     if ((e = ctx->row_acc.grow(SGS_MAX_ROWS)) != hipSuccess) return fail("the row counters", e);
     if ((e = hipMemset(ctx->row_acc.p, 0, sizeof(unsigned long long) * SGS_MAX_ROWS)) != hipSuccess) return fail("hipMemset", e);
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return fail("hipStreamSynchronize", e);
@@ -1065,43 +1105,43 @@ int sgs_scene_upload_compressed(sgs_ctx* ctx, const sgs_compressed_scene* z, int
 int sgs_scene_free(sgs_ctx* ctx, sgs_scene* scene) {
     if (!scene) return SGS_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipDeviceSynchronize(); }
-    if (ctx && ctx->last_scene == scene) ctx->last_scene = nullptr;
+    if (ctx && ctx->last.scene == scene) ctx->last.scene = nullptr;
     delete scene;
     return SGS_OK;
 }
 
 int sgs_frame_sync(sgs_ctx* ctx, sgs_stats* stats) {
     if (!ctx) return SGS_ERR_INVALID;
-    if (ctx->last_slot < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "no frame has been issued");
+    if (ctx->last.slot < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "no frame has been issued");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
-    SGS_HIP(ctx, hipStreamSynchronize(ctx->last_stream));
+    SGS_HIP(ctx, hipStreamSynchronize(ctx->last.stream));
     { int rc_ = drain_lanes(ctx); if (rc_ != SGS_OK) return rc_; }
-    collect(ctx, ctx->last_slot, stats, ctx->last_n, ctx->last_tiles, ctx->last_pixels, ctx->last_sh_rows, ctx->last_timed);
+    StatusRing& R = ctx->ring;
+    collect(R, ctx->last, stats);
     // every frame issued since the previous synchronisation is checked, not just the last one
     int bad = -1, n_bad = 0;
     double ms_sum[SGS_NUM_STAGES + 1] = {};
     int n_timed = 0;
-    for (int k = 0; k < ctx->pending_count; ++k) {
-        const int slot = (ctx->pending_begin + k) % kStatusRing;
-        if (ctx->h_status.p[slot].overflow) { bad = slot; ++n_bad; }
-        if (ctx->slot_timed[slot] && ctx->ev) {
-            const sgs::Event* ev = slot_events(ctx, slot);
+    R.for_pending([&](int slot) {
+        if (R.h_status.p[slot].overflow) { bad = slot; ++n_bad; }
+        if (R.timed[slot] && R.ev) {
+            const sgs::Event* ev = R.events(slot);
             float ms = 0.f;
             for (int i = 0; i < SGS_NUM_STAGES; ++i)
                 if (hipEventElapsedTime(&ms, ev[i].e, ev[i + 1].e) == hipSuccess) ms_sum[i] += ms;
             if (hipEventElapsedTime(&ms, ev[0].e, ev[SGS_NUM_STAGES].e) == hipSuccess) ms_sum[SGS_NUM_STAGES] += ms;
             ++n_timed;
         }
-    }
+    });
     if (stats && n_timed > 1) {          // several pipelined frames: report the per-frame average
         for (int i = 0; i < SGS_NUM_STAGES; ++i) stats->ms[i] = (float)(ms_sum[i] / n_timed);
         stats->ms_total = (float)(ms_sum[SGS_NUM_STAGES] / n_timed);
     }
-    ctx->pending_begin = ctx->next_slot; ctx->pending_count = 0;
+    R.seen();
     if (n_bad)
         SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "%d frame(s) overflowed the record capacity %lld (one needs at least %lld records: D = %u, D_s = %u "
                  "super-tile records of which the capacity holds half as many); call sgs_set_record_capacity", n_bad,
-                 (long long)ctx->lanes[0].rec.cap, (long long)records_needed(ctx->h_status.p[bad]), ctx->h_status.p[bad].d_total, ctx->h_status.p[bad].ds_total);
+                 (long long)ctx->lanes[0].rec.cap, (long long)records_needed(R.h_status.p[bad]), R.h_status.p[bad].d_total, R.h_status.p[bad].ds_total);
     return SGS_OK;
 }
 
@@ -1110,42 +1150,38 @@ int sgs_render_rgbd(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam,
                     void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
     int rc;
-    int z = 0;                                       // the frame's fine-tile shift (fine_shift_of)
     // out_aux is a full-frame buffer (sage_gs.h): the compact image of interleaved rows has no depth / coverage counterpart
     if (out_aux && cfg_in && cfg_in->tile_row_stride > 1)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "out_aux with interleaved tile rows (tile_row_stride %d) is not supported", cfg_in->tile_row_stride);
-    if ((rc = validate(ctx, scene, cam, cfg_in, tile_row_begin, tile_row_end, out_rgb, &z)) != SGS_OK) return rc;
     sgs_config cfg;
     if (cfg_in) cfg = *cfg_in; else sgs_config_default(&cfg);
+    float* outs[1] = {out_rgb};
+    Group g = {scene, cam, 1, &cfg, Band(), outs, out_aux, 0, 0, 0, static_cast<hipStream_t>(hip_stream), (cfg.flags & SGS_FLAG_TIMING) != 0, Issue::caller};
+    if ((rc = validate(ctx, scene, cam, cfg_in, tile_row_begin, tile_row_end, out_rgb, g.band)) != SGS_OK) return rc;
     SGS_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const bool timed = (cfg.flags & SGS_FLAG_TIMING) != 0;
-    ctx->last_retries = 0;
-    for (;;) {
-        if (ctx->pending_count == kStatusRing) {        // the status ring is full: drain it first
-            if ((rc = sgs_frame_sync(ctx, nullptr)) != SGS_OK) return rc;
-        }
-        const int slot = ctx->next_slot;
-        ctx->next_slot = (ctx->next_slot + 1) % kStatusRing;
-        if (ctx->pending_count == 0) ctx->pending_begin = slot;
-        ctx->pending_count++;
-        const bool pipelined = (cfg.flags & SGS_FLAG_PIPELINED) && (cfg.flags & SGS_FLAG_ASYNC) && ctx->n_lanes > 1 &&
-                               !(cfg.flags & SGS_FLAG_FULL_SORT);
-        int lane = 0;
-        if (pipelined) { lane = ctx->next_lane; ctx->next_lane = (ctx->next_lane + 1) % ctx->n_lanes; }
-        float* outs[1] = {out_rgb};
-        if ((rc = enqueue_group(ctx, scene, cam, 1, cfg, tile_row_begin, tile_row_end, outs, slot, stream, timed, out_aux,
-                                pipelined, false, lane, z)) != SGS_OK)
-            return rc;
+    const bool pipelined = (cfg.flags & SGS_FLAG_PIPELINED) && (cfg.flags & SGS_FLAG_ASYNC) && ctx->n_lanes > 1 &&
+                           !(cfg.flags & SGS_FLAG_FULL_SORT);
+    if (pipelined) g.mode = Issue::lane;
+    StatusRing& R = ctx->ring;
+    for (int retries = 0;;) {
+        if (R.full() && (rc = sgs_frame_sync(ctx, nullptr)) != SGS_OK) return rc;        // the status ring is full: drain it first
+        g.slot0 = R.slot();
+        if (pipelined) g.lane0 = ctx->next_lane;
+        FrameRec rec;
+        if ((rc = enqueue_group(ctx, g, rec)) != SGS_OK) return rc;          // (the slot was not taken: nothing will write its status word)
+        R.issued();
+        if (pipelined) ctx->next_lane = (ctx->next_lane + 1) % ctx->n_lanes;
+        rec.retries = retries;
+        ctx->last = rec;
         if (cfg.flags & SGS_FLAG_ASYNC) return SGS_OK;
         rc = sgs_frame_sync(ctx, stats);
         if (rc != SGS_ERR_OVERFLOW) return rc;
         // synchronous path: grow the queues to fit and render again.  A frame can overflow at level 1 of the binning (the super-tile
         // queues hold rec_cap / 2 records of 16 bytes): level 2 then never ran and d_total is 0 — what is known is D_s
-        const int64_t need = records_needed(ctx->h_status.p[slot]);
+        const int64_t need = records_needed(R.h_status.p[rec.slot]);
         ctx->rec_cap_wanted = std::max<int64_t>(need + need / 4, ctx->lanes[0].rec.cap * 2);
         if ((rc = ensure_records(ctx, ctx->lanes[0])) != SGS_OK) return rc;
-        if (++ctx->last_retries > 4) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "record capacity still too small after 4 retries");
+        if (++retries > 4) SGS_FAIL(ctx, SGS_ERR_OVERFLOW, "record capacity still too small after 4 retries");
     }
 }
 
@@ -1153,6 +1189,92 @@ int sgs_render(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cam, cons
                int tile_row_begin, int tile_row_end, float* out_rgb, sgs_stats* stats, void* hip_stream) {
     return sgs_render_rgbd(ctx, scene, cam, cfg, tile_row_begin, tile_row_end, out_rgb, nullptr, stats, hip_stream);
 }
+
+namespace {
+
+// ---- sgs_render_batch_strided, step by step ----
+
+// Every camera (and the stride) is validated BEFORE anything is enqueued; bands[i] = frame i's band (the fine-tile shift is a function
+// of its camera).
+int validate_batch(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, int n_cams, const sgs_config& cfg, int row_begin,
+                   int row_end, const float* out_rgb, int64_t frame_stride, std::vector<Band>& bands) {
+    int rc;
+    for (int i = 0; i < n_cams; ++i) {
+        if ((rc = validate(ctx, scene, &cams[i], &cfg, row_begin, row_end, out_rgb, bands[(size_t)i])) != SGS_OK) return rc;
+        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
+            SGS_FAIL(ctx, SGS_ERR_INVALID, "the cameras of a batch must share a resolution");
+    }
+    if (n_cams > 1) {
+        const int64_t band_floats = bands[0].pixel_rows * (int64_t)cams[0].width * 3;       // what one frame of the batch writes
+        if (frame_stride < band_floats)
+            SGS_FAIL(ctx, SGS_ERR_INVALID, "frame_stride %lld is smaller than the band a frame writes (%lld floats)",
+                     (long long)frame_stride, (long long)band_floats);
+    }
+    return SGS_OK;
+}
+
+// The plan of a chunk of cn frames: its groups, in issue order — a function of cn, F = sgs_tuning.group, the number GL of group streams
+// and the frames' fine-tile shifts alone.
+// The chunk's frames are dealt to the group streams in EQUAL shares (the stream with an extra group finished it alone, without a
+// neighbour's kernels to overlap with; more than four frames are worth a second stream), each share cut into EQUAL groups of <= F:
+// 20 frames on two streams are 5,5 + 5,5 under F = 8 (not 8,2 + 8,2: the frames of a group share their reads of the scene and their
+// launches, a group of two shares little).
+struct PlannedGroup { int first, count, stream; };
+int plan_chunk(int cn, int F, int GL, const Band* bands, PlannedGroup* plan) {
+    const int n_streams = std::min(GL, (cn + 3) / 4);
+    int left[kMaxLanes], todo[kMaxLanes];           // frames / groups each stream still has to issue
+    for (int sidx = 0; sidx < n_streams; ++sidx) {
+        left[sidx] = cn / n_streams + (sidx < cn % n_streams ? 1 : 0);
+        todo[sidx] = (left[sidx] + F - 1) / F;
+    }
+    int n_groups = 0;
+    for (int i = 0, g = 0; i < cn; ++g) {
+        const int sidx = g % n_streams;
+        if (left[sidx] <= 0) continue;
+        if (todo[sidx] <= 0) todo[sidx] = (left[sidx] + F - 1) / F;       // (a group that ended early, below, left frames behind)
+        int nf = (left[sidx] + todo[sidx] - 1) / todo[sidx];
+        --todo[sidx];
+        // (the frames of a group share one set of launches, hence one grid of tiles: a group ends where the fine-tile shift changes)
+        for (int f = 1; f < nf; ++f) if (bands[i + f].z != bands[i].z) { nf = f; break; }
+        left[sidx] -= nf;
+        plan[n_groups++] = {i, nf, sidx};
+        i += nf;
+    }
+    return n_groups;
+}
+
+// From the first enqueue of a chunk on, NO way out of the batch leaves work running that nobody waits for: going out of scope armed
+// (an error return) waits for the group streams and the caller's.  The success path calls wait() itself, which disarms.
+struct ChunkJoin {
+    sgs_ctx* ctx; hipStream_t stream; int n_lane_streams;
+    bool armed;
+    hipError_t wait() {          // (every stream is waited for, whatever an earlier one returned)
+        armed = false;
+        hipError_t e = hipSuccess;
+        for (int gl = 0; gl <= n_lane_streams; ++gl) {
+            const hipError_t e1 = hipStreamSynchronize(gl < n_lane_streams ? ctx->lanes[gl].stream.s : stream);
+            if (e == hipSuccess) e = e1;
+        }
+        return e;
+    }
+    ~ChunkJoin() { if (armed) (void)wait(); }
+};
+
+// Once per chunk of frames, not once per frame: zero the status slots, fork the group streams from the caller's.
+int begin_chunk(sgs_ctx* ctx, int cn, int GL, bool lanes, hipStream_t stream) {
+    int rc;
+    SGS_HIP(ctx, hipMemsetAsync(ctx->ring.d_status.p + ctx->ring.take_chunk(), 0, sizeof(FrameStatus) * (size_t)cn, stream));
+    if (!lanes) return SGS_OK;
+    if ((rc = ensure_lane_stream(ctx, ctx->lanes[0])) != SGS_OK) return rc;
+    SGS_HIP(ctx, hipEventRecord(ctx->lanes[0].fork.e, stream));
+    for (int gl = 0; gl < GL; ++gl) {
+        if ((rc = ensure_lane_stream(ctx, ctx->lanes[gl])) != SGS_OK) return rc;
+        SGS_HIP(ctx, hipStreamWaitEvent(ctx->lanes[gl].stream.s, ctx->lanes[0].fork.e, 0));
+    }
+    return SGS_OK;
+}
+
+}  // namespace
 
 int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, int n_cams,
                              const sgs_config* cfg_in, int tile_row_begin, int tile_row_end, float* out_rgb,
@@ -1164,96 +1286,48 @@ int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_cam
     cfg.flags &= ~(uint32_t)SGS_FLAG_TIMING;       // per-stage events are a single-frame facility
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    ctx->last_retries = 0;
+    StatusRing& R = ctx->ring;
     int rc;
-    if (ctx->pending_count > 0 && (rc = sgs_frame_sync(ctx, nullptr)) != SGS_OK) return rc;
+    if (!R.idle() && (rc = sgs_frame_sync(ctx, nullptr)) != SGS_OK) return rc;
     const bool lanes = !(cfg.flags & SGS_FLAG_FULL_SORT);           // own streams (the FULL_SORT test hook stays on the caller's)
     const int F = ctx->group, GL = lanes ? ctx->group_lanes : 1;
-    // every camera (and the stride) is validated BEFORE anything is enqueued: an error return half-way through a batch
-    // would leave earlier groups running on the lane streams with nobody waiting for them
-    int rb0 = tile_row_begin, re0 = tile_row_end;
-    std::vector<signed char> zs((size_t)std::max(n_cams, 1), 0);     // every frame's fine-tile shift (fine_shift_of: a function of its camera)
-    for (int i = 0; i < n_cams; ++i) {
-        int rb = tile_row_begin, re = tile_row_end, z = 0;
-        if ((rc = validate(ctx, scene, &cams[i], &cfg, rb, re, out_rgb, &z)) != SGS_OK) return rc;
-        zs[(size_t)i] = (signed char)z;
-        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
-            SGS_FAIL(ctx, SGS_ERR_INVALID, "the cameras of a batch must share a resolution");
-        if (i == 0) { rb0 = rb; re0 = re; }
-    }
-    if (n_cams > 1) {
-        const int stride_t = cfg.tile_row_stride > 1 ? cfg.tile_row_stride : 1, phase_t = stride_t > 1 ? cfg.tile_row_phase : 0;
-        const int64_t rows = band_pixel_rows(cams[0].height, rb0, re0, stride_t, phase_t);     // pixel rows one frame of the batch writes
-        if (frame_stride < rows * (int64_t)cams[0].width * 3)
-            SGS_FAIL(ctx, SGS_ERR_INVALID, "frame_stride %lld is smaller than the band a frame writes (%lld floats)",
-                     (long long)frame_stride, (long long)(rows * (int64_t)cams[0].width * 3));
-    }
+    std::vector<Band> bands((size_t)std::max(n_cams, 1));
+    if ((rc = validate_batch(ctx, scene, cams, n_cams, cfg, tile_row_begin, tile_row_end, out_rgb, frame_stride, bands)) != SGS_OK) return rc;
     for (int c0 = 0; c0 < n_cams; c0 += kStatusRing) {
         const int cn = std::min(kStatusRing, n_cams - c0);
-        int64_t px[kStatusRing]; int tl[kStatusRing];
-        // once per chunk of frames, not once per frame: zero the status slots, fork the group streams from the caller's
-        SGS_HIP(ctx, hipMemsetAsync(ctx->d_status.p, 0, sizeof(FrameStatus) * (size_t)cn, stream));
-        if (lanes) {
-            if ((rc = ensure_lane_stream(ctx, ctx->lanes[0])) != SGS_OK) return rc;
-            SGS_HIP(ctx, hipEventRecord(ctx->lanes[0].fork.e, stream));
-            for (int gl = 0; gl < GL; ++gl) {
-                if ((rc = ensure_lane_stream(ctx, ctx->lanes[gl])) != SGS_OK) return rc;
-                SGS_HIP(ctx, hipStreamWaitEvent(ctx->lanes[gl].stream.s, ctx->lanes[0].fork.e, 0));
-            }
-        }
-        // The chunk's frames are dealt to the group streams in EQUAL shares (the stream with an extra group finished it alone, without a
-        // neighbour's kernels to overlap with; more than four frames are worth a second stream), each share cut into EQUAL groups of <= F:
-        // 20 frames on two streams are 5,5 + 5,5 under F = 8 (not 8,2 + 8,2: the frames of a group share their reads of the scene and their
-        // launches, a group of two shares little).
-        const int n_streams = lanes ? std::min(GL, (cn + 3) / 4) : 1;
-        int left[kMaxLanes], todo[kMaxLanes];           // frames / groups each stream still has to issue
-        for (int sidx = 0; sidx < n_streams; ++sidx) {
-            left[sidx] = cn / n_streams + (sidx < cn % n_streams ? 1 : 0);
-            todo[sidx] = (left[sidx] + F - 1) / F;
-        }
-        for (int i = 0, g = 0; i < cn; ++g) {
-            const int sidx = g % n_streams;
-            if (left[sidx] <= 0) continue;
-            if (todo[sidx] <= 0) todo[sidx] = (left[sidx] + F - 1) / F;       // (a group that ended early, below, left frames behind)
-            int nf = (left[sidx] + todo[sidx] - 1) / todo[sidx];
-            --todo[sidx];
-            // (the frames of a group share one set of launches, hence one grid of tiles: a group ends where the fine-tile shift changes)
-            for (int f = 1; f < nf; ++f) if (zs[(size_t)(c0 + i + f)] != zs[(size_t)(c0 + i)]) { nf = f; break; }
-            left[sidx] -= nf;
+        FrameRec recs[kStatusRing];
+        PlannedGroup plan[kStatusRing];
+        const int n_groups = plan_chunk(cn, F, GL, &bands[(size_t)c0], plan);
+        if ((rc = begin_chunk(ctx, cn, GL, lanes, stream)) != SGS_OK) return rc;
+        ChunkJoin join = {ctx, stream, lanes ? GL : 0, true};
+        for (int k = 0; k < n_groups; ++k) {
+            const PlannedGroup& pg = plan[k];
             float* outs[SGS_MAX_GROUP];
-            const int rb = rb0, re = re0;
-            for (int f = 0; f < nf; ++f) outs[f] = out_rgb + (size_t)(c0 + i + f) * (size_t)frame_stride;
-            if ((rc = enqueue_group(ctx, scene, &cams[c0 + i], nf, cfg, rb, re, outs, i, stream, false, nullptr, lanes, true,
-                                    sidx * F, zs[(size_t)(c0 + i)], sidx)) != SGS_OK)
-                return rc;
-            for (int f = 0; f < nf; ++f) { px[i + f] = ctx->last_pixels; tl[i + f] = ctx->last_tiles; }
-            i += nf;
+            for (int f = 0; f < pg.count; ++f) outs[f] = out_rgb + (size_t)(c0 + pg.first + f) * (size_t)frame_stride;
+            const Group g = {scene, &cams[c0 + pg.first], pg.count, &cfg, bands[(size_t)(c0 + pg.first)], outs, nullptr, pg.first, pg.stream * F,
+                             pg.stream, stream, false, lanes ? Issue::batch_lanes : Issue::batch_caller};
+            if ((rc = enqueue_group(ctx, g, recs[pg.first])) != SGS_OK) return rc;
+            for (int f = 1; f < pg.count; ++f) { recs[pg.first + f] = recs[pg.first]; recs[pg.first + f].slot += f; recs[pg.first + f].lane += f; }
         }
+        ctx->last = recs[cn - 1];
         // ... wait for the lanes and fetch every frame's status in one copy
-        if (lanes) for (int gl = 0; gl < GL; ++gl) SGS_HIP(ctx, hipStreamSynchronize(ctx->lanes[gl].stream.s));
-        SGS_HIP(ctx, hipStreamSynchronize(stream));
+        SGS_HIP(ctx, join.wait());
         if ((rc = drain_lanes(ctx)) != SGS_OK) return rc;           // (frames issued outside this call)
-        SGS_HIP(ctx, hipMemcpy(ctx->h_status.p, ctx->d_status.p, sizeof(FrameStatus) * (size_t)cn, hipMemcpyDeviceToHost));
-        // The redo below goes through sgs_render, which takes ring slots of its own (from next_slot, two or more per
-        // grow-and-retry) — i.e. slots of frames of THIS chunk that have not been looked at yet.  So every frame's
-        // verdict and statistics are taken out of the ring before anything is re-rendered.
+        SGS_HIP(ctx, hipMemcpy(R.h_status.p, R.d_status.p, sizeof(FrameStatus) * (size_t)cn, hipMemcpyDeviceToHost));
+        // the redo's own frames take ring slots again — these (a full chunk leaves no others) — so every verdict is read out first
         bool over[kStatusRing];
         for (int i = 0; i < cn; ++i) {
-            over[i] = ctx->h_status.p[i].overflow != 0;
-            if (stats) collect(ctx, i, stats + c0 + i, scene->n, tl[i], px[i], scene->sh_rows, false);
+            over[i] = R.h_status.p[i].overflow != 0;
+            if (stats) collect(R, recs[i], stats + c0 + i);
         }
-        ctx->next_slot = 0; ctx->pending_begin = 0; ctx->pending_count = 0;
         for (int i = 0; i < cn; ++i) {
-            if (over[i]) {
-                // redo this one frame synchronously (grows the queues), then carry on
-                int rb = tile_row_begin, re = tile_row_end;
-                float* out = out_rgb + (size_t)(c0 + i) * (size_t)frame_stride;
-                sgs_config c1 = cfg; c1.flags &= ~(uint32_t)(SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED);
-                if ((rc = sgs_render(ctx, scene, &cams[c0 + i], &c1, rb, re, out, stats ? stats + c0 + i : nullptr, hip_stream)) != SGS_OK)
-                    return rc;
-            }
+            if (!over[i]) continue;
+            // redo this one frame synchronously (grows the queues), then carry on
+            sgs_config c1 = cfg; c1.flags &= ~(uint32_t)(SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED);
+            if ((rc = sgs_render(ctx, scene, &cams[c0 + i], &c1, tile_row_begin, tile_row_end, out_rgb + (size_t)(c0 + i) * (size_t)frame_stride,
+                                 stats ? stats + c0 + i : nullptr, hip_stream)) != SGS_OK)
+                return rc;
         }
-        ctx->next_slot = 0; ctx->pending_begin = 0; ctx->pending_count = 0;
     }
     return SGS_OK;
 }
@@ -1261,12 +1335,7 @@ int sgs_render_batch_strided(sgs_ctx* ctx, const sgs_scene* scene, const sgs_cam
 int sgs_render_batch(sgs_ctx* ctx, const sgs_scene* scene, const sgs_camera* cams, int n_cams,
                      const sgs_config* cfg_in, int tile_row_begin, int tile_row_end, float* out_rgb,
                      sgs_stats* stats, void* hip_stream) {
-    if (!ctx) return SGS_ERR_INVALID;
-    if (n_cams < 0 || (n_cams > 0 && !cams)) SGS_FAIL(ctx, SGS_ERR_INVALID, "bad camera array");
-    for (int i = 1; i < n_cams; ++i)
-        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height)
-            SGS_FAIL(ctx, SGS_ERR_INVALID, "the cameras of a batch must share a resolution");
-    const int64_t stride = n_cams > 0 ? (int64_t)cams[0].width * cams[0].height * 3 : 0;
+    const int64_t stride = n_cams > 0 && cams ? (int64_t)cams[0].width * cams[0].height * 3 : 0;       // dense frames
     return sgs_render_batch_strided(ctx, scene, cams, n_cams, cfg_in, tile_row_begin, tile_row_end, out_rgb, stride, stats, hip_stream);
 }
 
@@ -1296,138 +1365,163 @@ int sgs_pack_rgba8(sgs_ctx* ctx, const float* rgb, uint8_t* rgba, int width, int
     return SGS_OK;
 }
 
+namespace {
+
+// ---- sgs_debug_read's host-side decodes: n bytes of a buffer into host_dst, each from the device arrays as the kernels keep them ----
+
+// the tile offsets: k_tile_scan writes those of the band it rendered (and the band's end); outside it they are constant
+int read_tile_offsets(sgs_ctx* ctx, const FrameRec& r, const Lane& L, void* host_dst, int64_t n) {
+    const size_t cnt = (size_t)r.T + 1;
+    std::vector<unsigned> tmp(cnt);
+    SGS_HIP(ctx, hipMemcpy(tmp.data(), L.tile_offset.p, cnt * 4, hipMemcpyDeviceToHost));
+    const unsigned total = tmp[(size_t)r.t_hi];
+    for (int64_t i = 0; (i + 1) * 4 <= n; ++i)
+        ((unsigned*)host_dst)[i] = i < r.t_lo ? 0u : i >= r.t_hi ? total : tmp[(size_t)i];
+    return SGS_OK;
+}
+
+// the scene's geometry rows, back in the caller's order: [N, 11]
+int read_scene_geom(sgs_ctx* ctx, const sgs_scene* sc, int64_t n_slots, void* host_dst, int64_t n) {
+    std::vector<float4> rows((size_t)n_slots * SGS_GEOM_ROWS);
+    SGS_HIP(ctx, hipMemcpy(rows.data(), sc->geom.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    float* dst = (float*)host_dst;
+    for (int64_t p = 0; p < sc->n; ++p) {
+        const int64_t chunk = p >> 6, lane = p & 63;
+        const float4 g0 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 0) * 64 + lane)], g1 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 1) * 64 + lane)],
+                     g2 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 2) * 64 + lane)];
+        unsigned i; memcpy(&i, &g2.w, 4);
+        if ((int64_t)(i + 1) * 11 * 4 > n) continue;
+        float* o = dst + (size_t)i * 11;
+        o[0] = g0.x; o[1] = g0.y; o[2] = g0.z; o[3] = g0.w; o[4] = g1.x; o[5] = g1.y; o[6] = g1.z; o[7] = g1.w; o[8] = g2.x; o[9] = g2.y; o[10] = g2.z;
+    }
+    return SGS_OK;
+}
+
+// the scene's SH coefficients as k_preprocess evaluates them, back in the caller's order: [N, K, 3] fp32
+int read_scene_sh(sgs_ctx* ctx, const sgs_scene* sc, int64_t n_slots, void* host_dst, int64_t n) {
+    const int nf = 3 * (sc->sh_degree + 1) * (sc->sh_degree + 1), rows_n = sc->sh_rows;
+    std::vector<float4> rows((size_t)n_slots * rows_n), geo((size_t)n_slots * SGS_GEOM_ROWS);
+    SGS_HIP(ctx, hipMemcpy(rows.data(), sc->shq.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    SGS_HIP(ctx, hipMemcpy(geo.data(), sc->geom.p, geo.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    float* dst = (float*)host_dst;
+    std::vector<unsigned> w((size_t)rows_n * 4);
+    for (int64_t p = 0; p < sc->n; ++p) {
+        const int64_t chunk = p >> 6, lane = p & 63;
+        unsigned i; memcpy(&i, &geo[(size_t)((chunk * SGS_GEOM_ROWS + 2) * 64 + lane)].w, 4);       // the original index
+        if ((int64_t)(i + 1) * nf * 4 > n) continue;
+        for (int r = 0; r < rows_n; ++r) memcpy(&w[(size_t)4 * r], &rows[(size_t)((chunk * rows_n + r) * 64 + lane)], 16);
+        float* o = dst + (size_t)i * nf;
+        if (!sc->sh_packed) memcpy(o, w.data(), (size_t)nf * 4);
+        else {      // 12 B of fp32 DC, then a byte per coefficient: v / 32 - 4 + 1 / 64, exact in fp32 (sgs_kernels.h sgs_sh_byte)
+            memcpy(o, w.data(), 12);
+            for (int j = 0; j < nf - 3; ++j) {      // sgs_kernels.h sgs_sh_byte / sgs_sh_byte_mode, restated: one correctly rounded fma (exact in double, rounded once)
+                const unsigned v = (w[(size_t)3 + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
+                volatile double prod = (double)v * (8.0 / 255.0);         // (two roundings, as the kernel's __dmul_rn / __dsub_rn)
+                float x = sc->sh_decode == 1 ? (float)(prod - 4.0) : (float)((double)v * (1.0 / 32.0) + (-4.0 + 1.0 / 64.0));
+                if (sc->sh_decode == 2) x = v == 0u ? -4.0f : v == 255u ? 4.0f : x;
+                o[3 + j] = x;
+            }
+        }
+    }
+    return SGS_OK;
+}
+
+// per chunk: 1 = the per-chunk bounds skipped it (no slot live, every slot "big": k_chunk_cull's mark)
+int read_chunk_skipped(sgs_ctx* ctx, const Lane& L, int64_t n_chunks, void* host_dst, int64_t n) {
+    std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks)), bm(vm.size());
+    SGS_HIP(ctx, hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost));
+    SGS_HIP(ctx, hipMemcpy(bm.data(), L.bigmask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) ((unsigned char*)host_dst)[i] = vm[(size_t)i] == 0ull && bm[(size_t)i] == ~0ull;
+    return SGS_OK;
+}
+
+// device records (sgs_common.h: 64 B, conic pre-scaled for the composite, opacity also as an exponent offset) -> x,y,conic a,b | c,opacity,r,g | b,depth,rect01,rect23
+int read_splats(sgs_ctx* ctx, const Lane& L, void* host_dst, int64_t n, int64_t elem) {
+    const int64_t cnt = n / elem;
+    std::vector<Splat> tmp((size_t)std::max<int64_t>(1, cnt));
+    SGS_HIP(ctx, hipMemcpy(tmp.data(), L.splats.p, (size_t)cnt * sizeof(Splat), hipMemcpyDeviceToHost));
+    const double l2e = 1.4426950408889634;
+    for (int64_t i = 0; i < cnt; ++i) {
+        const Splat& sp = tmp[(size_t)i];
+        float* o = (float*)((char*)host_dst + i * elem);
+        o[0] = sp.x; o[1] = sp.y;
+        // (the record holds the roots of the completed square A (dx + k dy)^2 + C' dy^2 in the slots A, B, C: a = sqrt(A),
+        //  a k, c = +-sqrt(|C'|);  B = 2 A k = 2 a (a k),  C = A k^2 + C' = (a k)^2 + C')
+        const double a_ = sp.A, ak_ = sp.B, c_ = sp.C;
+        const double A_ = a_ * a_, Cp_ = c_ * std::fabs(c_);
+        o[2] = (float)(A_ / (0.5 * l2e)); o[3] = (float)(2.0 * a_ * ak_ / l2e); o[4] = (float)((ak_ * ak_ + Cp_) / (0.5 * l2e));
+        o[5] = sp.o; o[6] = sp.r; o[7] = sp.g; o[8] = sp.b;
+        memcpy(o + 9, &sp.key, 4); memcpy(o + 10, &sp.rect01, 4); memcpy(o + 11, &sp.rect23, 4);
+    }
+    return SGS_OK;
+}
+
+// A splat lives at its Gaussian's index; the per-chunk visibility masks say which are live.  Dead slots are blanked (slot ids ->
+// 0xFFFFFFFF, splats -> 0) so stale data cannot pass for live.
+int blank_dead_slots(sgs_ctx* ctx, const FrameRec& r, const Lane& L, bool slot_ids, void* host_dst, int64_t n, int64_t elem) {
+    const int64_t n_chunks = (r.n + 63) / 64, n_slots = n_chunks * 64;
+    std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks));
+    SGS_HIP(ctx, hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost));
+    char* dst = (char*)host_dst;
+    // vismask is indexed by layout position; slots by original index
+    const unsigned* perm = r.scene && !r.scene->perm_host.empty() ? r.scene->perm_host.data() : nullptr;
+    std::vector<unsigned char> live((size_t)n_slots, 0);
+    for (int64_t p = 0; p < r.n; ++p)
+        if ((vm[p >> 6] >> (p & 63)) & 1ull) live[perm ? perm[p] : (size_t)p] = 1;
+    for (int64_t i = 0; i < n_slots && (i + 1) * elem <= n; ++i) {
+        if (slot_ids) ((unsigned*)dst)[i] = live[(size_t)i] ? (unsigned)i : 0xFFFFFFFFu;
+        else if (!live[(size_t)i]) memset(dst + i * elem, 0, (size_t)elem);
+    }
+    return SGS_OK;
+}
+
+}  // namespace
+
 int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     if (!ctx) return SGS_ERR_INVALID;
-    if (ctx->last_slot < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "no frame has been rendered");
+    const FrameRec& r = ctx->last;
+    if (r.slot < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "no frame has been rendered");
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     SGS_HIP(ctx, hipDeviceSynchronize());
-    const FrameStatus& s = ctx->h_status.p[ctx->last_slot];
-    const Lane& L = ctx->lanes[ctx->last_lane];
-    const int64_t n_chunks = (ctx->last_n + 63) / 64;
+    const FrameStatus& s = ctx->ring.h_status.p[r.slot];
+    const Lane& L = ctx->lanes[r.lane];
+    const sgs_scene* sc = r.scene;
+    const int64_t n_chunks = (r.n + 63) / 64;
     const int64_t n_slots = n_chunks * 64;
     // (a growth that failed since that frame has emptied what it was replacing)
-    if (!L.splats.holds(n_slots) || !L.vismask.holds(n_chunks) || !L.bigmask.holds(n_chunks) || !L.tile_offset.holds((int64_t)ctx->last_T + 1))
+    if (!L.splats.holds(n_slots) || !L.vismask.holds(n_chunks) || !L.bigmask.holds(n_chunks) || !L.tile_offset.holds((int64_t)r.T + 1))
         SGS_FAIL(ctx, SGS_ERR_INVALID, "the last frame's intermediates are gone: an allocation has failed since");
     const void* src = nullptr;
     int64_t have = 0, elem = 0;
     switch (what) {
-        case SGS_BUF_TILE_OFFSETS: have = ((int64_t)ctx->last_T + 1) * 4; break;       // every 8th sub-queue offset
+        case SGS_BUF_TILE_OFFSETS: have = ((int64_t)r.T + 1) * 4; break;       // every 8th sub-queue offset
         case SGS_BUF_SORTED_SLOTS: src = L.sorted_out.p; have = (s.overflow || !L.sorted_out.p) ? 0 : (int64_t)s.d_total * 4; break;
         case SGS_BUF_SLOT_IDS: elem = 4; have = n_slots * elem; break;
         case SGS_BUF_SPLATS: elem = 48; have = n_slots * elem; break;          // the 12-word view documented in sage_gs.h
         case SGS_BUF_CHUNK_SKIPPED: have = n_chunks; break;
-        case SGS_BUF_SCENE_GEOM: have = ctx->last_scene ? ctx->last_n * 11 * 4 : 0; break;
-        case SGS_BUF_SCENE_SH: have = ctx->last_scene ? ctx->last_n * 3 * (ctx->last_scene->sh_degree + 1) * (ctx->last_scene->sh_degree + 1) * 4 : 0; break;
-        case SGS_BUF_SCENE_PERM: have = ctx->last_scene ? ctx->last_n * 4 : 0; break;
-        case SGS_BUF_CHUNK_BOUNDS: src = ctx->last_scene ? ctx->last_scene->cbound.p : nullptr; have = src ? n_chunks * 32 : 0; break;
-        case 100: src = L.tile_prof.p; have = (int64_t)ctx->last_T * 8 * SGS_PROF_WORDS; break;    // profiling build only
+        case SGS_BUF_SCENE_GEOM: have = sc ? r.n * 11 * 4 : 0; break;
+        case SGS_BUF_SCENE_SH: have = sc ? r.n * 3 * (sc->sh_degree + 1) * (sc->sh_degree + 1) * 4 : 0; break;
+        case SGS_BUF_SCENE_PERM: have = sc ? r.n * 4 : 0; break;
+        case SGS_BUF_CHUNK_BOUNDS: src = sc ? sc->cbound.p : nullptr; have = src ? n_chunks * 32 : 0; break;
+        case 100: src = L.tile_prof.p; have = (int64_t)r.T * 8 * SGS_PROF_WORDS; break;    // profiling build only
         case 101: src = L.bin_prof.p; have = (int64_t)SGS_BIN_BLOCKS * 64; break;  // profiling build only
         default: SGS_FAIL(ctx, SGS_ERR_INVALID, "unknown buffer id %d", what);
     }
     const int64_t n = std::min(have, bytes);
     if (n <= 0 || !host_dst) return have;
+    int rc = SGS_OK;
     if (src) SGS_HIP(ctx, hipMemcpy(host_dst, src, (size_t)n, hipMemcpyDeviceToHost));
-    if (what == SGS_BUF_TILE_OFFSETS) {
-        const size_t cnt = (size_t)ctx->last_T + 1;
-        std::vector<unsigned> tmp(cnt);
-        SGS_HIP(ctx, hipMemcpy(tmp.data(), L.tile_offset.p, cnt * 4, hipMemcpyDeviceToHost));
-        // k_tile_scan writes the offsets of the band it rendered (and the band's end); outside it they are constant
-        const unsigned total = tmp[(size_t)ctx->last_t_hi];
-        for (int64_t i = 0; (i + 1) * 4 <= n; ++i)
-            ((unsigned*)host_dst)[i] = i < ctx->last_t_lo ? 0u : i >= ctx->last_t_hi ? total : tmp[(size_t)i];
-    }
+    if (what == SGS_BUF_TILE_OFFSETS) rc = read_tile_offsets(ctx, r, L, host_dst, n);
     if (what == SGS_BUF_SCENE_PERM) {      // the host copy layout_scene kept (empty: the scene is in the caller's order)
-        const std::vector<unsigned>& perm = ctx->last_scene->perm_host;
+        const std::vector<unsigned>& perm = sc->perm_host;
         for (int64_t p = 0; (p + 1) * 4 <= n; ++p) ((unsigned*)host_dst)[p] = perm.empty() ? (unsigned)p : perm[(size_t)p];
     }
-    if (what == SGS_BUF_SCENE_GEOM) {
-        std::vector<float4> rows((size_t)n_slots * SGS_GEOM_ROWS);
-        hipError_t e = hipMemcpy(rows.data(), ctx->last_scene->geom.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-        float* dst = (float*)host_dst;
-        for (int64_t p = 0; p < ctx->last_n; ++p) {
-            const int64_t chunk = p >> 6, lane = p & 63;
-            const float4 g0 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 0) * 64 + lane)], g1 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 1) * 64 + lane)],
-                         g2 = rows[(size_t)((chunk * SGS_GEOM_ROWS + 2) * 64 + lane)];
-            unsigned i; memcpy(&i, &g2.w, 4);
-            if ((int64_t)(i + 1) * 11 * 4 > n) continue;
-            float* o = dst + (size_t)i * 11;
-            o[0] = g0.x; o[1] = g0.y; o[2] = g0.z; o[3] = g0.w; o[4] = g1.x; o[5] = g1.y; o[6] = g1.z; o[7] = g1.w; o[8] = g2.x; o[9] = g2.y; o[10] = g2.z;
-        }
-    }
-    if (what == SGS_BUF_SCENE_SH) {
-        const sgs_scene* sc = ctx->last_scene;
-        const int nf = 3 * (sc->sh_degree + 1) * (sc->sh_degree + 1), rows_n = sc->sh_rows;
-        std::vector<float4> rows((size_t)n_slots * rows_n), g2((size_t)n_slots);
-        hipError_t e = hipMemcpy(rows.data(), sc->shq.p, rows.size() * sizeof(float4), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-        std::vector<float4> geo((size_t)n_slots * SGS_GEOM_ROWS);
-        if ((e = hipMemcpy(geo.data(), sc->geom.p, geo.size() * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-        float* dst = (float*)host_dst;
-        std::vector<unsigned> w((size_t)rows_n * 4);
-        for (int64_t p = 0; p < ctx->last_n; ++p) {
-            const int64_t chunk = p >> 6, lane = p & 63;
-            unsigned i; memcpy(&i, &geo[(size_t)((chunk * SGS_GEOM_ROWS + 2) * 64 + lane)].w, 4);       // the original index
-            if ((int64_t)(i + 1) * nf * 4 > n) continue;
-            for (int r = 0; r < rows_n; ++r) memcpy(&w[(size_t)4 * r], &rows[(size_t)((chunk * rows_n + r) * 64 + lane)], 16);
-            float* o = dst + (size_t)i * nf;
-            if (!sc->sh_packed) memcpy(o, w.data(), (size_t)nf * 4);
-            else {      // 12 B of fp32 DC, then a byte per coefficient: v / 32 - 4 + 1 / 64, exact in fp32 (sgs_kernels.h sgs_sh_byte)
-                memcpy(o, w.data(), 12);
-                for (int j = 0; j < nf - 3; ++j) {      // sgs_kernels.h sgs_sh_byte / sgs_sh_byte_mode, restated: one correctly rounded fma (exact in double, rounded once)
-                    const unsigned v = (w[(size_t)3 + (j >> 2)] >> (8 * (j & 3))) & 0xffu;
-                    volatile double prod = (double)v * (8.0 / 255.0);         // (two roundings, as the kernel's __dmul_rn / __dsub_rn)
-                    float x = sc->sh_decode == 1 ? (float)(prod - 4.0) : (float)((double)v * (1.0 / 32.0) + (-4.0 + 1.0 / 64.0));
-                    if (sc->sh_decode == 2) x = v == 0u ? -4.0f : v == 255u ? 4.0f : x;
-                    o[3 + j] = x;
-                }
-            }
-        }
-    }
-    if (what == SGS_BUF_CHUNK_SKIPPED) {
-        std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks)), bm(vm.size());
-        hipError_t e = hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(bm.data(), L.bigmask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-        for (int64_t i = 0; i < n; ++i) ((unsigned char*)host_dst)[i] = vm[(size_t)i] == 0ull && bm[(size_t)i] == ~0ull;
-    }
-    if (what == SGS_BUF_SPLATS) {
-        // device records (sgs_common.h: 64 B, conic pre-scaled for the composite, opacity also as an exponent offset) -> x,y,conic a,b | c,opacity,r,g | b,depth,rect01,rect23
-        const int64_t cnt = n / elem;
-        std::vector<Splat> tmp((size_t)std::max<int64_t>(1, cnt));
-        hipError_t e = hipMemcpy(tmp.data(), L.splats.p, (size_t)cnt * sizeof(Splat), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) SGS_FAIL(ctx, SGS_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(e));
-        const double l2e = 1.4426950408889634;
-        for (int64_t i = 0; i < cnt; ++i) {
-            const Splat& sp = tmp[(size_t)i];
-            float* o = (float*)((char*)host_dst + i * elem);
-            o[0] = sp.x; o[1] = sp.y;
-            // (the record holds the roots of the completed square A (dx + k dy)^2 + C' dy^2 in the slots A, B, C: a = sqrt(A),
-            //  a k, c = +-sqrt(|C'|);  B = 2 A k = 2 a (a k),  C = A k^2 + C' = (a k)^2 + C')
-            const double a_ = sp.A, ak_ = sp.B, c_ = sp.C;
-            const double A_ = a_ * a_, Cp_ = c_ * std::fabs(c_);
-            o[2] = (float)(A_ / (0.5 * l2e)); o[3] = (float)(2.0 * a_ * ak_ / l2e); o[4] = (float)((ak_ * ak_ + Cp_) / (0.5 * l2e));
-            o[5] = sp.o; o[6] = sp.r; o[7] = sp.g; o[8] = sp.b;
-            memcpy(o + 9, &sp.key, 4); memcpy(o + 10, &sp.rect01, 4); memcpy(o + 11, &sp.rect23, 4);
-        }
-    }
-    if (elem) {
-        // a splat lives at its Gaussian's index; the per-chunk visibility masks say which are live.
-        // Dead slots are blanked (slot ids -> 0xFFFFFFFF, splats -> 0) so stale data cannot pass for live.
-        std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks));
-        SGS_HIP(ctx, hipMemcpy(vm.data(), L.vismask.p, (size_t)n_chunks * 8, hipMemcpyDeviceToHost));
-        char* dst = (char*)host_dst;
-        // vismask is indexed by layout position; slots by original index
-        const unsigned* perm = ctx->last_scene && !ctx->last_scene->perm_host.empty() ? ctx->last_scene->perm_host.data() : nullptr;
-        std::vector<unsigned char> live((size_t)n_slots, 0);
-        for (int64_t p = 0; p < ctx->last_n; ++p)
-            if ((vm[p >> 6] >> (p & 63)) & 1ull) live[perm ? perm[p] : (size_t)p] = 1;
-        for (int64_t i = 0; i < n_slots && (i + 1) * elem <= n; ++i) {
-            if (what == SGS_BUF_SLOT_IDS) ((unsigned*)dst)[i] = live[(size_t)i] ? (unsigned)i : 0xFFFFFFFFu;
-            else if (!live[(size_t)i]) memset(dst + i * elem, 0, (size_t)elem);
-        }
-    }
-    return have;
+    if (what == SGS_BUF_SCENE_GEOM) rc = read_scene_geom(ctx, sc, n_slots, host_dst, n);
+    if (what == SGS_BUF_SCENE_SH) rc = read_scene_sh(ctx, sc, n_slots, host_dst, n);
+    if (what == SGS_BUF_CHUNK_SKIPPED) rc = read_chunk_skipped(ctx, L, n_chunks, host_dst, n);
+    if (what == SGS_BUF_SPLATS) rc = read_splats(ctx, L, host_dst, n, elem);
+    if (rc == SGS_OK && elem) rc = blank_dead_slots(ctx, r, L, what == SGS_BUF_SLOT_IDS, host_dst, n, elem);
+    return rc != SGS_OK ? rc : have;
 }
 
 // ---- collision-mesh depth (include/sage_gs.h "Collision-mesh depth"; kernels in sgs_mesh.h) ------------------------------------------

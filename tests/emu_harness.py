@@ -140,6 +140,26 @@ class EmuRenderer:
         self.lib.check(self.lib.sgs_render_batch(self.ctx, self.scene, arr, len(cams), C.byref(k), 0, -1, out.ctypes.data, None, None), self.ctx)
         return out
 
+    def render_batch_stats(self, cams):
+        """sgs_render_batch with statistics: ([n, H, W, 3], one stats dict per frame)."""
+        arr = (_capi.SgsCamera * len(cams))(*[_capi.make_camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy,
+                                                                np.asarray(c.view, np.float32).reshape(4, 4).tolist()) for c in cams])
+        k = self._config(None, 0)
+        out = np.zeros((len(cams), cams[0].height, cams[0].width, 3), np.float32)
+        stats = (_capi.SgsStats * len(cams))()
+        self.lib.check(self.lib.sgs_render_batch(self.ctx, self.scene, arr, len(cams), C.byref(k), 0, -1, out.ctypes.data, stats, None), self.ctx)
+        return out, [s.as_dict() for s in stats]
+
+    def frames_in_flight(self, cams):
+        """One SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED sgs_render per camera, each into its own buffer, then ONE sgs_frame_sync."""
+        k = self._config(None, _capi.FLAG_ASYNC | _capi.FLAG_PIPELINED)
+        outs = [np.full((c.height, c.width, 3), -1.0, np.float32) for c in cams]
+        for c, o in zip(cams, outs):
+            cc = _capi.make_camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, np.asarray(c.view, np.float32).reshape(4, 4).tolist())
+            self.lib.check(self.lib.sgs_render(self.ctx, self.scene, C.byref(cc), C.byref(k), 0, -1, o.ctypes.data, None, None), self.ctx)
+        self.sync()
+        return outs
+
     def render_aux(self, cam, cfg=None, rows=(0, -1), fine=True, deep=True, stats=False, out=None, out_aux=None, flags=0):
         """sgs_render_rgbd: (rgb [H, W, 3], aux [H, W, 2] = expected depth and coverage, stats).  `out` / `out_aux`: pre-filled buffers
         (a band of tile rows leaves the other rows alone).  flags: more SGS_FLAG_* bits (SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED: the

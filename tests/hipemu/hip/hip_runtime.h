@@ -377,7 +377,8 @@ static inline hipError_t hipMalloc(void** p, size_t n) {
 static inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned) {
     if (hipemu::alloc_refused()) { *p = nullptr; return hipErrorOutOfMemory; }
-    *p = calloc(1, n ? n : 1);
+    *p = malloc(n ? n : 1);
+    if (*p) memset(*p, 0xCD, n);            // pinned memory is no more cleared than device memory: the same poison
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }

@@ -998,3 +998,61 @@ def case_refused_capacity_changes_nothing(drv):
     assert (got == want).all()
     drv.set_tuning(**{k: keep[k] for k in ("lanes", "group", "group_lanes", "morton")})
     assert drv.tuning() == keep
+
+
+def stats_without_times(st):
+    """What a frame's sgs_stats says of the FRAME: every field but the stage times and the number of renders it took."""
+    return {k: v for k, v in st.items() if k not in ("ms", "ms_total", "retries")}
+
+
+RING_SHIFTS = (-0.35, -0.1, 0.1, 0.15)
+RING_FRAMES = 260            # more frames than the status ring has slots (256): a batch of them is two chunks, the second of 4 frames
+
+
+def ring_scene_and_cameras():
+    """32x32 frames (four tiles) of 300 Gaussians from four cameras a step apart: D = 1 000 ... 1 035 per frame, on both sides of 1024."""
+    cams = []
+    for k in range(4):
+        V = np.eye(4, dtype=np.float32); V[0, 3] = RING_SHIFTS[k]
+        cams.append(onp.Camera(32, 32, 28.0, 28.0, 16.0, 16.0, V))
+    return random_scene(300, 9, 0, scale=(0.1, 0.4)), cams
+
+
+def case_status_ring(drv):
+    """The host's bookkeeping of the frames in flight (sgs_api.hip StatusRing, FrameRec), at frames so small that nothing else is tested.
+    A `drv` offers frames_in_flight(cams) -> the frames of SGS_FLAG_ASYNC | SGS_FLAG_PIPELINED renders, each into its own buffer, with
+    nothing but ONE sgs_frame_sync after the last; and render_batch_stats(cams) -> (frames, one stats dict per frame).
+    (a) 260 frames in flight — the ring wraps, the library has to drain it by itself: every buffer is the synchronous frame of its camera.
+    (b) one batch of 260 cameras under a record capacity of 1024, which some frames overflow and some do not: every frame is the frame
+        rendered alone, and its N_v, D and tile count are the single render's."""
+    scene, cams = ring_scene_and_cameras()
+    drv.upload(*scene)
+    alone = [drv.render(c, stats=False) for c in cams]
+    d = [st["d_total"] for _, st in alone]
+    assert max(d) > 1024 and min(d) <= 1024, d           # (the case's own precondition: both verdicts occur in the batch)
+    many = [cams[i % 4] for i in range(RING_FRAMES)]
+    for i, img in enumerate(drv.frames_in_flight(many)):
+        assert (img == alone[i % 4][0]).all(), f"frame {i} of {RING_FRAMES} in flight differs from the synchronous frame"
+    drv.set_record_capacity(1024)
+    batch, stats = drv.render_batch_stats(many)
+    for i in range(RING_FRAMES):
+        img, st = alone[i % 4]
+        assert (batch[i] == img).all(), f"frame {i} of a batch of {RING_FRAMES} differs from the frame rendered alone"
+        got = {k: stats[i][k] for k in ("n_visible", "d_total", "n_tiles")}
+        assert got == {k: st[k] for k in got}, (i, got, st)
+
+
+def case_batch_stats_of_mixed_tilings(drv, n=500, res=(96, 64)):
+    """A batch whose frames choose different tilings (a lens that zooms in and out: fine_shift_of decides per camera, a launch group ends
+    where the choice changes): every frame is the frame rendered alone and its sgs_stats — bytes[] too, which count the frame's OWN grid
+    of tiles — are the single render's, the stage times and `retries` aside."""
+    scene = random_scene(n, 303, 1, scale=(0.03, 0.15), opac_mu=1.0)
+    drv.upload(*scene)
+    w, h = res
+    cams = [onp.Camera(w, h, k * w, k * w, w / 2.0, h / 2.0, np.eye(4, dtype=np.float32)) for k in (0.9, 0.2, 3.0, 0.25, 0.9, 4.0, 0.3, 0.2, 2.5)]
+    alone = [drv.render(c, stats=False) for c in cams]
+    assert len({st["n_tiles"] for _, st in alone}) > 1, [st["n_tiles"] for _, st in alone]      # (or the case proves nothing)
+    batch, stats = drv.render_batch_stats(cams)
+    for i, (img, st) in enumerate(alone):
+        assert (batch[i] == img).all(), f"frame {i} of the batch differs from the frame rendered alone"
+        assert stats_without_times(stats[i]) == stats_without_times(st), (i, stats[i], st)

@@ -246,6 +246,18 @@ def test_batch_on_a_fresh_context_survives_overflowing_frames():
         d.close()
 
 
+def test_more_frames_in_flight_than_the_status_ring_has_slots():
+    d = emu_harness.EmuRenderer()
+    try:
+        pc.case_status_ring(d)
+    finally:
+        d.close()
+
+
+def test_batch_statistics_of_frames_that_choose_different_tilings(drv):
+    pc.case_batch_stats_of_mixed_tilings(drv)
+
+
 @pytest.mark.parametrize("case", __import__("known_answer_cases").ALL, ids=lambda f: f.__name__)
 def test_kernels_against_closed_form_answers(drv, case):
     """The analytic cases that pin the oracle, run straight against the kernels (emulator) — no oracle involved."""

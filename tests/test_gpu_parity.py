@@ -60,6 +60,21 @@ class GpuDriver:
         cl = [Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, np.asarray(c.view, np.float64)) for c in cams]
         return self.r.render_batch(cl, self.scene, config=self._config(cfg), fine_tiles=fine).cpu().numpy()
 
+    def render_batch_stats(self, cams):
+        from sage_gs import Camera
+        cl = [Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, np.asarray(c.view, np.float64)) for c in cams]
+        batch, stats = self.r.render_batch(cl, self.scene, want_stats=True)
+        return batch.cpu().numpy(), stats
+
+    def frames_in_flight(self, cams):
+        """One asynchronous pipelined render per camera, each into its own buffer, then ONE sync()."""
+        from sage_gs import Camera
+        outs = [self.torch.full((c.height, c.width, 3), -1.0, dtype=self.torch.float32, device="cuda:0") for c in cams]
+        for c, o in zip(cams, outs):
+            self.r.render(Camera(c.width, c.height, c.fx, c.fy, c.cx, c.cy, np.asarray(c.view, np.float64)), self.scene, out=o, sync=False, pipelined=True)
+        self.r.sync()
+        return [o.cpu().numpy() for o in outs]
+
     def render_aux(self, cam, cfg=None, rows=(0, -1), fine=True, deep=True, stats=False, out=None, out_aux=None):
         """Renderer.render(return_aux / out_aux): (rgb [H, W, 3], aux [H, W, 2] = expected depth and coverage, stats).  `out` / `out_aux`:
         pre-filled host arrays, copied to the device, rendered into and copied back (a band leaves the other rows alone)."""
@@ -216,6 +231,14 @@ def test_overflow_retry():
     d = GpuDriver()
     try:
         pc.case_overflow_retry(d)
+    finally:
+        d.close()
+
+
+def test_more_frames_in_flight_than_the_status_ring_has_slots():
+    d = GpuDriver()
+    try:
+        pc.case_status_ring(d)
     finally:
         d.close()
 
@@ -1107,7 +1130,11 @@ def test_a_batch_whose_frames_choose_different_tilings(drv):
     """fine_shift_of decides per camera (the growth of the record count under a split depends on how large the splats are on THAT
     screen); the frames of a launch group share one grid of tiles, so a batch's groups end where the choice changes.  A batch that zooms
     in and out of a room — focal lengths from a quarter to four times the reference lens — must hold every frame as the single-frame
-    call renders it, bit for bit, with the count of tiles the single call reports; and both tilings must occur, or the test proves nothing."""
+    call renders it, bit for bit, with the statistics the single call reports; and both tilings must occur, or the test proves nothing.
+    The statistics compared: every field but the stage times, `retries` and `n_deep_windows`.  The last is not a property of the frame
+    on the GPU: the SAME frame rendered alone three times reported 18, 17, 18 (zoom 0.3), 30, 28, 33 (zoom 0.25) and 24, 22, 23 windows,
+    three batches 18, 18, 18 / 32, 30, 31 / 27, 21, 24, with identical pixels and identical values in every other field (a diagnostic
+    of how the composite went about a tile, not of what it drew).  parity_cases.case_batch_stats_of_mixed_tilings (emulator) compares it too."""
     import torch
     from sage_gs import Camera, scenes
     sc = scenes.make_room(200_000, seed=9)
@@ -1115,9 +1142,10 @@ def test_a_batch_whose_frames_choose_different_tilings(drv):
     zooms = (1.0, 0.3, 3.5, 4.0, 0.25, 1.0, 3.0, 0.5, 0.3, 3.8, 1.2)
     cams = [Camera(c.width, c.height, c.fx * k, c.fy * k, c.cx, c.cy, c.view) for c, k in zip(base * 2, zooms)]
     scene = drv.r.upload(scenes.to_gaussians(sc, "cuda:0"))
-    one, tiles = [], []
+    of_frame = lambda st: {k: v for k, v in pc.stats_without_times(st).items() if k != "n_deep_windows"}
+    one, tiles, sts = [], [], []
     for c in cams:
-        one.append(drv.r.render(c, scene).clone()); tiles.append(drv.r.last_stats["n_tiles"])
+        one.append(drv.r.render(c, scene).clone()); tiles.append(drv.r.last_stats["n_tiles"]); sts.append(drv.r.last_stats)
     assert set(tiles) == {40 * 30, 80 * 60}, tiles
     batch, bst = drv.r.render_batch(cams, scene, want_stats=True)
     outs = [torch.zeros_like(one[0]) for _ in cams]
@@ -1126,6 +1154,7 @@ def test_a_batch_whose_frames_choose_different_tilings(drv):
     drv.r.sync()
     for i in range(len(cams)):
         assert bst[i]["n_tiles"] == tiles[i], (i, bst[i]["n_tiles"], tiles[i])
+        assert of_frame(bst[i]) == of_frame(sts[i]), (i, bst[i], sts[i])     # (bytes[] too: of the frame's OWN grid)
         assert (batch[i] == one[i]).all() and (outs[i] == one[i]).all(), f"frame {i} (zoom {zooms[i]}) depends on how it is issued"
     scene.free()
 
