@@ -605,6 +605,64 @@ typedef struct sgs_similarity_row {  /* 64 bytes, 8-byte aligned; one per frame 
 int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
                          const uint8_t* target, int64_t target_frame_stride, sgs_similarity_row* out_rows, void* hip_stream);
 
+/* ---- Top-down seen map — what an embodied agent has SEEN: depth frames unprojected on the device and binned by height into a grid of
+ * cells, per cell a count of free hits (the floor band) and of occupied hits (the obstacle band); the map module of an exploration or
+ * ObjectNav agent that consumes RGB-D, reduced next to the kernel that wrote the depth so that a grid of a few hundred cells a side
+ * crosses the link where a 1024 x 768 depth frame is 3 MB.  THIS PROJECT'S OWN definition, like the id channel, the object table and
+ * the similarity row: the reference scores NoGoalNav by the 0.5 m cells the agent STOOD in against a guessed total of 400
+ * (measures.py:399-437) and keeps no map of what it saw.  No new version: no existing struct changes.
+ *
+ *   Arithmetic  fp32; every multiply and add is rounded once, in the order written, never contracted; there is no division.
+ *   Point    frame f has P = pix_to_map[f], twelve floats: rows k = 0, 1, 2 of (a_k, b_k, c_k), then t_0, t_1, t_2.  Pixel (x, y)
+ *            with depth z:  d_k = ((float)x * a_k + (float)y * b_k) + c_k;  p_k = z * d_k + t_k.  p_0, p_1 are map coordinates in
+ *            metres, p_2 is the height h.  A caller builds P as map_from_cam . [(1/fx, 0, (0.5 - cx)/fx); (0, 1/fy, (0.5 - cy)/fy);
+ *            (0, 0, 1)] — the mesh path's ray through the pixel centre — with t the camera's position in the map; the entry composes
+ *            nothing and takes the twelve numbers as given.
+ *   Cell     u = (p_0 - origin_x) * inv, v = (p_1 - origin_y) * inv with inv = 1.0f / cell_size computed once on the host.  The point
+ *            is inside when u >= 0 && u < (float)nx && v >= 0 && v < (float)ny (NaN is outside); only then i = (int)u, j = (int)v.
+ *   Counters every pixel goes to exactly one of four per-frame counters, tested in this order: counts[f][0] z not in
+ *            [min_z, max_z]; [1] outside the grid; [2] inside but in neither height band; [3] binned.  They sum to height * width.
+ *            out_counts is written whole by every call, whatever it held.
+ *   Grid     a binned pixel adds 1 to grid[j][i][0] when free_lo <= h && h <= free_hi (free), else to grid[j][i][1] when
+ *            occ_lo < h && h <= occ_hi (occupied): where the bands overlap, free wins.  The grid's total grows by sum_f counts[f][3].
+ *   Exact    everything is an integer count: a grid depends on the frames, the matrices and the parameters alone — not on the batch,
+ *            the order of the frames, frame_stride, how the kernel cuts a frame, or whether two batches are accumulated by two calls
+ *            or by one.  Counts saturate nowhere: a call whose n_frames * height * width exceeds 2^32 - 1 — which could overflow one
+ *            cell — is refused; overflow ACROSS accumulating calls (SGS_TOPDOWN_CLEAR not set) is the caller's concern.
+ *   Kernels  sage-3d_official_amd/csrc/sgs_topdown.h. */
+#define SGS_TOPDOWN_CLEAR 1u         /* sgs_topdown_params.flags: zero the grid before accumulating */
+typedef struct sgs_topdown_params {
+    int32_t nx, ny;            /* cells; 1 <= nx, ny, and 2*nx*ny <= 2^31 - 1 */
+    float   origin_x, origin_y;/* map coordinates of the corner of cell (0,0) */
+    float   cell_size;         /* metres, > 0, finite */
+    float   min_z, max_z;      /* a sample enters only if min_z <= z && z <= max_z (both false for NaN) */
+    float   free_lo, free_hi;  /* height h is "free"     when free_lo <= h && h <= free_hi */
+    float   occ_lo,  occ_hi;   /*             "occupied" when occ_lo  <  h && h <= occ_hi; tested only when not free */
+    uint32_t flags;            /* SGS_TOPDOWN_CLEAR = 1: zero the grid before accumulating; otherwise add to what it holds */
+    int32_t reserved;          /* 0 */
+} sgs_topdown_params;
+/* 256 x 256 cells of 0.05 m, origin (-6.4, -6.4), z in [0.1, 6.5] (the reference's depth clip, simple_env.py:1578), free
+ * [-0.15, 0.15], occupied (0.15, 1.5], SGS_TOPDOWN_CLEAR. */
+void sgs_topdown_params_default(sgs_topdown_params* params);
+/* n_frames depth frames of width x height, frame f at depth + f * frame_stride (floats), accumulated into ONE grid
+ * uint32 [ny][nx][2] (free hits, occupied hits); out_counts is uint32 [n_frames][4].  depth, pix_to_map (float [n_frames][12]), grid
+ * and out_counts are DEVICE buffers: the kernels update grid and out_counts with integer atomics, which a link to pinned host memory
+ * need not carry.  Stream-ordered and asynchronous: the call never synchronises, owns no scratch and leaves none behind.  A clear
+ * (of the counters, and of the grid with SGS_TOPDOWN_CLEAR), then one reduction over frames x regions of a frame per 65535 frames.
+ * SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument: null depth, pix_to_map, params,
+ * grid or out_counts; n_frames < 1; width < 1 or height < 1; height * width > 2^31 - 1; frame_stride < height * width;
+ * n_frames * height * width > 2^32 - 1; nx < 1, ny < 1 or 2 * nx * ny > 2^31 - 1; cell_size, an origin or a band edge not finite;
+ * cell_size <= 0; min_z <= max_z not true (NaN included); free_lo > free_hi; occ_lo > occ_hi; unknown flags; reserved != 0; depth,
+ * pix_to_map, grid or out_counts not 4-byte aligned. */
+int sgs_topdown_map(sgs_ctx* ctx, const float* depth, int width, int height, int n_frames, int64_t frame_stride,
+                    const float* pix_to_map, const sgs_topdown_params* params, uint32_t* grid, uint32_t* out_counts, void* hip_stream);
+/* The four numbers of a grid uint32 [ny][nx][2], written to out (DEVICE uint64[4]) whatever it held: out[0] cells with
+ * occupied >= min_hits; out[1] cells with occupied < min_hits && free >= min_hits; out[2] the sum of free hits; out[3] the sum of
+ * occupied hits.  out[0] + out[1] is the number of cells seen.  Stream-ordered and asynchronous, no scratch: a clear followed by one
+ * reduction.  SGS_ERR_INVALID, before anything is enqueued or written: null grid or out; nx < 1, ny < 1 or 2 * nx * ny > 2^31 - 1;
+ * min_hits < 1; grid not 4-byte aligned; out not 8-byte aligned (it is updated with 64-bit atomics). */
+int sgs_topdown_summary(sgs_ctx* ctx, const uint32_t* grid, int nx, int ny, uint32_t min_hits, uint64_t* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

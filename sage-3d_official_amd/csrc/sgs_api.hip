@@ -27,6 +27,7 @@
 #include "sgs_resize.h"
 #include "sgs_objects.h"
 #include "sgs_similarity.h"
+#include "sgs_topdown.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2170,6 +2171,97 @@ int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, 
         K.n_frames = std::min(SGS_SIM_MAX_FRAMES, n_frames - f0);
         hipLaunchKernelGGL(sgs::k_sim_reduce, dim3((unsigned)(tiles_x * tiles_y), (unsigned)K.n_frames), dim3(SGS_SIM_THREADS), 0, st, K);
     }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_topdown_map, sgs_topdown_summary (csrc/sgs_topdown.h) -------------------------------------------------------------------------
+static_assert(sizeof(sgs_topdown_params) == 52, "sgs_topdown_params is thirteen 4-byte fields");
+
+extern "C" {
+
+void sgs_topdown_params_default(sgs_topdown_params* p) {
+    if (!p) return;
+    p->nx = 256; p->ny = 256; p->origin_x = -6.4f; p->origin_y = -6.4f; p->cell_size = 0.05f;
+    p->min_z = 0.1f; p->max_z = 6.5f; p->free_lo = -0.15f; p->free_hi = 0.15f; p->occ_lo = 0.15f; p->occ_hi = 1.5f;
+    p->flags = SGS_TOPDOWN_CLEAR; p->reserved = 0;
+}
+
+int sgs_topdown_map(sgs_ctx* ctx, const float* depth, int width, int height, int n_frames, int64_t frame_stride,
+                    const float* pix_to_map, const sgs_topdown_params* p, uint32_t* grid, uint32_t* out_counts, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_topdown_map";
+    if (!depth) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null depth", who);
+    if (!pix_to_map) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null pix_to_map", who);
+    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
+    if (!grid) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null grid", who);
+    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
+    if (height < 1 || width < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d", who, width, height);
+    const int64_t pixels = (int64_t)height * width;
+    if (pixels > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d has more than 2^31 - 1 pixels", who, width, height);
+    if (frame_stride < pixels)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (frame_stride %lld elements, a frame has %lld)", who, (long long)frame_stride, (long long)pixels);
+    if ((int64_t)n_frames * pixels > 0xFFFFFFFFll)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames * height * width = %lld could pass 2^32 - 1 hits in one cell", who, (long long)((int64_t)n_frames * pixels));
+    if (p->nx < 1 || p->ny < 1 || 2ll * p->nx * p->ny > 0x7FFFFFFFll)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny and 2 nx ny <= 2^31 - 1)", who, (int)p->nx, (int)p->ny);
+    if (!std::isfinite(p->cell_size) || p->cell_size <= 0.0f) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: cell_size = %g (finite and > 0)", who, (double)p->cell_size);
+    if (!std::isfinite(p->origin_x) || !std::isfinite(p->origin_y))
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: origin (%g, %g) is not finite", who, (double)p->origin_x, (double)p->origin_y);
+    if (!(p->min_z <= p->max_z)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min_z %g is not <= max_z %g", who, (double)p->min_z, (double)p->max_z);
+    if (!std::isfinite(p->free_lo) || !std::isfinite(p->free_hi) || p->free_lo > p->free_hi)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: free band [%g, %g] (finite, free_lo <= free_hi)", who, (double)p->free_lo, (double)p->free_hi);
+    if (!std::isfinite(p->occ_lo) || !std::isfinite(p->occ_hi) || p->occ_lo > p->occ_hi)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: occupied band (%g, %g] (finite, occ_lo <= occ_hi)", who, (double)p->occ_lo, (double)p->occ_hi);
+    if (p->flags & ~SGS_TOPDOWN_CLEAR) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
+    // the kernels' atomics are 32-bit; a misaligned one must never reach the device
+    const struct { const void* at; const char* name; } buffers[] = {{depth, "depth"}, {pix_to_map, "pix_to_map"}, {grid, "grid"}, {out_counts, "out_counts"}};
+    for (const auto& b : buffers)
+        if (reinterpret_cast<uintptr_t>(b.at) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s %p is not 4-byte aligned", who, b.name, b.at);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::TopdownJob J;
+    J.depth = depth; J.P = pix_to_map; J.grid = grid; J.counts = out_counts;
+    J.stride = frame_stride; J.W = width; J.H = height; J.n_frames = n_frames; J.nx = p->nx; J.ny = p->ny;
+    J.origin_x = p->origin_x; J.origin_y = p->origin_y; J.inv = 1.0f / p->cell_size;
+    J.min_z = p->min_z; J.max_z = p->max_z; J.free_lo = p->free_lo; J.free_hi = p->free_hi; J.occ_lo = p->occ_lo; J.occ_hi = p->occ_hi;
+    J.clear = p->flags & SGS_TOPDOWN_CLEAR;
+    const int64_t clear_words = std::max<int64_t>(4ll * n_frames, J.clear ? 2ll * p->nx * p->ny : 0);
+    const int64_t clear_blocks = std::min<int64_t>((clear_words + SGS_TOPDOWN_THREADS - 1) / SGS_TOPDOWN_THREADS, 65536);
+    hipLaunchKernelGGL(sgs::k_topdown_clear, dim3((unsigned)clear_blocks), dim3(SGS_TOPDOWN_THREADS), 0, st, J);
+    const unsigned regions = (unsigned)((pixels + SGS_TOPDOWN_REGION - 1) / SGS_TOPDOWN_REGION);
+    for (int f0 = 0; f0 < n_frames; f0 += SGS_TOPDOWN_MAX_FRAMES) {
+        sgs::TopdownJob K = J;
+        K.depth = depth + (int64_t)f0 * frame_stride; K.P = pix_to_map + 12ll * f0;
+        K.counts = out_counts + 4ll * f0;
+        K.n_frames = std::min(SGS_TOPDOWN_MAX_FRAMES, n_frames - f0);
+        hipLaunchKernelGGL(sgs::k_topdown_map, dim3(regions, (unsigned)K.n_frames), dim3(SGS_TOPDOWN_THREADS), 0, st, K);
+    }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+int sgs_topdown_summary(sgs_ctx* ctx, const uint32_t* grid, int nx, int ny, uint32_t min_hits, uint64_t* out, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_topdown_summary";
+    if (!grid) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null grid", who);
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out", who);
+    if (nx < 1 || ny < 1 || 2ll * nx * ny > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny and 2 nx ny <= 2^31 - 1)", who, nx, ny);
+    if (min_hits < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min_hits = 0", who);
+    if (reinterpret_cast<uintptr_t>(grid) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: grid %p is not 4-byte aligned", who, (const void*)grid);
+    // out is updated with 64-bit atomics; a misaligned one must never reach the device
+    if (reinterpret_cast<uintptr_t>(out) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out %p is not 8-byte aligned", who, (const void*)out);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const long long cells = (long long)nx * ny;
+    unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
+    hipLaunchKernelGGL(sgs::k_topdown_sum_clear, dim3(1), dim3(64), 0, st, o);
+    const unsigned blocks = (unsigned)std::min<long long>((cells + SGS_TOPDOWN_THREADS - 1) / SGS_TOPDOWN_THREADS, SGS_TOPDOWN_SUM_BLOCKS);
+    hipLaunchKernelGGL(sgs::k_topdown_sum, dim3(blocks), dim3(SGS_TOPDOWN_THREADS), 0, st, grid, cells, (unsigned)min_hits, o);
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }

@@ -24,12 +24,12 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ and _os.environ.get("SAGE_GS_KEEP_ENV"
 from . import _capi  # noqa: F401,E402
 from ._capi import SgsError  # noqa: F401,E402
 
-__all__ = ["Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "render", "default_renderer",
+__all__ = ["Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "TopdownGrid", "render", "default_renderer",
            "SgsError", "scenes"]
 
 
 def __getattr__(name):          # torch is imported only when the renderer is actually used
-    if name in ("Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "render", "default_renderer"):
+    if name in ("Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "TopdownGrid", "render", "default_renderer"):
         from . import renderer
         return getattr(renderer, name)
     if name in ("scenes", "camera", "dist", "adapter", "ply", "mesh"):

@@ -37,7 +37,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_mesh_set_labels", "sgs_render_mesh_ids", "sgs_render_mesh_ids_batch",
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
-           "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity")
+           "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity",
+           "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary")
 
 
 class SgsError(RuntimeError):
@@ -161,6 +162,24 @@ SIMILARITY_DTYPE = __import__("numpy").dtype(SIMILARITY_ROW_DTYPE.descr + [("ssi
 assert SIMILARITY_ROW_DTYPE.itemsize == C.sizeof(SgsSimilarityRow) == 64
 
 
+TOPDOWN_CLEAR = 1                            # include/sage_gs.h SGS_TOPDOWN_CLEAR (sgs_topdown_params.flags)
+
+
+class SgsTopdownParams(C.Structure):
+    """include/sage_gs.h sgs_topdown_params: the grid, the depth range and the two height bands of the top-down seen map."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("origin_x", C.c_float), ("origin_y", C.c_float), ("cell_size", C.c_float),
+                ("min_z", C.c_float), ("max_z", C.c_float), ("free_lo", C.c_float), ("free_hi", C.c_float),
+                ("occ_lo", C.c_float), ("occ_hi", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class SgsTopdownSummary(C.Structure):
+    """sgs_topdown_summary's out: uint64[4]."""
+    _fields_ = [("occupied_cells", C.c_uint64), ("free_cells", C.c_uint64), ("free_hits", C.c_uint64), ("occupied_hits", C.c_uint64)]
+
+
+assert C.sizeof(SgsTopdownParams) == 52 and C.sizeof(SgsTopdownSummary) == 32
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -248,6 +267,9 @@ class Lib:
         lib.sgs_resize.argtypes = [vp, vp, i32, i32, i32, i64, C.POINTER(SgsResizeParams), vp, i64, vp]
         lib.sgs_object_table.argtypes = [vp, vp, vp, i32, i32, i32, i64, C.c_int32, vp, vp, vp]
         lib.sgs_image_similarity.argtypes = [vp, vp, i32, i32, i32, i64, vp, i64, vp, vp]
+        lib.sgs_topdown_params_default.argtypes = [C.POINTER(SgsTopdownParams)]; lib.sgs_topdown_params_default.restype = None
+        lib.sgs_topdown_map.argtypes = [vp, vp, i32, i32, i32, i64, vp, C.POINTER(SgsTopdownParams), vp, vp, vp]
+        lib.sgs_topdown_summary.argtypes = [vp, vp, i32, i32, C.c_uint32, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -50,6 +50,7 @@ class GsCamera:
         self._instance_paths = None if instance_paths is None else [str(p) for p in instance_paths]
         self._instance_in_frame = False
         self._boxes_in_frame = False
+        self._explore = None                                              # start_exploration_map: (TopdownGrid, model_to_map, grid, counts)
         self._target = None                                               # set_target_image: uint8 [h,w,3] on the device, at get_output_size()
         self._w, self._h = int(resolution[0]), int(resolution[1])         # Isaac resolution = (width, height)
         self._pos = np.zeros(3, np.float32)
@@ -288,6 +289,43 @@ class GsCamera:
         if n > 65534:
             raise ValueError(f"{n} labels do not fit a 16-bit PNG of id + 1 (at most 65534)")
         return self._r.encode_png((ids + 1).float().contiguous(), format="depth16", depth_scale=1.0, depth_max=65535.0)[0]
+
+    # -- the exploration map: what the agent has SEEN, binned top-down on the GPU.  THIS PROJECT'S OWN observation (Renderer.topdown_map):
+    # the reference's ExploredAreas / ExplorationCoverage count the 0.5 m cells the agent stood in (measures.py:399-437).
+    def start_exploration_map(self, grid=None, model_to_map=None):
+        """Starts (or restarts, empty) the map that update_exploration_map() accumulates: grid a TopdownGrid (default TopdownGrid()).
+        The map is in WORLD coordinates — the coordinates of set_world_pose, where the scene stands after asset_model_to_world — with
+        the stage's up axis Z as the height: cell (i, j) covers world x, y from the grid's origin.  model_to_map: a 3x4 from world
+        coordinates to map coordinates (third coordinate the height) for a stage whose up axis is not Z, or a map frame of one's
+        own; default the identity.  Needs collision_mesh=: the depth that is binned is the mesh's, the reference's source of depth."""
+        import torch
+        from .renderer import TopdownGrid
+        if self._mesh is None:
+            raise RuntimeError("the exploration map bins the collision mesh's depth: construct the camera with collision_mesh=")
+        g = TopdownGrid() if grid is None else grid
+        m = None if model_to_map is None else np.array(model_to_map, np.float64)
+        cells = torch.zeros((int(g.ny), int(g.nx), 2), dtype=torch.int32, device=self._r.device)
+        self._explore = (g, m, cells, torch.zeros((1, 4), dtype=torch.int32, device=self._r.device))
+
+    def update_exploration_map(self):
+        """Renders the collision mesh's depth at the current pose and adds it to the map, on the GPU; nothing crosses the link.
+        Returns the frame's four counters as a device tensor (Renderer.topdown_map's counts[0])."""
+        if self._explore is None:
+            raise RuntimeError("start_exploration_map() first")
+        g, m, cells, counts = self._explore
+        cam = self._camera()
+        self._r.topdown_map(self._mesh_depth(), self._r.pix_to_map(cam, m), g, out=(cells, counts), clear=False)
+        return counts[0]
+
+    def get_exploration_grid(self):
+        """The map so far: int32 [ny, nx, 2] on the GPU (free hits, occupied hits per cell)."""
+        if self._explore is None:
+            raise RuntimeError("start_exploration_map() first")
+        return self._explore[2]
+
+    def get_exploration(self, min_hits: int = 1) -> dict:
+        """Renderer.topdown_summary of the map so far: occupied_cells, free_cells, free_hits, occupied_hits, seen_cells, seen_area_m2."""
+        return self._r.topdown_summary(self.get_exploration_grid(), min_hits, cell_size=self._explore[0].cell_size)
 
     def get_depth(self, clip=(0.1, 6.5)) -> np.ndarray:
         """float32 [H,W] metres, limited to [0.1, 6.5] exactly as SimpleVLNEnv.get_depth does with the simulator's

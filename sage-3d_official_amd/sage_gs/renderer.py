@@ -60,6 +60,30 @@ class RenderConfig:
 
 
 @dataclass
+class TopdownGrid:
+    """The grid, the depth range and the two height bands of the top-down seen map (include/sage_gs.h sgs_topdown_params; the
+    defaults are sgs_topdown_params_default's): nx x ny cells of cell_size metres, cell (0, 0) cornered at (origin_x, origin_y) in
+    map coordinates; a depth sample enters when min_z <= z <= max_z (the reference's depth clip, simple_env.py:1578); a point of
+    height h is "free" when free_lo <= h <= free_hi and otherwise "occupied" when occ_lo < h <= occ_hi."""
+    nx: int = 256
+    ny: int = 256
+    origin_x: float = -6.4
+    origin_y: float = -6.4
+    cell_size: float = 0.05
+    min_z: float = 0.1
+    max_z: float = 6.5
+    free_lo: float = -0.15
+    free_hi: float = 0.15
+    occ_lo: float = 0.15
+    occ_hi: float = 1.5
+
+    def c_params(self, clear: bool = True) -> "_capi.SgsTopdownParams":
+        return _capi.SgsTopdownParams(int(self.nx), int(self.ny), float(self.origin_x), float(self.origin_y), float(self.cell_size),
+                                      float(self.min_z), float(self.max_z), float(self.free_lo), float(self.free_hi),
+                                      float(self.occ_lo), float(self.occ_hi), _capi.TOPDOWN_CLEAR if clear else 0, 0)
+
+
+@dataclass
 class Gaussians:
     """A 3DGS scene with activations applied: linear scales, (w,x,y,z) quaternions,
     opacities in (0,1), SH coefficients [N,(d+1)^2,3].  `model_to_world` is the asset transform of
@@ -1016,6 +1040,90 @@ class Renderer:
         with np.errstate(divide="ignore"):
             out["psnr"] = np.where(out["mse"] > 0, 10.0 * np.log10(255.0 * 255.0 / np.where(out["mse"] > 0, out["mse"], 1.0)), np.inf)
         return out
+
+    # -- the top-down seen map of depth frames (include/sage_gs.h sgs_topdown_map: this project's own definition) ------------------
+    def pix_to_map(self, cameras, model_to_map=None) -> torch.Tensor:
+        """float32 [B,12] on the device: per camera the twelve numbers sgs_topdown_map unprojects a depth frame with — the rows of
+        map_from_cam . [(1/fx, 0, (0.5 - cx)/fx); (0, 1/fy, (0.5 - cy)/fy); (0, 0, 1)] (the mesh path's ray through the pixel
+        centre), then the camera's position in the map.  Computed in NumPy fp64 from each camera's intrinsics and the inverse of its
+        rigid view, then rounded once.  model_to_map: a 3x4 (or 4x4) taking the space the view maps FROM — the world of the
+        cameras' poses — to the map, whose third coordinate is the height; default the identity.  `cameras`: a Camera or a sequence."""
+        cams = [cameras] if isinstance(cameras, Camera) else list(cameras)
+        if not cams:
+            raise ValueError("no cameras")
+        m = np.eye(4)
+        if model_to_map is not None:
+            mm = np.asarray(model_to_map, np.float64)
+            if mm.shape not in ((3, 4), (4, 4)) or not np.isfinite(mm).all():
+                raise ValueError("model_to_map must be a finite 3x4 (or 4x4) matrix")
+            m[:3] = mm[:3]
+        out = np.empty((len(cams), 12), np.float64)
+        for k, c in enumerate(cams):
+            view = np.asarray(c.view.detach().cpu().numpy() if isinstance(c.view, torch.Tensor) else c.view, np.float64).reshape(4, 4)
+            c2m = m @ np.linalg.inv(_rigid(view))
+            fx, fy, cx, cy = float(c.fx), float(c.fy), float(c.cx), float(c.cy)
+            K = np.array([[1.0 / fx, 0.0, (0.5 - cx) / fx], [0.0, 1.0 / fy, (0.5 - cy) / fy], [0.0, 0.0, 1.0]])
+            out[k, :9] = (c2m[:3, :3] @ K).reshape(9)
+            out[k, 9:] = c2m[:3, 3]
+        return torch.from_numpy(out.astype(np.float32)).to(self.device)
+
+    def topdown_map(self, depth: torch.Tensor, cameras_or_P, grid: Optional[TopdownGrid] = None, out=None, clear: bool = True):
+        """The top-down seen map of float32 depth frames [H,W] or [B,H,W] on the device (render_mesh_depth*'s, or any other distance to
+        the image plane), accumulated there in one launch for the whole batch: (grid, counts).  grid is uint32-valued int32
+        [ny, nx, 2] — per cell the free hits and the occupied hits — and counts int32 [B, 4]: per frame the pixels whose depth is
+        outside [min_z, max_z], outside the grid, inside it but in neither height band, and binned.  cameras_or_P: the frames'
+        cameras (pix_to_map is taken of them, with the identity as model_to_map) or a float32 [B,12] tensor that pix_to_map made.
+        grid: a TopdownGrid (default TopdownGrid()).  out=(grid, counts): contiguous int32 tensors of those shapes to write into;
+        clear=False adds to what out's grid holds (it needs out=).  Nothing is copied to the host; asynchronous on the current
+        stream.  Every count is an integer: the map does not depend on the batch, the order of the frames or how they are split
+        over calls.  This project's own definition: the reference counts the cells the agent stood in (measures.py:399-437)."""
+        g = TopdownGrid() if grid is None else grid
+        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
+            raise ValueError("depth must be a float32 tensor")
+        if depth.dim() == 2:
+            depth = depth.unsqueeze(0)
+        if depth.device != self.device or depth.dim() != 3 or min(depth.shape) < 1 or not depth[0].is_contiguous():
+            raise ValueError("depth must be float32 [H,W] or [B,H,W] on the renderer's device with contiguous frames")
+        b, h, w = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
+        if isinstance(cameras_or_P, torch.Tensor):
+            P = cameras_or_P
+            if P.device != self.device or P.dtype != torch.float32 or tuple(P.shape) != (b, 12) or not P.is_contiguous():
+                raise ValueError(f"P must be a contiguous float32 [{b}, 12] tensor on the renderer's device")
+        else:
+            cams = [cameras_or_P] if isinstance(cameras_or_P, Camera) else list(cameras_or_P)
+            if len(cams) != b or any(c.width != w or c.height != h for c in cams):
+                raise ValueError(f"{len(cams)} cameras for {b} frames of {w} x {h}")
+            P = self.pix_to_map(cams)
+        if out is None:
+            if not clear:
+                raise ValueError("clear=False adds to a grid: pass it as out=(grid, counts)")
+            cells = torch.empty((int(g.ny), int(g.nx), 2), dtype=torch.int32, device=self.device)
+            counts = torch.empty((b, 4), dtype=torch.int32, device=self.device)
+        else:
+            cells, counts = out
+            cells = self._ids_out(cells, (int(g.ny), int(g.nx), 2), torch.int32, "out[0]")
+            counts = self._ids_out(counts, (b, 4), torch.int32, "out[1]")
+        params = g.c_params(clear)
+        self._lib.check(self._lib.sgs_topdown_map(self._ctx, depth.data_ptr(), w, h, b, int(depth.stride(0)) if b > 1 else h * w,
+                                                  P.data_ptr(), C.byref(params), cells.data_ptr(), counts.data_ptr(), self._stream()), self._ctx)
+        return cells, counts
+
+    def topdown_summary(self, grid: torch.Tensor, min_hits: int = 1, cell_size: Optional[float] = None) -> dict:
+        """What a seen map holds, reduced on the device (32 bytes come back): a dict of Python ints — occupied_cells (occupied hits
+        >= min_hits), free_cells (free hits >= min_hits and occupied hits below it), free_hits, occupied_hits — plus
+        seen_cells = occupied_cells + free_cells and, given the grid's cell_size, seen_area_m2 = seen_cells cell_size^2."""
+        if (not isinstance(grid, torch.Tensor) or grid.device != self.device or grid.dtype != torch.int32 or grid.dim() != 3 or grid.shape[2] != 2
+                or not grid.is_contiguous()):
+            raise ValueError("grid must be a contiguous int32 [ny, nx, 2] tensor on the renderer's device")
+        if int(min_hits) < 1 or int(min_hits) > 0xFFFFFFFF:
+            raise ValueError("min_hits must be within 1 .. 2^32 - 1")
+        out = torch.empty(4, dtype=torch.int64, device=self.device)
+        self._lib.check(self._lib.sgs_topdown_summary(self._ctx, grid.data_ptr(), int(grid.shape[1]), int(grid.shape[0]), int(min_hits),
+                                                      out.data_ptr(), self._stream()), self._ctx)
+        occ, free, free_hits, occ_hits = (int(v) for v in out.cpu().numpy().view(np.uint64))
+        d = {"occupied_cells": occ, "free_cells": free, "free_hits": free_hits, "occupied_hits": occ_hits, "seen_cells": occ + free}
+        d["seen_area_m2"] = None if cell_size is None else (occ + free) * float(cell_size) ** 2
+        return d
 
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
