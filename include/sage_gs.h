@@ -663,6 +663,86 @@ int sgs_topdown_map(sgs_ctx* ctx, const float* depth, int width, int height, int
  * min_hits < 1; grid not 4-byte aligned; out not 8-byte aligned (it is updated with 64-bit atomics). */
 int sgs_topdown_summary(sgs_ctx* ctx, const uint32_t* grid, int nx, int ny, uint32_t min_hits, uint64_t* out, void* hip_stream);
 
+/* ---- Clearance map — where an agent can STAND: the exact squared Euclidean distance transform of obstacle grids, and the position
+ * and path checks that look positions up in it.  What the reference's 2-D collision detector does on the host for every motion
+ * sub-step and for its collision measures (collision_detector.py:95-132, 191-261): an obstacle grid, SciPy's
+ * distance_transform_edt, obstacles grown by the robot radius (dist_m <= robot_radius_m), then positions and ten-sample path
+ * segments looked up in the grown grid.  Here the grid stays on the device — a mask, or the seen map sgs_topdown_map wrote —, a batch
+ * of maps costs one call, and the growth is a threshold on d2 that the query applies: cell c is inside the grown obstacles iff
+ * d2[c] <= max_d2 (sage_gs.clearance.inflation_limit gives the max_d2 of a radius and a scale).  No new version: no existing struct
+ * changes.
+ *
+ *   Source   SGS_CLEARANCE_SRC_MASK8: uint8 [ny][nx], a non-zero byte is an obstacle (the reference's obstacle_map before
+ *            inflation).  SGS_CLEARANCE_SRC_TOPDOWN: uint32 [ny][nx][2], the grid of sgs_topdown_map (free hits, occupied hits): a
+ *            cell is an obstacle iff occupied >= min_hits, and with SGS_CLEARANCE_UNSEEN_BLOCKS also when occupied < min_hits &&
+ *            free < min_hits.  Map k begins k * map_stride ELEMENTS of the source's type (bytes; uint32 words) after map 0.
+ *   d2       uint32 [n_maps][ny][nx], dense: d2[j][i] = min over obstacle cells (i', j') of (i - i')^2 + (j - j')^2, in cells^2; 0 on
+ *            an obstacle; SGS_CLEARANCE_NONE in every cell of a map without obstacles.  1 <= nx, ny <= 32768, so the largest finite
+ *            value, 2 * 32767^2, fits.
+ *   Counters out_counts uint32 [n_maps][4], written whole by every call: [0] obstacle cells, [1] cells with 0 < d2 <= max_d2,
+ *            [2] cells with max_d2 < d2 < NONE, [3] cells equal to NONE.  They sum to nx * ny.
+ *   Exact    all arithmetic is on integers: a map's d2 depends on that map alone — not on the batch, map_stride or how the kernels
+ *            cut the map.
+ *   Kernels  sage-3d_official_amd/csrc/sgs_clearance.h. */
+#define SGS_CLEARANCE_NONE 0xFFFFFFFFu
+#define SGS_CLEARANCE_SRC_MASK8 0
+#define SGS_CLEARANCE_SRC_TOPDOWN 1
+#define SGS_CLEARANCE_UNSEEN_BLOCKS 1u   /* sgs_clearance_params.flags */
+typedef struct sgs_clearance_params {    /* 28 bytes */
+    int32_t  nx, ny;           /* cells; 1 <= nx, ny <= 32768 */
+    int32_t  source;           /* SGS_CLEARANCE_SRC_* */
+    uint32_t flags;            /* SGS_CLEARANCE_UNSEEN_BLOCKS (the topdown source only) */
+    uint32_t min_hits;         /* the topdown source: >= 1; ignored for a mask */
+    uint32_t max_d2;           /* the boundary between out_counts[1] and [2]; d2 does not depend on it */
+    int32_t  reserved;         /* 0 */
+} sgs_clearance_params;
+/* src, work, d2 and out_counts are DEVICE buffers; work is scratch of d2's shape (uint32 [n_maps][ny][nx]) that the caller owns and
+ * whose contents before and after the call mean nothing.  Stream-ordered and asynchronous: the call never synchronises, owns no
+ * scratch and leaves none behind.  A clear of the counters, a pass over rows and a pass over columns per 65535 maps.
+ * SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument: null src, params, work, d2 or
+ * out_counts; n_maps < 1; nx or ny outside 1 .. 32768; map_stride shorter than a map (nx * ny bytes; 2 * nx * ny words); an unknown
+ * source; unknown flags, or SGS_CLEARANCE_UNSEEN_BLOCKS with a mask; min_hits < 1 with the topdown source; reserved != 0; d2 and
+ * work the same buffer or overlapping; work, d2, out_counts or a topdown src not 4-byte aligned. */
+int sgs_clearance_map(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_clearance_params* params,
+                      uint32_t* work, uint32_t* d2, uint32_t* out_counts, void* hip_stream);
+
+/* The reference's check_collision_3d / check_path_collision_3d for n segments in one launch, against ONE d2 map of nx x ny.
+ *
+ *   Arithmetic  fp64; every operation is rounded once, in the order written, never contracted; the division is a true division.
+ *   Samples  segment (x0, y0) -> (x1, y1) has samples s = 1 .. n_samples: t = (double)s / (double)n_samples,
+ *            x = x0 * (1 - t) + x1 * t, y likewise.  With n_samples <= 1 there is one sample, the end point itself, untouched
+ *            (check_path_collision_3d:250-251).
+ *   Mapping  SGS_CLEARANCE_NEGATE first: x = -x, y = -y; then x = sum_x - x with SGS_CLEARANCE_FLIP_X and y = sum_y - y with
+ *            SGS_CLEARANCE_FLIP_Y (forward_position_mapping; sum_x = min_x + max_x, added once on the host).
+ *   Pixel    px = rint((x - min_x) / scale), py = rint((y - min_y) / scale); rint rounds ties to even, as Python's round does.
+ *   Bounds   inside: 0 <= px < nx and 0 <= py < ny.  Otherwise, when -margin <= px < nx + margin and -margin <= py < ny + margin,
+ *            both are clamped to the border; otherwise the sample collides.
+ *   Collision  a sample that is inside, or was clamped, collides iff d2[py][px] <= max_d2.
+ *   DEPARTURE  a px or py that is not finite (a NaN or infinite coordinate) is outside and COLLIDES.  The reference raises inside a
+ *            try there and answers "no collision".
+ *   Output   uint32 [n][2]: [0] the index s of the first colliding sample (from 1; 1 for the single-sample form), or 0 for none;
+ *            [1] the d2 of the cell the last sample — the end point — landed on after clamping, SGS_CLEARANCE_NONE when it was
+ *            outside beyond the margin. */
+#define SGS_CLEARANCE_NEGATE 1u          /* sgs_clearance_frame.flags */
+#define SGS_CLEARANCE_FLIP_X 2u
+#define SGS_CLEARANCE_FLIP_Y 4u
+typedef struct sgs_clearance_frame {     /* 64 bytes, 8-byte aligned */
+    double   min_x, min_y;     /* the coordinates of pixel (0, 0) */
+    double   sum_x, sum_y;     /* min + max of the map's bounds, for the flips */
+    double   scale;            /* metres per pixel: finite, > 0 */
+    uint32_t flags;            /* SGS_CLEARANCE_NEGATE | FLIP_X | FLIP_Y: the reference's defaults are all three */
+    int32_t  margin;           /* pixels of tolerance outside the map, >= 0; the reference's is 2 */
+    uint32_t max_d2;           /* a cell collides iff d2 <= max_d2 */
+    int32_t  n_samples;        /* the reference's default is 10; <= 1: the end point alone */
+    int64_t  reserved;         /* 0 */
+} sgs_clearance_frame;
+/* d2, segs (double [n][4]: x0, y0, x1, y1) and out are DEVICE buffers.  One launch, stream-ordered and asynchronous.
+ * SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument: null d2, segs, frame or out;
+ * n < 1; nx or ny outside 1 .. 32768; scale not finite or <= 0; min_x, min_y, sum_x or sum_y not finite; margin < 0; unknown
+ * flags; reserved != 0; d2 or out not 4-byte aligned; segs not 8-byte aligned. */
+int sgs_clearance_query(sgs_ctx* ctx, const uint32_t* d2, int nx, int ny, const double* segs, int n,
+                        const sgs_clearance_frame* frame, uint32_t* out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@
 #include "sgs_objects.h"
 #include "sgs_similarity.h"
 #include "sgs_topdown.h"
+#include "sgs_clearance.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2262,6 +2263,94 @@ int sgs_topdown_summary(sgs_ctx* ctx, const uint32_t* grid, int nx, int ny, uint
     hipLaunchKernelGGL(sgs::k_topdown_sum_clear, dim3(1), dim3(64), 0, st, o);
     const unsigned blocks = (unsigned)std::min<long long>((cells + SGS_TOPDOWN_THREADS - 1) / SGS_TOPDOWN_THREADS, SGS_TOPDOWN_SUM_BLOCKS);
     hipLaunchKernelGGL(sgs::k_topdown_sum, dim3(blocks), dim3(SGS_TOPDOWN_THREADS), 0, st, grid, cells, (unsigned)min_hits, o);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_clearance_map, sgs_clearance_query (csrc/sgs_clearance.h) ----------------------------------------------------------------------
+static_assert(sizeof(sgs_clearance_params) == 28, "sgs_clearance_params is seven 4-byte fields");
+static_assert(sizeof(sgs_clearance_frame) == 64, "sgs_clearance_frame is five doubles, four 4-byte fields and an int64");
+static_assert(SGS_CLEARANCE_NONE == SGS_CLEAR_NONE && SGS_CLEARANCE_SRC_MASK8 == SGS_CLEAR_SRC_MASK8 && SGS_CLEARANCE_SRC_TOPDOWN == SGS_CLEAR_SRC_TOPDOWN &&
+              SGS_CLEARANCE_UNSEEN_BLOCKS == SGS_CLEAR_UNSEEN_BLOCKS && SGS_CLEARANCE_NEGATE == SGS_CLEAR_NEGATE && SGS_CLEARANCE_FLIP_X == SGS_CLEAR_FLIP_X &&
+              SGS_CLEARANCE_FLIP_Y == SGS_CLEAR_FLIP_Y, "the kernels' constants are the header's");
+
+extern "C" {
+
+int sgs_clearance_map(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_clearance_params* p,
+                      uint32_t* work, uint32_t* d2, uint32_t* out_counts, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_clearance_map";
+    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
+    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
+    if (!work) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null work", who);
+    if (!d2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null d2", who);
+    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    if (n_maps < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_maps = %d", who, n_maps);
+    if (p->nx < 1 || p->ny < 1 || p->nx > SGS_CLEAR_MAX_NX || p->ny > SGS_CLEAR_MAX_NX)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, (int)p->nx, (int)p->ny, SGS_CLEAR_MAX_NX);
+    if (p->source != SGS_CLEARANCE_SRC_MASK8 && p->source != SGS_CLEARANCE_SRC_TOPDOWN) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
+    const bool topdown = p->source == SGS_CLEARANCE_SRC_TOPDOWN;
+    const int64_t cells = (int64_t)p->nx * p->ny, map_elements = topdown ? 2 * cells : cells;
+    if (map_stride < map_elements)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: maps overlap (map_stride %lld elements, a map has %lld)", who, (long long)map_stride, (long long)map_elements);
+    if ((p->flags & ~SGS_CLEARANCE_UNSEEN_BLOCKS) || (p->flags && !topdown)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x for source %d", who, (unsigned)p->flags, (int)p->source);
+    if (topdown && p->min_hits < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min_hits = 0", who);
+    if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
+    const uintptr_t a_d2 = reinterpret_cast<uintptr_t>(d2), a_work = reinterpret_cast<uintptr_t>(work);
+    const uint64_t out_bytes = 4ull * (uint64_t)n_maps * (uint64_t)cells;
+    if (a_d2 < a_work + out_bytes && a_work < a_d2 + out_bytes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: d2 %p and work %p overlap", who, (void*)d2, (void*)work);
+    // the kernels' loads, stores and atomics are 32-bit; a misaligned one must never reach the device
+    const struct { const void* at; const char* name; bool words; } buffers[] = {{src, "src", topdown}, {work, "work", true}, {d2, "d2", true}, {out_counts, "out_counts", true}};
+    for (const auto& b : buffers)
+        if (b.words && reinterpret_cast<uintptr_t>(b.at) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s %p is not 4-byte aligned", who, b.name, b.at);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::ClearanceJob J;
+    J.src = src; J.work = work; J.d2 = d2; J.counts = out_counts; J.stride = map_stride; J.map0 = 0;
+    J.nx = p->nx; J.ny = p->ny; J.n_maps = n_maps; J.kind = p->source;
+    J.min_hits = p->min_hits; J.unseen_blocks = p->flags & SGS_CLEARANCE_UNSEEN_BLOCKS; J.max_d2 = p->max_d2;
+    const int64_t count_words = 4ll * n_maps;
+    const unsigned clear_blocks = (unsigned)std::min<int64_t>((count_words + SGS_CLEAR_THREADS - 1) / SGS_CLEAR_THREADS, 1024);
+    hipLaunchKernelGGL(sgs::k_clear_counts, dim3(clear_blocks), dim3(SGS_CLEAR_THREADS), 0, st, out_counts, (long long)count_words);
+    const unsigned row_groups = (unsigned)((p->ny + SGS_CLEAR_ROWS - 1) / SGS_CLEAR_ROWS), words = (unsigned)((p->nx + 63) / 64);
+    for (int m0 = 0; m0 < n_maps; m0 += SGS_CLEAR_MAX_MAPS) {
+        sgs::ClearanceJob K = J;
+        K.map0 = m0;
+        K.n_maps = std::min(SGS_CLEAR_MAX_MAPS, n_maps - m0);
+        hipLaunchKernelGGL(sgs::k_clear_rows, dim3(row_groups, (unsigned)K.n_maps), dim3(SGS_CLEAR_THREADS), 0, st, K);
+        hipLaunchKernelGGL(sgs::k_clear_cols, dim3(words, row_groups, (unsigned)K.n_maps), dim3(SGS_CLEAR_THREADS), 0, st, K);
+    }
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+int sgs_clearance_query(sgs_ctx* ctx, const uint32_t* d2, int nx, int ny, const double* segs, int n,
+                        const sgs_clearance_frame* f, uint32_t* out, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_clearance_query";
+    if (!d2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null d2", who);
+    if (!segs) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null segs", who);
+    if (!f) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null frame", who);
+    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out", who);
+    if (n < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n = %d", who, n);
+    if (nx < 1 || ny < 1 || nx > SGS_CLEAR_MAX_NX || ny > SGS_CLEAR_MAX_NX) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, nx, ny, SGS_CLEAR_MAX_NX);
+    if (!std::isfinite(f->scale) || f->scale <= 0.0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: scale = %g (finite and > 0)", who, f->scale);
+    if (!std::isfinite(f->min_x) || !std::isfinite(f->min_y)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min (%g, %g) is not finite", who, f->min_x, f->min_y);
+    if (!std::isfinite(f->sum_x) || !std::isfinite(f->sum_y)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: sum (%g, %g) is not finite", who, f->sum_x, f->sum_y);
+    if (f->margin < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: margin = %d", who, (int)f->margin);
+    if (f->flags & ~(SGS_CLEARANCE_NEGATE | SGS_CLEARANCE_FLIP_X | SGS_CLEARANCE_FLIP_Y)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)f->flags);
+    if (f->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %lld", who, (long long)f->reserved);
+    if (reinterpret_cast<uintptr_t>(d2) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: d2 %p is not 4-byte aligned", who, (const void*)d2);
+    if (reinterpret_cast<uintptr_t>(out) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out %p is not 4-byte aligned", who, (const void*)out);
+    if (reinterpret_cast<uintptr_t>(segs) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: segs %p is not 8-byte aligned", who, (const void*)segs);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::ClearanceQuery Q;
+    Q.d2 = d2; Q.segs = segs; Q.out = out; Q.n = n; Q.nx = nx; Q.ny = ny; Q.margin = f->margin; Q.n_samples = f->n_samples;
+    Q.min_x = f->min_x; Q.min_y = f->min_y; Q.sum_x = f->sum_x; Q.sum_y = f->sum_y; Q.scale = f->scale; Q.flags = f->flags; Q.max_d2 = f->max_d2;
+    hipLaunchKernelGGL(sgs::k_clear_query, dim3((unsigned)((n + SGS_CLEAR_THREADS - 1) / SGS_CLEAR_THREADS)), dim3(SGS_CLEAR_THREADS), 0, st, Q);
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }

@@ -38,7 +38,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_jpeg_params_default", "sgs_jpeg_bound", "sgs_encode_jpeg", "sgs_jpeg_status",
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
            "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity",
-           "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary")
+           "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary",
+           "sgs_clearance_map", "sgs_clearance_query")
 
 
 class SgsError(RuntimeError):
@@ -180,6 +181,28 @@ class SgsTopdownSummary(C.Structure):
 assert C.sizeof(SgsTopdownParams) == 52 and C.sizeof(SgsTopdownSummary) == 32
 
 
+CLEARANCE_NONE = 0xFFFFFFFF                  # include/sage_gs.h SGS_CLEARANCE_NONE: d2 of a map without obstacles
+CLEARANCE_SRC_MASK8, CLEARANCE_SRC_TOPDOWN = 0, 1
+CLEARANCE_UNSEEN_BLOCKS = 1                  # sgs_clearance_params.flags
+CLEARANCE_NEGATE, CLEARANCE_FLIP_X, CLEARANCE_FLIP_Y = 1, 2, 4       # sgs_clearance_frame.flags
+
+
+class SgsClearanceParams(C.Structure):
+    """include/sage_gs.h sgs_clearance_params: the map's size, what its source is and where its counters are cut."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("source", C.c_int32), ("flags", C.c_uint32), ("min_hits", C.c_uint32),
+                ("max_d2", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class SgsClearanceFrame(C.Structure):
+    """include/sage_gs.h sgs_clearance_frame: how sgs_clearance_query takes a caller's coordinates to a pixel of the map."""
+    _fields_ = [("min_x", C.c_double), ("min_y", C.c_double), ("sum_x", C.c_double), ("sum_y", C.c_double), ("scale", C.c_double),
+                ("flags", C.c_uint32), ("margin", C.c_int32), ("max_d2", C.c_uint32), ("n_samples", C.c_int32), ("reserved", C.c_int64)]
+
+
+# the struct-size handshake of the two: the library asserts the same figures when it is compiled (csrc/sgs_api.hip)
+assert C.sizeof(SgsClearanceParams) == 28 and C.sizeof(SgsClearanceFrame) == 64 and SgsClearanceFrame.reserved.offset == 56
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -270,6 +293,8 @@ class Lib:
         lib.sgs_topdown_params_default.argtypes = [C.POINTER(SgsTopdownParams)]; lib.sgs_topdown_params_default.restype = None
         lib.sgs_topdown_map.argtypes = [vp, vp, i32, i32, i32, i64, vp, C.POINTER(SgsTopdownParams), vp, vp, vp]
         lib.sgs_topdown_summary.argtypes = [vp, vp, i32, i32, C.c_uint32, vp, vp]
+        lib.sgs_clearance_map.argtypes = [vp, vp, i32, i64, C.POINTER(SgsClearanceParams), vp, vp, vp, vp]
+        lib.sgs_clearance_query.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(SgsClearanceFrame), vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -327,6 +327,14 @@ class GsCamera:
         """Renderer.topdown_summary of the map so far: occupied_cells, free_cells, free_hits, occupied_hits, seen_cells, seen_area_m2."""
         return self._r.topdown_summary(self.get_exploration_grid(), min_hits, cell_size=self._explore[0].cell_size)
 
+    def get_exploration_clearance(self, robot_radius_m: float = 0.1, min_hits: int = 1, unseen_blocks: bool = False):
+        """Where the agent can stand, by what it has seen so far: a sage_gs.clearance.ClearanceMap of the exploration map (its
+        occupied cells, with unseen_blocks also the cells not seen yet, grown by robot_radius_m), computed on the GPU.  Positions are
+        the map's coordinates: world x, y unless start_exploration_map was given a model_to_map."""
+        from .clearance import ClearanceMap
+        cells = self.get_exploration_grid()
+        return ClearanceMap.from_topdown(self._explore[0], cells, robot_radius_m, min_hits=min_hits, unseen_blocks=unseen_blocks, renderer=self._r)
+
     def get_depth(self, clip=(0.1, 6.5)) -> np.ndarray:
         """float32 [H,W] metres, limited to [0.1, 6.5] exactly as SimpleVLNEnv.get_depth does with the simulator's
         distance_to_image_plane (simple_env.py:1573-1578: astype(float32), np.clip(depth, 0.1, 6.5)); a pixel that hit

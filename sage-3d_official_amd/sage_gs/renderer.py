@@ -1125,6 +1125,77 @@ class Renderer:
         d["seen_area_m2"] = None if cell_size is None else (occ + free) * float(cell_size) ** 2
         return d
 
+    # -- the clearance map: where an agent can stand (include/sage_gs.h sgs_clearance_map, sgs_clearance_query) ------------------------
+    def clearance_map(self, src: torch.Tensor, *, kind: Optional[str] = None, min_hits: int = 1, unseen_blocks: bool = False,
+                      max_d2: int = 0, out=None):
+        """The exact squared Euclidean distance transform of obstacle grids on the device, a whole batch in one call: (d2, counts).
+        src: a mask — uint8 or bool [ny,nx] or [B,ny,nx], non-zero is an obstacle — or a seen map — int32 [ny,nx,2] or [B,ny,nx,2]
+        as topdown_map writes it, a cell an obstacle iff its occupied hits >= min_hits, with unseen_blocks also when neither count
+        reaches min_hits.  kind ("mask" / "topdown") is inferred from the dtype and shape.  d2 is uint32-valued int32 of src's map
+        shape — cells^2 to the nearest obstacle, 0 on one, -1 (SGS_CLEARANCE_NONE) all over a map without any — and counts int32
+        [4] or [B,4]: obstacle cells, cells with 0 < d2 <= max_d2, cells with max_d2 < d2 < NONE, cells equal to NONE.
+        out=(d2, counts): contiguous int32 tensors of those shapes.  Nothing is copied to the host; asynchronous on the current
+        stream.  All integer: a map's d2 does not depend on the batch it is issued in."""
+        if not isinstance(src, torch.Tensor) or src.device != self.device:
+            raise ValueError("src must be a tensor on the renderer's device")
+        if kind is None:
+            kind = "topdown" if src.dtype == torch.int32 else "mask"
+        if kind == "mask":
+            if src.dtype == torch.bool:
+                src = src.view(torch.uint8)
+            if src.dtype != torch.uint8 or src.dim() not in (2, 3):
+                raise ValueError("a mask must be uint8 or bool [ny,nx] or [B,ny,nx]")
+            batched, maps = src.dim() == 3, src if src.dim() == 3 else src.unsqueeze(0)
+            source, per_cell = _capi.CLEARANCE_SRC_MASK8, 1
+            if unseen_blocks:
+                raise ValueError("unseen_blocks has a meaning for a seen map only")
+        elif kind == "topdown":
+            if src.dtype != torch.int32 or src.dim() not in (3, 4) or src.shape[-1] != 2:
+                raise ValueError("a seen map must be int32 [ny,nx,2] or [B,ny,nx,2]")
+            batched, maps = src.dim() == 4, src if src.dim() == 4 else src.unsqueeze(0)
+            source, per_cell = _capi.CLEARANCE_SRC_TOPDOWN, 2
+        else:
+            raise ValueError(f"unknown kind {kind!r}: 'mask' or 'topdown'")
+        b, ny, nx = int(maps.shape[0]), int(maps.shape[1]), int(maps.shape[2])
+        if min(b, ny, nx) < 1 or not maps[0].is_contiguous() or (b > 1 and int(maps.stride(0)) < ny * nx * per_cell):
+            raise ValueError("src must hold at least one map, each contiguous")
+        if not (1 <= int(min_hits) <= 0xFFFFFFFF and 0 <= int(max_d2) <= 0xFFFFFFFF):
+            raise ValueError("min_hits must be within 1 .. 2^32 - 1 and max_d2 within 0 .. 2^32 - 1")
+        shape, cshape = ((b, ny, nx), (b, 4)) if batched else ((ny, nx), (4,))
+        if out is None:
+            d2 = torch.empty(shape, dtype=torch.int32, device=self.device)
+            counts = torch.empty(cshape, dtype=torch.int32, device=self.device)
+        else:
+            d2 = self._ids_out(out[0], shape, torch.int32, "out[0]")
+            counts = self._ids_out(out[1], cshape, torch.int32, "out[1]")
+        work = torch.empty((b, ny, nx), dtype=torch.int32, device=self.device)
+        params = _capi.SgsClearanceParams(nx, ny, source, _capi.CLEARANCE_UNSEEN_BLOCKS if unseen_blocks else 0,
+                                          int(min_hits) if source == _capi.CLEARANCE_SRC_TOPDOWN else 0, int(max_d2), 0)
+        self._lib.check(self._lib.sgs_clearance_map(self._ctx, maps.data_ptr(), b, int(maps.stride(0)) if b > 1 else ny * nx * per_cell,
+                                                    C.byref(params), work.data_ptr(), d2.data_ptr(), counts.data_ptr(), self._stream()), self._ctx)
+        return d2, counts
+
+    def clearance_query(self, d2: torch.Tensor, frame, segments, n_samples: int = 10) -> torch.Tensor:
+        """The reference's position and path checks for n segments in one launch: int64 [n,2] on the device — per segment the index
+        of its first colliding sample (from 1) or 0, and the d2 under its end point (SGS_CLEARANCE_NONE = 4294967295 when that is
+        outside the map beyond the margin).  d2: one map, int32 [ny,nx] as clearance_map returns it; frame: a
+        sage_gs.clearance.ClearanceFrame; segments: float64 [n,4] (x0, y0, x1, y1), a tensor on the device or anything
+        np.asarray takes.  n_samples <= 1 checks the end point alone.  A NaN or infinite coordinate collides."""
+        if not isinstance(d2, torch.Tensor) or d2.device != self.device or d2.dtype != torch.int32 or d2.dim() != 2 or not d2.is_contiguous():
+            raise ValueError("d2 must be a contiguous int32 [ny,nx] tensor on the renderer's device")
+        if isinstance(segments, torch.Tensor):
+            segs = segments.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            segs = torch.from_numpy(np.ascontiguousarray(np.asarray(segments, np.float64))).to(self.device)
+        if segs.dim() != 2 or segs.shape[1] != 4 or segs.shape[0] < 1:
+            raise ValueError("segments must be [n,4] with n >= 1")
+        n = int(segs.shape[0])
+        out = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        f = frame.c_frame(n_samples)
+        self._lib.check(self._lib.sgs_clearance_query(self._ctx, d2.data_ptr(), int(d2.shape[1]), int(d2.shape[0]), segs.data_ptr(), n,
+                                                      C.byref(f), out.data_ptr(), self._stream()), self._ctx)
+        return out.to(torch.int64) & 0xFFFFFFFF
+
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
         self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)
