@@ -743,6 +743,75 @@ typedef struct sgs_clearance_frame {     /* 64 bytes, 8-byte aligned */
 int sgs_clearance_query(sgs_ctx* ctx, const uint32_t* d2, int nx, int ny, const double* segs, int n,
                         const sgs_clearance_frame* frame, uint32_t* out, void* hip_stream);
 
+/* ---- Geodesic distance fields and shortest paths — how FAR one place is from another when walls have to be walked round.  What the
+ * reference's trajectory generator plans with one host A* per (start, goal) pair over the grid the clearance map holds
+ * (vln_trajectory_generator.py astar_pixel: 8-connected moves, a step costs hypot — 1 or sqrt(2) —, a diagonal move may cut a corner).
+ * Here one field from a goal answers every start cell of a map, and a batch of goals on one map is one call.  No new version: no
+ * existing struct changes.
+ *
+ *   Field    for every cell the pair (a, b) = (straight steps, diagonal steps) of the cheapest 8-connected walk to any seed over cells
+ *            that are not blocked; its cost is a + b sqrt(2).  A diagonal step needs only its two end cells free.  Seeds hold (0, 0);
+ *            blocked and unreachable cells hold SGS_GEODESIC_NONE in both words.
+ *   Exact    costs are compared in integers (p = a1 - a2 and q = b2 - b1 by sign, then p^2 against 2 q^2 in 64 bits); sqrt(2) is
+ *            irrational, so two different pairs never cost the same: the cheapest pair of a cell is unique even where the walk is
+ *            not, the field is the unique fixed point of the relaxation, and its bits do not depend on the schedule, the tiling,
+ *            the batch or the number of rounds per call.
+ *   Source   SGS_GEODESIC_SRC_MASK8: uint8 [ny][nx], non-zero is blocked.  SGS_GEODESIC_SRC_D2: uint32 [ny][nx], the d2 map
+ *            sgs_clearance_map wrote: blocked iff d2 <= max_d2.  Map k begins k * map_stride ELEMENTS after map 0; field f runs on map
+ *            field_map[f], so many goals share one map.
+ *   Rounds   a round is four launches, one per tile colour (tx & 1, ty & 1) of tiles of sgs_geodesic_tile() cells square: a dirty
+ *            tile is solved in LDS with a one-cell halo and marks the neighbours dirty that see a border cell that got smaller.  A
+ *            field is final when no tile is dirty; the number of rounds that takes is bounded by the tile crossings of the longest
+ *            shortest walk.
+ *   Tables   field_map (int32 [n_fields]) and seeds (int32 [n_seeds][3] = field, i, j) are HOST arrays: the call validates them and
+ *            carries them to the device in kernel arguments; they may be changed or freed as soon as the call returns.  queries
+ *            (int32 [n_queries][3] = field, i, j) is a DEVICE buffer.
+ *   Kernels  sage-3d_official_amd/csrc/sgs_geodesic.h. */
+#define SGS_GEODESIC_NONE 0xFFFFFFFFu
+#define SGS_GEODESIC_SRC_MASK8 0
+#define SGS_GEODESIC_SRC_D2 1
+#define SGS_GEODESIC_CONTINUE 1u         /* sgs_geodesic_params.flags */
+#define SGS_GEODESIC_MAX_N 4096
+#define SGS_GEODESIC_MAX_FIELDS 65535
+#define SGS_GEODESIC_PATH_MAX_FIELDS 512
+typedef struct sgs_geodesic_params {     /* 24 bytes */
+    int32_t  nx, ny;           /* cells; 1 <= nx, ny <= 4096 */
+    int32_t  source;           /* SGS_GEODESIC_SRC_* */
+    uint32_t max_d2;           /* the d2 source: a cell is blocked iff d2 <= max_d2; ignored for a mask */
+    uint32_t flags;            /* SGS_GEODESIC_CONTINUE (sgs_geodesic_field only) */
+    int32_t  reserved;         /* 0 */
+} sgs_geodesic_params;
+/* The tile edge of the relaxation, and the uint32 words of `state` for n_fields fields of nx x ny (-1 for arguments the field call
+ * would refuse): n_fields * (2 + tiles_x * tiles_y). */
+int sgs_geodesic_tile(void);
+int64_t sgs_geodesic_state_words(int nx, int ny, int n_fields);
+/* src, dist, state and status are DEVICE buffers the caller owns; field_map and seeds are HOST arrays (see Tables).  dist is
+ * uint32 [n_fields][ny][nx][2]; state is scratch of sgs_geodesic_state_words words that carries the dirty flags from call to call;
+ * status is uint32 [n_fields][2], written whole by every call: [0] tiles still dirty — 0: the field is final —, [1] seeds ignored
+ * because their cell is blocked.  Without SGS_GEODESIC_CONTINUE the call sets dist to NONE, places the seeds, marks their tiles dirty
+ * and enqueues `rounds` rounds; with it, it takes dist and state as an earlier call with the same arguments left them and enqueues
+ * `rounds` more (seeds are validated but not placed again).  Stream-ordered and asynchronous: the call never synchronises.
+ * SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument: null src, params, field_map,
+ * seeds, dist, state or status; n_maps, n_seeds or rounds < 1; n_fields outside 1 .. 65535; nx or ny outside 1 .. 4096; an unknown
+ * source; unknown flags; reserved != 0; map_stride shorter than a map (nx * ny elements); a field_map entry outside 0 .. n_maps - 1;
+ * a seed whose field is outside 0 .. n_fields - 1 or whose cell is outside the grid; dist not 8-byte aligned; state, status or a d2
+ * src not 4-byte aligned; dist and state overlapping. */
+int sgs_geodesic_field(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* params,
+                       const int32_t* field_map, int n_fields, const int32_t* seeds, int n_seeds,
+                       uint32_t* dist, uint32_t* state, int rounds, uint32_t* status, void* hip_stream);
+/* One thread per query (field, start cell) walks a FINAL field downhill to a seed: at each cell it takes the first neighbour, in the
+ * order (di, dj) = (-1,0) (1,0) (0,-1) (0,1) (-1,-1) (-1,1) (1,-1) (1,1), that is in the grid, not blocked, and whose pair is exactly
+ * the current pair minus that step.  A path has a + b + 1 cells.  out_cells is int32 [n_queries][max_len][2] = (i, j), the start
+ * first; the cells beyond a path's length are left as they were.  out_info is uint32 [n_queries][2]: [0] the cells written, [1] a
+ * status: 0 ok; 1 the start is blocked or unreachable (no cell written); 2 the path is longer than max_len and was truncated; 3 the
+ * query names no field or no cell of the grid (no cell written); 4 a cell had no downhill neighbour — the field is not final.
+ * One launch; field_map travels in its arguments, hence n_fields <= 512 here.  params->flags must be 0.  SGS_ERR_INVALID as for
+ * sgs_geodesic_field, and: null dist, queries, out_cells or out_info; n_queries or max_len < 1; dist not 8-byte aligned; queries,
+ * out_cells or out_info not 4-byte aligned. */
+int sgs_geodesic_path(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* params,
+                      const int32_t* field_map, int n_fields, const uint32_t* dist, const int32_t* queries, int n_queries,
+                      int max_len, int32_t* out_cells, uint32_t* out_info, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

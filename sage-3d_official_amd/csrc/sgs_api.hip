@@ -29,6 +29,7 @@
 #include "sgs_similarity.h"
 #include "sgs_topdown.h"
 #include "sgs_clearance.h"
+#include "sgs_geodesic.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2351,6 +2352,136 @@ int sgs_clearance_query(sgs_ctx* ctx, const uint32_t* d2, int nx, int ny, const 
     Q.d2 = d2; Q.segs = segs; Q.out = out; Q.n = n; Q.nx = nx; Q.ny = ny; Q.margin = f->margin; Q.n_samples = f->n_samples;
     Q.min_x = f->min_x; Q.min_y = f->min_y; Q.sum_x = f->sum_x; Q.sum_y = f->sum_y; Q.scale = f->scale; Q.flags = f->flags; Q.max_d2 = f->max_d2;
     hipLaunchKernelGGL(sgs::k_clear_query, dim3((unsigned)((n + SGS_CLEAR_THREADS - 1) / SGS_CLEAR_THREADS)), dim3(SGS_CLEAR_THREADS), 0, st, Q);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_geodesic_field, sgs_geodesic_path (csrc/sgs_geodesic.h) --------------------------------------------------------------------------
+static_assert(sizeof(sgs_geodesic_params) == 24, "sgs_geodesic_params is six 4-byte fields");
+static_assert(SGS_GEODESIC_NONE == SGS_GEO_NONE && SGS_GEODESIC_SRC_MASK8 == SGS_GEO_SRC_MASK8 && SGS_GEODESIC_SRC_D2 == SGS_GEO_SRC_D2 &&
+              SGS_GEODESIC_MAX_N == SGS_GEO_MAX_N && SGS_GEODESIC_MAX_FIELDS == SGS_GEO_MAX_FIELDS && SGS_GEODESIC_PATH_MAX_FIELDS == SGS_GEO_PATH_MAX_FIELDS,
+              "the kernels' constants are the header's");
+
+// What sgs_geodesic_field and sgs_geodesic_path refuse alike: the map, the params and the field table (a HOST array).
+static int geodesic_check(sgs_ctx* ctx, const char* who, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* p,
+                          const int32_t* field_map, int n_fields, int max_fields) {
+    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
+    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
+    if (!field_map) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null field_map", who);
+    if (n_maps < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_maps = %d", who, n_maps);
+    if (n_fields < 1 || n_fields > max_fields) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_fields = %d (1 <= n_fields <= %d)", who, n_fields, max_fields);
+    if (p->nx < 1 || p->ny < 1 || p->nx > SGS_GEO_MAX_N || p->ny > SGS_GEO_MAX_N)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, (int)p->nx, (int)p->ny, SGS_GEO_MAX_N);
+    if (p->source != SGS_GEODESIC_SRC_MASK8 && p->source != SGS_GEODESIC_SRC_D2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
+    if (p->flags & ~SGS_GEODESIC_CONTINUE) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
+    if (map_stride < (int64_t)p->nx * p->ny)
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: maps overlap (map_stride %lld elements, a map has %lld)", who, (long long)map_stride, (long long)p->nx * p->ny);
+    for (int f = 0; f < n_fields; ++f)
+        if (field_map[f] < 0 || field_map[f] >= n_maps) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: field_map[%d] = %d (n_maps = %d)", who, f, (int)field_map[f], n_maps);
+    if (p->source == SGS_GEODESIC_SRC_D2 && reinterpret_cast<uintptr_t>(src) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src %p is not 4-byte aligned", who, src);
+    return SGS_OK;
+}
+
+extern "C" {
+
+int sgs_geodesic_tile(void) { return SGS_GEO_TILE; }
+
+int64_t sgs_geodesic_state_words(int nx, int ny, int n_fields) {
+    if (nx < 1 || ny < 1 || nx > SGS_GEO_MAX_N || ny > SGS_GEO_MAX_N || n_fields < 1 || n_fields > SGS_GEO_MAX_FIELDS) return -1;
+    const int64_t tiles = (int64_t)((nx + SGS_GEO_TILE - 1) / SGS_GEO_TILE) * ((ny + SGS_GEO_TILE - 1) / SGS_GEO_TILE);
+    return (int64_t)n_fields * (2 + tiles);
+}
+
+int sgs_geodesic_field(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* p,
+                       const int32_t* field_map, int n_fields, const int32_t* seeds, int n_seeds,
+                       uint32_t* dist, uint32_t* state, int rounds, uint32_t* status, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_geodesic_field";
+    if (const int rc = geodesic_check(ctx, who, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_MAX_FIELDS)) return rc;
+    if (!seeds) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null seeds", who);
+    if (!dist) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dist", who);
+    if (!state) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null state", who);
+    if (!status) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null status", who);
+    if (n_seeds < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_seeds = %d", who, n_seeds);
+    if (rounds < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rounds = %d", who, rounds);
+    for (int s = 0; s < n_seeds; ++s) {
+        const int32_t* e = seeds + 3 * (size_t)s;
+        if (e[0] < 0 || e[0] >= n_fields) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: seeds[%d] names field %d (n_fields = %d)", who, s, (int)e[0], n_fields);
+        if (e[1] < 0 || e[1] >= p->nx || e[2] < 0 || e[2] >= p->ny)
+            SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: seeds[%d] = (%d, %d) is outside the grid %d x %d", who, s, (int)e[1], (int)e[2], (int)p->nx, (int)p->ny);
+    }
+    if (reinterpret_cast<uintptr_t>(dist) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p is not 8-byte aligned", who, (void*)dist);
+    if (reinterpret_cast<uintptr_t>(state) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: state %p is not 4-byte aligned", who, (void*)state);
+    if (reinterpret_cast<uintptr_t>(status) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: status %p is not 4-byte aligned", who, (void*)status);
+    const int64_t cells = (int64_t)p->nx * p->ny, state_words = sgs_geodesic_state_words(p->nx, p->ny, n_fields);
+    const uintptr_t a_dist = reinterpret_cast<uintptr_t>(dist), a_state = reinterpret_cast<uintptr_t>(state);
+    const uint64_t dist_bytes = 8ull * (uint64_t)n_fields * (uint64_t)cells, state_bytes = 4ull * (uint64_t)state_words;
+    if (a_dist < a_state + state_bytes && a_state < a_dist + dist_bytes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p and state %p overlap", who, (void*)dist, (void*)state);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::GeodesicJob J;
+    J.src = src; J.dist = reinterpret_cast<unsigned long long*>(dist); J.state = state; J.stride = map_stride;
+    J.nx = p->nx; J.ny = p->ny; J.n_fields = n_fields; J.kind = p->source; J.max_d2 = p->max_d2;
+    J.tiles_x = (p->nx + SGS_GEO_TILE - 1) / SGS_GEO_TILE; J.tiles_y = (p->ny + SGS_GEO_TILE - 1) / SGS_GEO_TILE;
+    J.colour_x = J.colour_y = 0;
+    if (!(p->flags & SGS_GEODESIC_CONTINUE)) {
+        const int64_t pairs = (int64_t)n_fields * cells, zero_words = state_words - n_fields;
+        const unsigned blocks = (unsigned)std::min<int64_t>((std::max(pairs, zero_words) + SGS_GEO_THREADS - 1) / SGS_GEO_THREADS, 4096);
+        hipLaunchKernelGGL(sgs::k_geo_fill, dim3(blocks), dim3(SGS_GEO_THREADS), 0, st, J.dist, (long long)pairs, state + n_fields, (long long)zero_words);
+        for (int f0 = 0; f0 < n_fields; f0 += SGS_GEO_PUT_WORDS) {                   // the field table travels in kernel arguments: no host buffer outlives the call
+            sgs::GeodesicWords W;
+            const int n = std::min(SGS_GEO_PUT_WORDS, n_fields - f0);
+            for (int k = 0; k < SGS_GEO_PUT_WORDS; ++k) W.w[k] = k < n ? (unsigned)field_map[f0 + k] : 0u;
+            hipLaunchKernelGGL(sgs::k_geo_put, dim3(1), dim3(SGS_GEO_PUT_WORDS), 0, st, state + f0, W, n);
+        }
+        for (int s0 = 0; s0 < n_seeds; s0 += SGS_GEO_SEEDS_PER_LAUNCH) {
+            sgs::GeodesicSeeds S;
+            const int n = std::min(SGS_GEO_SEEDS_PER_LAUNCH, n_seeds - s0);
+            for (int k = 0; k < SGS_GEO_SEEDS_PER_LAUNCH; ++k)
+                for (int c = 0; c < 3; ++c) S.s[k][c] = k < n ? seeds[3 * (size_t)(s0 + k) + c] : 0;
+            hipLaunchKernelGGL(sgs::k_geo_seed, dim3(1), dim3(SGS_GEO_SEEDS_PER_LAUNCH), 0, st, J, S, n);
+        }
+    }
+    for (int r = 0; r < rounds; ++r)
+        for (int colour = 0; colour < 4; ++colour) {
+            sgs::GeodesicJob K = J;
+            K.colour_x = colour & 1; K.colour_y = colour >> 1;
+            const int cx = (J.tiles_x - K.colour_x + 1) / 2, cy = (J.tiles_y - K.colour_y + 1) / 2;      // the tiles of this colour
+            if (cx < 1 || cy < 1) continue;
+            hipLaunchKernelGGL(sgs::k_geo_relax, dim3((unsigned)cx, (unsigned)cy, (unsigned)n_fields), dim3(SGS_GEO_THREADS), 0, st, K);
+        }
+    hipLaunchKernelGGL(sgs::k_geo_status, dim3((unsigned)n_fields), dim3(SGS_GEO_THREADS), 0, st, J, status);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+int sgs_geodesic_path(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* p,
+                      const int32_t* field_map, int n_fields, const uint32_t* dist, const int32_t* queries, int n_queries,
+                      int max_len, int32_t* out_cells, uint32_t* out_info, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_geodesic_path";
+    if (const int rc = geodesic_check(ctx, who, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_PATH_MAX_FIELDS)) return rc;
+    if (p->flags) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    if (!dist) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dist", who);
+    if (!queries) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null queries", who);
+    if (!out_cells) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_cells", who);
+    if (!out_info) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_info", who);
+    if (n_queries < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_queries = %d", who, n_queries);
+    if (max_len < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: max_len = %d", who, max_len);
+    if (reinterpret_cast<uintptr_t>(dist) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p is not 8-byte aligned", who, (const void*)dist);
+    if (reinterpret_cast<uintptr_t>(queries) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: queries %p is not 4-byte aligned", who, (const void*)queries);
+    if (reinterpret_cast<uintptr_t>(out_cells) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_cells %p is not 4-byte aligned", who, (void*)out_cells);
+    if (reinterpret_cast<uintptr_t>(out_info) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_info %p is not 4-byte aligned", who, (void*)out_info);
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::GeodesicPathJob Q;
+    Q.src = src; Q.dist = reinterpret_cast<const unsigned long long*>(dist); Q.queries = queries; Q.cells = out_cells; Q.info = out_info;
+    Q.stride = map_stride; Q.nx = p->nx; Q.ny = p->ny; Q.n_fields = n_fields; Q.kind = p->source; Q.n = n_queries; Q.max_len = max_len; Q.max_d2 = p->max_d2;
+    for (int f = 0; f < SGS_GEO_PATH_MAX_FIELDS; ++f) Q.field_map[f] = f < n_fields ? field_map[f] : 0;
+    hipLaunchKernelGGL(sgs::k_geo_path, dim3((unsigned)((n_queries + SGS_GEO_THREADS - 1) / SGS_GEO_THREADS)), dim3(SGS_GEO_THREADS), 0, st, Q);
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }

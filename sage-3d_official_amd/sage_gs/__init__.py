@@ -32,7 +32,7 @@ def __getattr__(name):          # torch is imported only when the renderer is ac
     if name in ("Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "TopdownGrid", "render", "default_renderer"):
         from . import renderer
         return getattr(renderer, name)
-    if name in ("scenes", "camera", "dist", "adapter", "ply", "mesh", "clearance"):
+    if name in ("scenes", "camera", "dist", "adapter", "ply", "mesh", "clearance", "geodesic"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -39,7 +39,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_png_params_default", "sgs_png_bound", "sgs_encode_png", "sgs_png_status",
            "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity",
            "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary",
-           "sgs_clearance_map", "sgs_clearance_query")
+           "sgs_clearance_map", "sgs_clearance_query",
+           "sgs_geodesic_tile", "sgs_geodesic_state_words", "sgs_geodesic_field", "sgs_geodesic_path")
 
 
 class SgsError(RuntimeError):
@@ -203,6 +204,22 @@ class SgsClearanceFrame(C.Structure):
 assert C.sizeof(SgsClearanceParams) == 28 and C.sizeof(SgsClearanceFrame) == 64 and SgsClearanceFrame.reserved.offset == 56
 
 
+GEODESIC_NONE = 0xFFFFFFFF                   # include/sage_gs.h SGS_GEODESIC_NONE: both words of a blocked or unreachable cell
+GEODESIC_SRC_MASK8, GEODESIC_SRC_D2 = 0, 1
+GEODESIC_CONTINUE = 1                        # sgs_geodesic_params.flags
+GEODESIC_MAX_N, GEODESIC_MAX_FIELDS, GEODESIC_PATH_MAX_FIELDS = 4096, 65535, 512
+GEODESIC_PATH_OK, GEODESIC_PATH_UNREACHABLE, GEODESIC_PATH_TRUNCATED, GEODESIC_PATH_INVALID, GEODESIC_PATH_NOT_FINAL = 0, 1, 2, 3, 4
+
+
+class SgsGeodesicParams(C.Structure):
+    """include/sage_gs.h sgs_geodesic_params: the map's size, what its source is, and whether a field call continues an earlier one."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("source", C.c_int32), ("max_d2", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_int32)]
+
+
+assert C.sizeof(SgsGeodesicParams) == 24
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -295,6 +312,10 @@ class Lib:
         lib.sgs_topdown_summary.argtypes = [vp, vp, i32, i32, C.c_uint32, vp, vp]
         lib.sgs_clearance_map.argtypes = [vp, vp, i32, i64, C.POINTER(SgsClearanceParams), vp, vp, vp, vp]
         lib.sgs_clearance_query.argtypes = [vp, vp, i32, i32, vp, i32, C.POINTER(SgsClearanceFrame), vp, vp]
+        lib.sgs_geodesic_tile.argtypes = []
+        lib.sgs_geodesic_state_words.argtypes = [i32, i32, i32]; lib.sgs_geodesic_state_words.restype = i64
+        lib.sgs_geodesic_field.argtypes = [vp, vp, i32, i64, C.POINTER(SgsGeodesicParams), vp, i32, vp, i32, vp, vp, i32, vp, vp]
+        lib.sgs_geodesic_path.argtypes = [vp, vp, i32, i64, C.POINTER(SgsGeodesicParams), vp, i32, vp, vp, i32, i32, vp, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

@@ -174,6 +174,25 @@ class ClearanceMap:
     def check_collision_at_position(self, x: float, y: float) -> bool:
         return self.check_collision_3d([x, y, 0.0])
 
+    def geodesic_field(self, goals_xy):
+        """How far every cell is from the nearest of goals_xy ([n, 2] or [n, 3] positions as the checks above take them) when the
+        grown obstacles have to be walked round: a sage_gs.geodesic.GeodesicField of this map."""
+        from .geodesic import GeodesicField
+        return GeodesicField.from_clearance(self, goals_xy=goals_xy)
+
+    def cells_of(self, xy) -> np.ndarray:
+        """int64 [n, 2] = (i, j): the pixel of every position of xy, mapped and rounded as the queries map and round it (negation,
+        flips, rint of a true division); not clamped — a position outside the map gives a cell outside 0 .. width - 1, 0 .. height - 1."""
+        p = np.asarray(xy, np.float64).reshape(-1, np.asarray(xy).shape[-1])[:, :2].copy()
+        f = self.frame
+        if f.negate_xy:
+            p = -p
+        if f.flip_x:
+            p[:, 0] = (float(f.min_x) + float(f.max_x)) - p[:, 0]
+        if f.flip_y:
+            p[:, 1] = (float(f.min_y) + float(f.max_y)) - p[:, 1]
+        return np.stack([np.rint((p[:, 0] - f.min_x) / f.scale), np.rint((p[:, 1] - f.min_y) / f.scale)], 1).astype(np.int64)
+
     @property
     def obstacle_map(self) -> np.ndarray:
         """uint8 [height, width]: 1 where the grown obstacles are — the reference's obstacle_map after inflation."""

@@ -1196,6 +1196,104 @@ class Renderer:
                                                       C.byref(f), out.data_ptr(), self._stream()), self._ctx)
         return out.to(torch.int64) & 0xFFFFFFFF
 
+    # -- geodesic fields and shortest paths (include/sage_gs.h sgs_geodesic_field, sgs_geodesic_path) ---------------------------------
+    def _geodesic_source(self, src, max_d2):
+        if not isinstance(src, torch.Tensor) or src.device != self.device:
+            raise ValueError("src must be a tensor on the renderer's device")
+        if src.dtype == torch.bool:
+            src = src.view(torch.uint8)
+        if src.dtype == torch.uint8:
+            source = _capi.GEODESIC_SRC_MASK8
+            if max_d2 is not None:
+                raise ValueError("max_d2 has a meaning for a d2 map only")
+        elif src.dtype == torch.int32:
+            source = _capi.GEODESIC_SRC_D2
+            if max_d2 is None:
+                raise ValueError("a d2 map needs max_d2: a cell is blocked iff d2 <= max_d2")
+        else:
+            raise ValueError("src must be a mask (uint8 or bool) or a d2 map (int32 as clearance_map returns it), [ny,nx] or [B,ny,nx]")
+        if src.dim() not in (2, 3):
+            raise ValueError("src must be [ny,nx] or [B,ny,nx]")
+        maps = src if src.dim() == 3 else src.unsqueeze(0)
+        b, ny, nx = (int(v) for v in maps.shape)
+        if min(b, ny, nx) < 1 or max(nx, ny) > _capi.GEODESIC_MAX_N or not maps[0].is_contiguous() or (b > 1 and int(maps.stride(0)) < ny * nx):
+            raise ValueError(f"src must hold at least one map of 1 .. {_capi.GEODESIC_MAX_N} cells a side, each contiguous")
+        if max_d2 is not None and not 0 <= int(max_d2) <= 0xFFFFFFFF:
+            raise ValueError("max_d2 must be within 0 .. 2^32 - 1")
+        return maps, source, b, ny, nx, int(maps.stride(0)) if b > 1 else ny * nx
+
+    @staticmethod
+    def _geodesic_table(rows, width, what):
+        t = np.ascontiguousarray(np.asarray(rows, np.int64).reshape(-1, width) if width > 1 else np.asarray(rows, np.int64).reshape(-1))
+        if len(t) < 1 or np.abs(t).max() > 0x7FFFFFFF:
+            raise ValueError(f"{what} must hold at least one row of int32 values")
+        return np.ascontiguousarray(t.astype(np.int32))
+
+    def geodesic_field(self, src: torch.Tensor, seeds, field_map=None, max_d2: Optional[int] = None, rounds: Optional[int] = None):
+        """Geodesic distance fields on the device: for every cell of a blocked grid the pair (a, b) = (straight steps, diagonal steps)
+        of the cheapest 8-connected walk to any seed of its field — cost a + b sqrt(2), compared exactly in integers, a diagonal step
+        needing only its two end cells free.  src: a mask (uint8 or bool, non-zero is blocked) or a d2 map (int32 as clearance_map
+        returns it, blocked iff d2 <= max_d2), [ny,nx] or [B,ny,nx].  seeds: [(field, i, j)] on the host; field_map: the map of every
+        field (default: one field per map).  Returns (steps, blocked_seeds): steps int32 [n_fields,ny,nx,2], uint32-valued — -1 in
+        both words (SGS_GEODESIC_NONE) where a cell is blocked or unreachable —, and per field the seeds ignored because their cell
+        is blocked.  This method owns the loop: a first call of `rounds` rounds (default 2 (tiles_x + tiles_y)), the status read
+        back, and SGS_GEODESIC_CONTINUE calls of as many rounds until no tile of any field is dirty.  Raises if that takes more than
+        nx * ny rounds, which no map needs.  The result does not depend on `rounds`: the field is the relaxation's unique fixed point."""
+        maps, source, b, ny, nx, stride = self._geodesic_source(src, max_d2)
+        fm = self._geodesic_table(np.arange(b) if field_map is None else field_map, 1, "field_map")
+        sd = self._geodesic_table(seeds, 3, "seeds")
+        nf = len(fm)
+        T = int(self._lib.sgs_geodesic_tile())
+        per_call = 2 * ((nx + T - 1) // T + (ny + T - 1) // T) if rounds is None else int(rounds)
+        words = int(self._lib.sgs_geodesic_state_words(nx, ny, nf))
+        if words < 0 or per_call < 1:
+            raise ValueError(f"{nf} fields of {nx} x {ny} cells, {per_call} rounds a call: outside what sgs_geodesic_field takes")
+        dist = torch.empty((nf, ny, nx, 2), dtype=torch.int32, device=self.device)
+        state = torch.empty((words,), dtype=torch.int32, device=self.device)
+        status = torch.empty((nf, 2), dtype=torch.int32, device=self.device)
+        total, flags = 0, 0
+        while True:
+            params = _capi.SgsGeodesicParams(nx, ny, source, int(max_d2 or 0), flags, 0)
+            self._lib.check(self._lib.sgs_geodesic_field(self._ctx, maps.data_ptr(), b, stride, C.byref(params), fm.ctypes.data, nf, sd.ctypes.data,
+                                                         len(sd), dist.data_ptr(), state.data_ptr(), per_call, status.data_ptr(), self._stream()), self._ctx)
+            total += per_call
+            st = status.cpu().numpy().view(np.uint32)
+            if not st[:, 0].any():
+                break
+            if total > nx * ny:
+                raise RuntimeError(f"geodesic_field: tiles are still dirty after {total} rounds on a map of {nx} x {ny}")
+            flags = _capi.GEODESIC_CONTINUE
+        self.last_geodesic_rounds = total
+        return dist, st[:, 1].astype(np.int64)
+
+    def geodesic_path(self, src: torch.Tensor, steps: torch.Tensor, queries, field_map=None, max_d2: Optional[int] = None, max_len: Optional[int] = None):
+        """Shortest paths down a final field, one thread per query, one launch: (cells, info).  src, field_map, max_d2: as given to
+        geodesic_field; steps: what it returned; queries: [(field, i, j)], a tensor on the device or anything np.asarray takes.
+        cells int32 [n,max_len,2] = (i, j) from the start to a seed — max_len defaults to nx * ny, so give one —, info int64 [n,2]:
+        the cells written and a status (0 ok, 1 the start is blocked or unreachable, 2 truncated at max_len, 3 no such field or
+        cell, 4 the field is not final).  Among equal-cost walks the one the fixed neighbour order picks."""
+        maps, source, b, ny, nx, stride = self._geodesic_source(src, max_d2)
+        fm = self._geodesic_table(np.arange(b) if field_map is None else field_map, 1, "field_map")
+        if not isinstance(steps, torch.Tensor) or steps.device != self.device or steps.dtype != torch.int32 or not steps.is_contiguous() or \
+                tuple(steps.shape) != (len(fm), ny, nx, 2):
+            raise ValueError(f"steps must be a contiguous int32 [{len(fm)},{ny},{nx},2] tensor on the renderer's device")
+        if isinstance(queries, torch.Tensor):
+            q = queries.to(device=self.device, dtype=torch.int32).contiguous()
+        else:
+            q = torch.from_numpy(self._geodesic_table(queries, 3, "queries")).to(self.device)
+        if q.dim() != 2 or q.shape[1] != 3 or q.shape[0] < 1:
+            raise ValueError("queries must be [n,3] with n >= 1")
+        n = int(q.shape[0])
+        max_len = nx * ny if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError("max_len must be >= 1")
+        cells = torch.full((n, max_len, 2), -1, dtype=torch.int32, device=self.device)
+        info = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        params = _capi.SgsGeodesicParams(nx, ny, source, int(max_d2 or 0), 0, 0)
+        self._lib.check(self._lib.sgs_geodesic_path(self._ctx, maps.data_ptr(), b, stride, C.byref(params), fm.ctypes.data, len(fm), steps.data_ptr(),
+                                                    q.data_ptr(), n, max_len, cells.data_ptr(), info.data_ptr(), self._stream()), self._ctx)
+        return cells, info.to(torch.int64) & 0xFFFFFFFF
+
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
         self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)
