@@ -10,26 +10,11 @@ import os
 import numpy as np
 
 import clearance_ref as ref
-import jpeg_cases
+from abi_driver import POISON, SENTINEL, AbiDriver, GpuBuffers      # POISON: work, d2, out_counts and out before every call
 
-SENTINEL = jpeg_cases.SENTINEL
-POISON = 0xA5A5A5A5                       # work, d2, out_counts and out before every call (SENTINEL bytes)
 NONE = ref.NONE
 INF, NAN = float("inf"), float("nan")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "clearance_golden.json")
-
-
-def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_clearance.h is newer than it (emu_harness's staleness list predates the header)."""
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_clearance.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
-
-
-def start_emu_copy(base, edits, name="libsage_gs_clearance_copy.so"):
-    import object_cases
-    return object_cases.start_emu_copy(base, edits, name)
 
 
 # ---- pictures: {name: bool [ny, nx]} ---------------------------------------------------------------------------------------------------
@@ -115,18 +100,8 @@ def c_frame(f: ref.Frame):
     return _capi.SgsClearanceFrame(f.min_x, f.min_y, f.sum_x, f.sum_y, f.scale, f.flags, f.margin, f.max_d2, f.n_samples, f.reserved)
 
 
-class AbiClearance(jpeg_cases.AbiEncoder):
+class AbiClearance(AbiDriver):
     """sgs_clearance_map and sgs_clearance_query over host buffers; a GPU driver overrides the buffer hooks (GpuClearance)."""
-
-    def _put(self, data, slack=0):
-        """A buffer of SENTINEL bytes holding `data` (any array) at its start: (keep, address, getter of a host copy)."""
-        b = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-        keep, ptr, get = self._bytes(len(b) + slack)
-        self._fill(keep, b)
-        return keep, ptr, get
-
-    def _fill(self, keep, b):
-        keep[:len(b)] = b
 
     def call(self, src, n, stride, params, work, d2, counts, stream=None):
         return int(self.lib.sgs_clearance_map(self.ctx, src, int(n), int(stride), None if params is None else C.byref(params), work, d2, counts, stream))
@@ -177,12 +152,8 @@ class AbiClearance(jpeg_cases.AbiEncoder):
         return ob[:8 * n].view(np.uint32).reshape(n, 2).astype(np.int64)
 
 
-class GpuClearance(jpeg_cases.GpuBuffers, AbiClearance):
+class GpuClearance(GpuBuffers, AbiClearance):
     """AbiClearance over torch device buffers, on a Renderer's context."""
-
-    def _fill(self, keep, b):
-        import torch
-        keep[:len(b)] = torch.from_numpy(np.array(b)).to(keep.device)
 
 
 def check_map(name, d2, counts, ob, max_d2=0):

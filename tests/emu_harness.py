@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import shutil
 import subprocess
 import sys
 
@@ -18,14 +19,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "sage-3d_official_amd")
 EMU_DIR = os.path.join(ROOT, "tests", "hipemu")
 EMU_LIB = os.path.join(EMU_DIR, "_build", "libsage_gs_emu.so")
-KERNEL_SRCS = ("sgs_api.hip", "sgs_kernels.h", "sgs_mesh.h", "sgs_jpeg.h", "sgs_png.h", "sgs_encode.h", "sgs_resize.h", "sgs_objects.h",
-               "sgs_common.h", "sgs_own.h")                                                 # csrc/ files the library is built from
-SRCS = [os.path.join(PKG, "csrc", n) for n in KERNEL_SRCS] + \
-       [os.path.join(EMU_DIR, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "sage_gs.h")]
+OUTSIDE_SRCS = [os.path.join(EMU_DIR, "hip", "hip_runtime.h"), os.path.join(ROOT, "include", "sage_gs.h")]
 
 if PKG not in sys.path:
     sys.path.insert(0, PKG)
 from sage_gs import _capi  # noqa: E402
+
+
+def sources(csrc=None):
+    """The files a library of `csrc` (default: the product's csrc/) is built from: every *.h and *.hip of that directory, the emulator's
+    hip_runtime.h and include/sage_gs.h.  One newer than the library makes it stale."""
+    csrc = os.path.join(PKG, "csrc") if csrc is None else str(csrc)
+    return sorted(os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".h", ".hip"))) + OUTSIDE_SRCS
+
+
+def stale(lib_out, srcs):
+    """Whether lib_out is missing or older than one of srcs."""
+    return not os.path.exists(lib_out) or any(os.path.getmtime(s) > os.path.getmtime(lib_out) for s in srcs)
 
 
 def build_emu(force=False, src_dir=None, out=None, wait=True):
@@ -34,18 +44,51 @@ def build_emu(force=False, src_dir=None, out=None, wait=True):
     its Popen (None when the library is up to date); the caller waits."""
     csrc = os.path.join(PKG, "csrc") if src_dir is None else str(src_dir)
     lib_out = EMU_LIB if out is None else str(out)
-    srcs = [os.path.join(csrc, n) for n in KERNEL_SRCS] + SRCS[len(KERNEL_SRCS):]
     os.makedirs(os.path.dirname(lib_out), exist_ok=True)
-    stale = force or not os.path.exists(lib_out) or any(
-        os.path.getmtime(s) > os.path.getmtime(lib_out) for s in srcs)
-    if not stale:
+    if not force and not stale(lib_out, sources(csrc)):
         return lib_out if wait else None
     cmd = ["g++", "-x", "c++", "-std=c++17", "-O2", "-g", "-fopenmp", "-fPIC", "-shared",
-           "-I", EMU_DIR, srcs[0], "-o", lib_out]
+           "-I", EMU_DIR, os.path.join(csrc, "sgs_api.hip"), "-o", lib_out]
     if not wait:
         return subprocess.Popen(cmd)
     subprocess.check_call(cmd)
     return lib_out
+
+
+# ---- copies of csrc/ with edits made in them (mutants, other constants) -------------------------------------------------------------------
+def apply_edits(csrc, edits):
+    """Makes edits = {file of csrc/: [(anchor, replacement)]} in the directory `csrc`, in list order.  Every anchor must occur exactly
+    once at the moment it is applied."""
+    for fname, pairs in edits.items():
+        path = os.path.join(str(csrc), fname)
+        with open(path) as fh:
+            text = fh.read()
+        for old, new in pairs:
+            assert text.count(old) == 1, f"{fname}: anchor found {text.count(old)} times: {old!r}"
+            text = text.replace(old, new)
+        with open(path, "w") as fh:
+            fh.write(text)
+
+
+def start_emu_copy(base, edits, name="libsage_gs_emu_copy.so"):
+    """A copy of csrc/ under `base` with `edits` made in it (apply_edits), and its emulator build started: (the library's path, the
+    compiler's Popen).  The caller waits."""
+    base = str(base)
+    csrc = os.path.join(base, "pkg", "csrc")
+    shutil.copytree(os.path.join(PKG, "csrc"), csrc)
+    os.makedirs(os.path.join(base, "include"))
+    shutil.copy(os.path.join(ROOT, "include", "sage_gs.h"), os.path.join(base, "include", "sage_gs.h"))     # (../../include/sage_gs.h)
+    apply_edits(csrc, edits)
+    out = os.path.join(base, name)
+    return out, build_emu(src_dir=csrc, out=out, wait=False)
+
+
+def build_mutants(root, mutants, lib_name):
+    """mutants = {name: edits}: every mutant's emulator library, compiled side by side (one g++ each) -> {name: library path}."""
+    started = {name: start_emu_copy(os.path.join(str(root), f"m{k}"), edits, lib_name) for k, (name, edits) in enumerate(mutants.items())}
+    for name, (_, proc) in started.items():
+        assert proc.wait() == 0, f"{name}: the mutant does not compile"
+    return {name: path for name, (path, _) in started.items()}
 
 
 _lib = None

@@ -11,24 +11,10 @@ import os
 import numpy as np
 
 import geodesic_ref as ref
-import jpeg_cases
+from abi_driver import SENTINEL, AbiDriver, GpuBuffers
 
-SENTINEL = jpeg_cases.SENTINEL
 NONE = ref.NONE
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "geodesic_golden.json")
-
-
-def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_geodesic.h is newer than it (emu_harness's staleness list predates the header)."""
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_geodesic.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
-
-
-def start_emu_copy(base, edits, name="libsage_gs_geodesic_copy.so"):
-    import object_cases
-    return object_cases.start_emu_copy(base, edits, name)
 
 
 def c_params(nx, ny, source=ref.SRC_MASK8, max_d2=0, flags=0, reserved=0):
@@ -46,22 +32,13 @@ def default_rounds(T, nx, ny):
 
 
 # ---- the C ABI over plain buffers -----------------------------------------------------------------------------------------------------
-class AbiGeodesic(jpeg_cases.AbiEncoder):
+class AbiGeodesic(AbiDriver):
     """sgs_geodesic_field and sgs_geodesic_path over host buffers; a GPU driver overrides the buffer hooks (GpuGeodesic).  field_map
     and seeds are host arrays for both."""
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
         self.T = int(self.lib.sgs_geodesic_tile())
-
-    def _put(self, data, slack=0):
-        b = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
-        keep, ptr, get = self._bytes(len(b) + slack)
-        self._fill(keep, b)
-        return keep, ptr, get
-
-    def _fill(self, keep, b):
-        keep[:len(b)] = b
 
     def call(self, src, n_maps, stride, params, field_map, n_fields, seeds, n_seeds, dist, state, rounds, status, stream=None):
         return int(self.lib.sgs_geodesic_field(self.ctx, src, int(n_maps), int(stride), None if params is None else C.byref(params), field_map, int(n_fields),
@@ -132,16 +109,8 @@ class AbiGeodesic(jpeg_cases.AbiEncoder):
         return cb[:cell_bytes].view(np.int32).reshape(len(q), max_len, 2).copy(), ib[:8 * len(q)].view(np.uint32).reshape(len(q), 2).copy()
 
 
-class GpuGeodesic(jpeg_cases.GpuBuffers, AbiGeodesic):
+class GpuGeodesic(GpuBuffers, AbiGeodesic):
     """AbiGeodesic over torch device buffers, on a Renderer's context."""
-
-    def __init__(self, renderer):
-        jpeg_cases.GpuBuffers.__init__(self, renderer)
-        self.T = int(self.lib.sgs_geodesic_tile())
-
-    def _fill(self, keep, b):
-        import torch
-        keep[:len(b)] = torch.from_numpy(np.array(b)).to(keep.device)
 
 
 # ---- pictures: (blocked bool [ny, nx], seeds [(i, j)]) -----------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """The JPEG encoder's checks, shared by the CPU-emulator tests (test_emu_jpeg.py) and the GPU tests (test_gpu_jpeg.py): the image
-set, the driver of the C ABI over plain buffers (AbiEncoder: the PNG encoder's is built on it too), and the assertions on a file
-(coefficients, structure, interoperability, fidelity)."""
+set, the driver of the C ABI over abi_driver's buffers (AbiEncoder: the PNG encoder's is built on it too), and the assertions on a
+file (coefficients, structure, interoperability, fidelity)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,10 +9,10 @@ import io
 import numpy as np
 
 import jpeg_ref
+from abi_driver import SENTINEL, AbiDriver, GpuBuffers  # noqa: F401  (SENTINEL, GpuBuffers: re-exported)
 
 QUALITIES = (50, 75, 95, 100)
 SUBSAMPLINGS = ("4:2:0", "4:4:4")
-SENTINEL = 0xA5
 MAX_WINDOW_SHARE = 0.01
 
 
@@ -73,40 +73,10 @@ def image_set():
     }
 
 
-class AbiEncoder:
-    """One of the file encoders of the C ABI (sgs_encode_jpeg, sgs_encode_png) over host buffers (the emulator's 'device' is the
-    host).  A subclass names its two entry points and supplies _params and bound, which take the encoder's own arguments — the ones
-    encode and encode_one pass through.  A GPU driver overrides the four buffer hooks (GpuBuffers)."""
+class AbiEncoder(AbiDriver):
+    """One of the file encoders of the C ABI (sgs_encode_jpeg, sgs_encode_png) over abi_driver's buffers.  A subclass names its two
+    entry points and supplies _params and bound, which take the encoder's own arguments — the ones encode and encode_one pass through."""
     ENCODE = STATUS = None
-
-    def __init__(self, lib, ctx=None):
-        from sage_gs import _capi
-        self._capi, self.lib = _capi, lib
-        self.ctx, self._own = ctx, ctx is None
-        if ctx is None:
-            self.ctx = C.c_void_p()
-            lib.check(lib.sgs_create(0, _capi.BACKEND_HIP, C.byref(self.ctx)))
-
-    def close(self):
-        if self._own and self.ctx:
-            self.lib.sgs_destroy(self.ctx)
-            self.ctx = None
-
-    # buffer hooks: (object that keeps the memory alive, address[, getter of a host copy])
-    def _frames(self, frames):
-        a = np.ascontiguousarray(frames, np.float32)
-        return a, a.ctypes.data
-
-    def _bytes(self, n):
-        a = np.full(n, SENTINEL, np.uint8)
-        return a, a.ctypes.data, lambda: a
-
-    def _i64(self, n):
-        a = np.full(n, -1, np.int64)
-        return a, a.ctypes.data, lambda: a
-
-    def _sync(self):
-        pass
 
     def encode(self, frames, *args, capacity=None, slack=64, stride=None, **kw):
         """frames fp32 [n,H,W,...]; args, kw: the encoder's own (_params).  Returns dict(files, offsets, sizes, buffer (capacity + slack
@@ -148,33 +118,6 @@ class AbiJpeg(AbiEncoder):
 
     def bound(self, w, h, quality, subsampling):
         return int(self.lib.sgs_jpeg_bound(int(w), int(h), C.byref(self._params(quality, subsampling))))
-
-
-class GpuBuffers:
-    """The buffer hooks over torch device buffers, on a Renderer's context: class GpuX(GpuBuffers, AbiX)."""
-
-    def __init__(self, renderer):
-        super().__init__(renderer._lib, renderer._ctx)
-        self.r = renderer
-
-    def _frames(self, frames):
-        import torch
-        t = torch.from_numpy(np.ascontiguousarray(frames, np.float32)).to(self.r.device)
-        return t, t.data_ptr()
-
-    def _bytes(self, n):
-        import torch
-        t = torch.full((n,), SENTINEL, dtype=torch.uint8, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _i64(self, n):
-        import torch
-        t = torch.full((n,), -1, dtype=torch.int64, device=self.r.device)
-        return t, t.data_ptr(), lambda: t.cpu().numpy()
-
-    def _sync(self):
-        import torch
-        torch.cuda.synchronize(self.r.device)
 
 
 def strided(frames, stride):

@@ -3,52 +3,20 @@ tests (test_gpu_objects.py): the pictures, a driver of the C ABI over plain buff
 Every comparison is exact equality of every field, z_min by bits: there is no tolerance anywhere in this feature."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-
 import numpy as np
 
 import jpeg_cases
 import object_table_ref as ref
+from abi_driver import POISON, SENTINEL, AbiDriver, GpuBuffers          # POISON: out_rows and out_counts before every call
 
 NONE = ref.ID_NONE
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
 # restated from sage-3d_official_amd/csrc/sgs_objects.h (SGS_OBJ_REGION, SGS_OBJ_SLOT_BITS, SGS_OBJ_SLOTS, SGS_OBJ_HASH, obj_slot)
 REGION, SLOT_BITS, SLOTS, HASH = 2048, 7, 128, 0x9E3779B1
-POISON = 0xA5A5A5A5                   # out_rows and out_counts before every call (jpeg_cases.SENTINEL bytes)
 
 
 def slot_of(label):
     return ((int(label) * HASH) & 0xFFFFFFFF) >> (32 - SLOT_BITS)
-
-
-def emu_lib_path():
-    """The emulator library (emu_harness rebuilds it when a file of csrc/ is newer than it)."""
-    import emu_harness
-    return emu_harness.build_emu()
-
-
-def start_emu_copy(base, edits, name="libsage_gs_objects_copy.so"):
-    """A copy of csrc/ under `base` with edits = {file of csrc/: [(anchor, replacement)]} made in it (every anchor must occur exactly
-    once), and its emulator build started: (the library's path, the compiler's Popen).  The caller waits."""
-    import shutil
-    import emu_harness
-    base = str(base)
-    csrc = os.path.join(base, "pkg", "csrc")
-    shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), csrc)
-    os.makedirs(os.path.join(base, "include"))
-    shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), os.path.join(base, "include", "sage_gs.h"))     # (../../include/sage_gs.h)
-    for fname, pairs in edits.items():
-        path = os.path.join(csrc, fname)
-        with open(path) as fh:
-            text = fh.read()
-        for old, new in pairs:
-            assert text.count(old) == 1, f"{fname}: anchor found {text.count(old)} times: {old!r}"
-            text = text.replace(old, new)
-        with open(path, "w") as fh:
-            fh.write(text)
-    out = os.path.join(base, name)
-    return out, emu_harness.build_emu(src_dir=csrc, out=out, wait=False)
 
 
 def chunk_edit(chunk):
@@ -251,7 +219,7 @@ def check_mixed_paths_properties():
 
 
 # ---- the C ABI over plain buffers ---------------------------------------------------------------------------------------------------------
-class AbiObjects(jpeg_cases.AbiEncoder):
+class AbiObjects(AbiDriver):
     """sgs_object_table over host buffers; a GPU driver overrides the buffer hooks (GpuObjects)."""
 
     def _ints(self, a):
@@ -278,11 +246,11 @@ class AbiObjects(jpeg_cases.AbiEncoder):
         self.lib.check(self.call(i_ptr, d_ptr, n, H, W, st, n_labels, r_ptr, c_ptr), self.ctx)
         self._sync()
         rb, cb = np.array(r_get()), np.array(c_get())
-        assert (rb[row_bytes:] == jpeg_cases.SENTINEL).all() and (cb[cnt_bytes:] == jpeg_cases.SENTINEL).all(), "bytes were written behind the outputs"
+        assert (rb[row_bytes:] == SENTINEL).all() and (cb[cnt_bytes:] == SENTINEL).all(), "bytes were written behind the outputs"
         return rb[:row_bytes].view(ref.ROW_DTYPE).reshape(n, n_labels), cb[:cnt_bytes].view(np.uint32).reshape(n, 2)
 
 
-class GpuObjects(jpeg_cases.GpuBuffers, AbiObjects):
+class GpuObjects(GpuBuffers, AbiObjects):
     """AbiObjects over torch device buffers, on a Renderer's context."""
 
     def _ints(self, a):
@@ -388,7 +356,7 @@ def check_refusals(drv):
         assert call(**kw) == -1, word
         assert word in drv.lib.sgs_last_error(drv.ctx), (word, drv.lib.sgs_last_error(drv.ctx))
     drv._sync()
-    assert (np.array(r_get()) == jpeg_cases.SENTINEL).all() and (np.array(c_get()) == jpeg_cases.SENTINEL).all(), "a refused call wrote to its outputs"
+    assert (np.array(r_get()) == SENTINEL).all() and (np.array(c_get()) == SENTINEL).all(), "a refused call wrote to its outputs"
     assert call() == 0 and call(n=1, H=46340, W=1, stride=46340 * 4, ids=None) == -1          # the context still works
     drv._sync()
     assert (np.array(r_get())[:2 * 3 * 40].view(ref.ROW_DTYPE)["n_pixels"] == [64, 0, 0, 64, 0, 0]).all()
@@ -414,7 +382,7 @@ def check_misaligned(drv):
         msg = drv.lib.sgs_last_error(drv.ctx)
         assert word in msg and b"aligned" in msg, (word, msg)
     drv._sync()
-    assert (np.array(r_get()) == jpeg_cases.SENTINEL).all() and (np.array(c_get()) == jpeg_cases.SENTINEL).all(), "a refused call wrote to its outputs"
+    assert (np.array(r_get()) == SENTINEL).all() and (np.array(c_get()) == SENTINEL).all(), "a refused call wrote to its outputs"
     assert call() == 0 and call(rows=8, counts=4, ids=4, depth=4) == 0               # aligned, and aligned again: the context still works
     drv._sync()
     assert (np.array(r_get())[8:8 + 2 * 3 * 40].view(ref.ROW_DTYPE)["n_pixels"] == [64, 0, 0, 64, 0, 0]).all()

@@ -11,8 +11,8 @@ import numpy as np
 
 import jpeg_cases
 import png_ref
+from abi_driver import SENTINEL, GpuBuffers  # noqa: F401  (SENTINEL: the tests name it as png_cases.SENTINEL)
 
-SENTINEL = jpeg_cases.SENTINEL
 # Test 5: our file against zlib restricted to the same design (the same filtered bytes, every strip deflated alone at level 1 with run
 # matches only, the same framing).  The worst ratio over the whole picture set, measured on the emulator build (whose bytes are the
 # GPU's), was 1.0519 (depth_1x1: 81 bytes against 77, and colour_1x1: 82 against 78 — a strip of 3 or 4 bytes, which we store and zlib
@@ -99,6 +99,10 @@ class AbiPng(jpeg_cases.AbiEncoder):
 
     def bound(self, w, h, fmt="rgb8", depth_scale=10000.0, depth_max=6.5):
         return int(self.lib.sgs_png_bound(int(w), int(h), C.byref(self._params(fmt, depth_scale, depth_max))))
+
+
+class GpuPng(GpuBuffers, AbiPng):
+    """AbiPng over torch device buffers, on a Renderer's context."""
 
 
 def pil_size(samples, **kw):

@@ -4,7 +4,6 @@ buffers, and the assertions against tests/resize_ref.py."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
@@ -12,6 +11,7 @@ import jpeg_cases
 import png_cases
 import png_ref
 import resize_ref as ref
+from abi_driver import AbiDriver, GpuBuffers
 
 # W, H -> w, h
 SHAPES = [
@@ -31,14 +31,6 @@ SENTINEL = np.float32(-7.0e8)      # what dst holds before a call, padding inclu
 
 def shape_id(s):
     return f"{s[0]}x{s[1]}_to_{s[2]}x{s[3]}"
-
-
-def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_resize.h is newer than it (emu_harness's staleness list predates the header)."""
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_resize.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
 
 
 # ---- pictures ---------------------------------------------------------------------------------------------------------------------------
@@ -111,7 +103,7 @@ def check_picture_properties(shape):
 
 
 # ---- the C ABI over plain buffers ---------------------------------------------------------------------------------------------------------
-class AbiResize(jpeg_cases.AbiEncoder):
+class AbiResize(AbiDriver):
     """sgs_resize (and sgs_pack_rgba8) over host buffers; a GPU driver overrides the buffer hooks (GpuResize)."""
 
     def _floats(self, a):
@@ -162,7 +154,7 @@ class AbiResize(jpeg_cases.AbiEncoder):
         return rgba[..., :3]
 
 
-class GpuResize(jpeg_cases.GpuBuffers, AbiResize):
+class GpuResize(GpuBuffers, AbiResize):
     """AbiResize over torch device buffers, on a Renderer's context."""
 
     def _floats(self, a):

@@ -10,8 +10,8 @@ import numpy as np
 
 import jpeg_cases
 import similarity_ref as ref
+from abi_driver import SENTINEL, AbiDriver, GpuBuffers
 
-SENTINEL = jpeg_cases.SENTINEL
 ROW = ref.ROW_DTYPE.itemsize
 
 
@@ -42,14 +42,6 @@ assert {s[0] for s in SHAPES} == set(WIDTHS) and {s[1] for s in SHAPES} == set(H
 
 def shape_id(shape):
     return f"{shape[0]}x{shape[1]}"
-
-
-def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_similarity.h is newer than it (emu_harness's staleness list predates the header)."""
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_similarity.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
 
 
 # ---- pictures: name -> (frame fp32 [H,W,3], target uint8 [H,W,3]) -----------------------------------------------------------------------
@@ -86,7 +78,7 @@ def pictures_of(shape, seed=0):
 
 
 # ---- the C ABI over plain buffers ---------------------------------------------------------------------------------------------------------
-class AbiSimilarity(jpeg_cases.AbiEncoder):
+class AbiSimilarity(AbiDriver):
     """sgs_image_similarity (and sgs_pack_rgba8) over host buffers; a GPU driver overrides the buffer hooks (GpuSimilarity)."""
 
     def _u8(self, a):
@@ -135,7 +127,7 @@ class AbiSimilarity(jpeg_cases.AbiEncoder):
         return rgba[..., :3]
 
 
-class GpuSimilarity(jpeg_cases.GpuBuffers, AbiSimilarity):
+class GpuSimilarity(GpuBuffers, AbiSimilarity):
     """AbiSimilarity over torch device buffers, on a Renderer's context."""
 
     def _u8(self, a):

@@ -6,9 +6,6 @@ alone, which must PASS (the gap tight_parity.py closes: otherwise the mutant pro
 FAIL with a [tight] assertion — not with a crash, not with another check.  The anchor of every patch must be found exactly once, so that a
 refactor of the kernels cannot make a mutant vanish silently.
 """
-import os
-import shutil
-
 import numpy as np
 import pytest
 
@@ -19,33 +16,36 @@ import parity_cases as pc
 
 R11 = "#define SGS_MUT_R11(x) ((x) * 8193.0f - ((x) * 8193.0f - (x)))   /* x rounded to an 11-bit significand: fp16 precision */\n"
 
-# mutant -> [(anchor in sgs_kernels.h, replacement)]
+INCLUDE = '#include "sgs_common.h"\n'
+DEFINE_R11 = (INCLUDE, INCLUDE + R11)                      # every mutant's first edit: the macro, behind the kernels' first include
+K = "sgs_kernels.h"
+# mutant -> {file of csrc/: [(anchor, replacement)]}
 MUTANTS = {
     # SGS_STAGE: the splat's colour staged at fp16 precision
-    "stage_rgb_fp16": [("s_p3[J] = make_float2(B_.z, B_.w);", "s_p3[J] = make_float2(SGS_MUT_R11(B_.z), SGS_MUT_R11(B_.w));"),
-                       ("s_p4[J] = make_float2(C_.x, C_.y);", "s_p4[J] = make_float2(SGS_MUT_R11(C_.x), C_.y);")],
+    "stage_rgb_fp16": {K: [DEFINE_R11, ("s_p3[J] = make_float2(B_.z, B_.w);", "s_p3[J] = make_float2(SGS_MUT_R11(B_.z), SGS_MUT_R11(B_.w));"),
+                                       ("s_p4[J] = make_float2(C_.x, C_.y);", "s_p4[J] = make_float2(SGS_MUT_R11(C_.x), C_.y);")]},
     # SGS_APPLY: the depth added to the AUX output's expected depth at fp16 precision
-    "aux_depth_fp16": [("if (AUX) Dz = __builtin_fmaf(wgt, (N##4).y, Dz);", "if (AUX) Dz = __builtin_fmaf(wgt, SGS_MUT_R11((N##4).y), Dz);")],
+    "aux_depth_fp16": {K: [DEFINE_R11, ("if (AUX) Dz = __builtin_fmaf(wgt, (N##4).y, Dz);", "if (AUX) Dz = __builtin_fmaf(wgt, SGS_MUT_R11((N##4).y), Dz);")]},
     # SGS_ALPHA_F: every alpha 2^-13 too large
-    "alpha_x(1+2^-13)": [("AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big));",
-                          "AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big)) * (1.0f + 0x1p-13f);")],
+    "alpha_x(1+2^-13)": {K: [DEFINE_R11, ("AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big));",
+                                          "AL = SGS_SAT(SGS_EXP2(-q)) * SGS_SAT(__builtin_fmaf(-q, big, cq_big)) * (1.0f + 0x1p-13f);")]},
     # fine tiles only: the splat's centre 2^-10 px off along x when the frame is rendered through 8x8 / 4x4-pixel tiles
-    "fine_centre_2^-10px": [("sp[0] = make_float4(sx * up, sy * up,", "sp[0] = make_float4((sx + (zf > 0 ? 0x1p-10f : 0.0f)) * up, sy * up,")],
+    "fine_centre_2^-10px": {K: [DEFINE_R11, ("sp[0] = make_float4(sx * up, sy * up,", "sp[0] = make_float4((sx + (zf > 0 ? 0x1p-10f : 0.0f)) * up, sy * up,")]},
     # termination: the stop rule T (1 - alpha) < t_min at 1.05 t_min
-    "t_min_x1.05": [("nt_big = -(P.alpha_max * P.t_min) * SGS_BIG;", "nt_big = -(P.alpha_max * (P.t_min * 1.05f)) * SGS_BIG;")],
+    "t_min_x1.05": {K: [DEFINE_R11, ("nt_big = -(P.alpha_max * P.t_min) * SGS_BIG;", "nt_big = -(P.alpha_max * (P.t_min * 1.05f)) * SGS_BIG;")]},
     # background: the final transmittance rounded to fp16 precision before T * bg
-    "bg_T_fp16": [("o[0] = C0 + Tf * P.bg[0]; o[1] = C1 + Tf * P.bg[1]; o[2] = C2 + Tf * P.bg[2];",
-                   "o[0] = C0 + SGS_MUT_R11(Tf) * P.bg[0]; o[1] = C1 + SGS_MUT_R11(Tf) * P.bg[1]; o[2] = C2 + SGS_MUT_R11(Tf) * P.bg[2];")],
+    "bg_T_fp16": {K: [DEFINE_R11, ("o[0] = C0 + Tf * P.bg[0]; o[1] = C1 + Tf * P.bg[1]; o[2] = C2 + Tf * P.bg[2];",
+                                   "o[0] = C0 + SGS_MUT_R11(Tf) * P.bg[0]; o[1] = C1 + SGS_MUT_R11(Tf) * P.bg[1]; o[2] = C2 + SGS_MUT_R11(Tf) * P.bg[2];")]},
     # the final transmittance of a STOPPED pixel (1 - the sum of its weights) dropped: such a pixel loses T_final bg, between t_min and
     # t_min / (1 - alpha) of the background for the alpha it stopped on — 1.0e-4 to 1.012e-4 in a queue of faint splats (alpha <= 0.012)
-    "tf_stopped_zero": [("const float Tf = Tm > 0.0f ? Tm / amax : fmaxf(1.0f - Wsum, 0.0f);", "const float Tf = Tm > 0.0f ? Tm / amax : 0.0f;")],
+    "tf_stopped_zero": {K: [DEFINE_R11, ("const float Tf = Tm > 0.0f ? Tm / amax : fmaxf(1.0f - Wsum, 0.0f);", "const float Tf = Tm > 0.0f ? Tm / amax : 0.0f;")]},
     # SGS_APPLY: the weights summed into 1 - T_final at fp16 precision.  Caught where pixels stop on a few LARGE weights (the deep-tile
     # scene's opaque layers: a weight of 0.99 rounded to 11 bits is off by up to 2.4e-4, the budget there is A = 1.5e-5).  NOT caught on
     # the big-depth-bucket scene, measured under the emulator: ~1100 weights of <= 0.012 rounded to 11 bits move coverage by 4.9e-5,
     # and the budget at n_px = 1100 is A + B n_px = 8.1e-5 — B grants every record one whole rounding of a sum of 1, a faint record's
     # fp16 rounding (w 2^-12 <= 3e-6 each, signs random) stays below that.  The budget is a bound on fp32 arithmetic, not a detector of
     # every lower precision: in a queue of faint records it cannot tell fp16 weights from fp32 ones.
-    "tf_wsum_fp16": [("if (TF) Wsum += wgt;", "if (TF) Wsum += SGS_MUT_R11(wgt);")],
+    "tf_wsum_fp16": {K: [DEFINE_R11, ("if (TF) Wsum += wgt;", "if (TF) Wsum += SGS_MUT_R11(wgt);")]},
 }
 # No mutant sits in the deep-tile branch of render_tile (`!STATS && deep_ok && ...`) alone: that branch culls a window's records against the
 # live pixels and compacts the survivors' keys — it holds no line that touches Wsum or Dz; the survivors are staged and blended by the code
@@ -98,34 +98,10 @@ CASES = {
 }
 
 
-def _patch(src_dir, edits):
-    path = os.path.join(src_dir, "sgs_kernels.h")
-    s = open(path).read()
-    anchor = '#include "sgs_common.h"\n'
-    assert s.count(anchor) == 1
-    s = s.replace(anchor, anchor + R11)
-    for old, new in edits:
-        assert s.count(old) == 1, f"mutant anchor found {s.count(old)} times (expected once): {old!r}"
-        s = s.replace(old, new)
-    open(path, "w").write(s)
-
-
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("mutants")
-    procs, libs = {}, {}
-    for k, (name, edits) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        _patch(str(base / "pkg" / "csrc"), edits)
-        libs[name] = str(base / "libsage_gs_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("mutants"), MUTANTS, "libsage_gs_mutant.so")
 
 
 def _run(lib_path, case, tight, monkeypatch):

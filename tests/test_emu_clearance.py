@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import emu_harness
 import clearance_cases as cc
 import clearance_ref as ref
 from sage_gs import _capi
@@ -15,7 +16,7 @@ from sage_gs import _capi
 
 @pytest.fixture(scope="module")
 def lib():
-    return _capi.Lib(cc.emu_lib_path())
+    return _capi.Lib(emu_harness.build_emu())
 
 
 @pytest.fixture(scope="module")

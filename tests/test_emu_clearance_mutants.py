@@ -12,6 +12,7 @@ import re
 
 import pytest
 
+import emu_harness
 import clearance_cases as cc
 from sage_gs import _capi
 
@@ -62,11 +63,8 @@ MUTANTS = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("clearance_mutants")
-    started = {name: cc.start_emu_copy(root / f"m{k}", edits, "libsage_gs_clearance_mutant.so") for k, (name, (edits, _, _)) in enumerate(MUTANTS.items())}
-    for name, (_, p) in started.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return {name: path for name, (path, _) in started.items()}
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("clearance_mutants"), {name: edits for name, (edits, _, _) in MUTANTS.items()},
+                                     "libsage_gs_clearance_mutant.so")
 
 
 @pytest.mark.parametrize("name", list(MUTANTS))
@@ -83,7 +81,7 @@ def test_clearance_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = cc.AbiClearance(_capi.Lib(cc.emu_lib_path()))
+    d = cc.AbiClearance(_capi.Lib(emu_harness.build_emu()))
     try:
         cc.check_pictures(d, {**cc.lane_pictures(), **cc.shape_pictures()})
         cc.check_sizes(d, [(63, 3)])

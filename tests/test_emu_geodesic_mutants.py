@@ -11,6 +11,7 @@ import re
 
 import pytest
 
+import emu_harness
 import geodesic_cases as gc
 from sage_gs import _capi
 
@@ -56,11 +57,8 @@ MUTANTS = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("geodesic_mutants")
-    started = {name: gc.start_emu_copy(root / f"m{k}", edits, "libsage_gs_geodesic_mutant.so") for k, (name, (edits, _, _)) in enumerate(MUTANTS.items())}
-    for name, (_, p) in started.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return {name: path for name, (path, _) in started.items()}
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("geodesic_mutants"), {name: edits for name, (edits, _, _) in MUTANTS.items()},
+                                     "libsage_gs_geodesic_mutant.so")
 
 
 @pytest.mark.parametrize("name", list(MUTANTS))
@@ -77,7 +75,7 @@ def test_geodesic_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = gc.AbiGeodesic(_capi.Lib(gc.emu_lib_path()))
+    d = gc.AbiGeodesic(_capi.Lib(emu_harness.build_emu()))
     try:
         gc.check_sizes(d)
         gc.check_pictures(d, gc.pictures(d.T))

@@ -6,7 +6,6 @@ and listed in DESIGN.md §11."""
 import ctypes as C
 import os
 import re
-import shutil
 
 import numpy as np
 import pytest
@@ -142,14 +141,15 @@ def test_refusals(drv):
 
 
 # ---- test 8: seeded faults ------------------------------------------------------------------------------------------------------------
-MUTANTS = {
-    "halves_toward_zero": [("(int)roundf(f / s_q[tq][lane])", "(int)(f / s_q[tq][lane] < 0 ? ceilf(f / s_q[tq][lane] - 0.5f) : floorf(f / s_q[tq][lane] + 0.5f) - (floorf(f / s_q[tq][lane] + 0.5f) - f / s_q[tq][lane] == 0.5f ? 1.0f : 0.0f))")],
-    "luminance_table_off_by_one": [("T.q[0][k] = (float)quant_step(kQLum[n], quality);", "T.q[0][k] = (float)(quant_step(kQLum[n], quality) + (k == 5 ? 1 : 0));")],
-    "dc_predictor_not_reset": [("int pred_y = 0, pred_cb = 0, pred_cr = 0;", "int pred_y = it ? 3 : 0, pred_cb = 0, pred_cr = 0;")],
-    "stuffing_skipped": [("if (ff) dst[at + 1] = 0;", "if (ff) dst[at + 1] = 0x5A;")],
-    "zero_padding": [("min(py, J.height - 1) * J.width + min(px, J.width - 1));", "min(py, J.height - 1) * J.width + min(px, J.width - 1));\n            const bool outside = px >= J.width || py >= J.height;"),
-                     ("const float r = jpeg_level(p[0]), g = jpeg_level(p[1]), bl = jpeg_level(p[2]);", "const float r = outside ? 0.f : jpeg_level(p[0]), g = outside ? 0.f : jpeg_level(p[1]), bl = outside ? 0.f : jpeg_level(p[2]);")],
-    "cb_cr_swapped": [("s = comp == 1 ? w * fmaf(-0.168736f, srg, 0.5f * sbg)", "s = comp == 2 ? w * fmaf(-0.168736f, srg, 0.5f * sbg)")],
+H = "sgs_jpeg.h"
+MUTANTS = {          # name: {file of csrc/: [(anchor, replacement)]}
+    "halves_toward_zero": {H: [("(int)roundf(f / s_q[tq][lane])", "(int)(f / s_q[tq][lane] < 0 ? ceilf(f / s_q[tq][lane] - 0.5f) : floorf(f / s_q[tq][lane] + 0.5f) - (floorf(f / s_q[tq][lane] + 0.5f) - f / s_q[tq][lane] == 0.5f ? 1.0f : 0.0f))")]},
+    "luminance_table_off_by_one": {H: [("T.q[0][k] = (float)quant_step(kQLum[n], quality);", "T.q[0][k] = (float)(quant_step(kQLum[n], quality) + (k == 5 ? 1 : 0));")]},
+    "dc_predictor_not_reset": {H: [("int pred_y = 0, pred_cb = 0, pred_cr = 0;", "int pred_y = it ? 3 : 0, pred_cb = 0, pred_cr = 0;")]},
+    "stuffing_skipped": {H: [("if (ff) dst[at + 1] = 0;", "if (ff) dst[at + 1] = 0x5A;")]},
+    "zero_padding": {H: [("min(py, J.height - 1) * J.width + min(px, J.width - 1));", "min(py, J.height - 1) * J.width + min(px, J.width - 1));\n            const bool outside = px >= J.width || py >= J.height;"),
+                         ("const float r = jpeg_level(p[0]), g = jpeg_level(p[1]), bl = jpeg_level(p[2]);", "const float r = outside ? 0.f : jpeg_level(p[0]), g = outside ? 0.f : jpeg_level(p[1]), bl = outside ? 0.f : jpeg_level(p[2]);")]},
+    "cb_cr_swapped": {H: [("s = comp == 1 ? w * fmaf(-0.168736f, srg, 0.5f * sbg)", "s = comp == 2 ? w * fmaf(-0.168736f, srg, 0.5f * sbg)")]},
 }
 CAUGHT_BY = {
     "halves_toward_zero": r"exact tie",
@@ -161,31 +161,10 @@ CAUGHT_BY = {
 }
 
 
-def _patch(src_dir, edits):
-    path = os.path.join(src_dir, "sgs_jpeg.h")
-    s = open(path).read()
-    for old, new in edits:
-        assert s.count(old) == 1, f"mutant anchor found {s.count(old)} times (expected once): {old!r}"
-        s = s.replace(old, new)
-    open(path, "w").write(s)
-
-
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("jpeg_mutants")
-    procs, libs = {}, {}
-    for k, (name, edits) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        _patch(str(base / "pkg" / "csrc"), edits)
-        libs[name] = str(base / "libsage_gs_jpeg_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("jpeg_mutants"), MUTANTS, "libsage_gs_jpeg_mutant.so")
 
 
 def _checks_1_and_2(d):

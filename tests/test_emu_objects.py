@@ -16,8 +16,8 @@ SPLIT_CHUNK = 4
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """(the emulator library, a build of a copy of csrc/ whose SGS_OBJ_MAX_FRAMES is 4), compiled side by side."""
-    path, proc = oc.start_emu_copy(tmp_path_factory.mktemp("object_split"), {"sgs_objects.h": [oc.chunk_edit(SPLIT_CHUNK)]})
-    main = oc.emu_lib_path()
+    path, proc = emu_harness.start_emu_copy(tmp_path_factory.mktemp("object_split"), {"sgs_objects.h": [oc.chunk_edit(SPLIT_CHUNK)]})
+    main = emu_harness.build_emu()
     assert proc.wait() == 0, "the copy with launches of 4 frames does not compile"
     return main, path
 

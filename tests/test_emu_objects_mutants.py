@@ -12,16 +12,17 @@ import emu_harness
 import object_cases as oc
 from sage_gs import _capi
 
-MUTANTS = {          # name: ([(anchor, replacement)], the pictures that are run)
-    "run_continues_across_a_row_end": ([("(lane == 0 || x == 0 || v != prev)", "(lane == 0 || v != prev)")], oc.SMALL),
-    "run_head_contributes_length_1": ([("const unsigned long long L = len;", "const unsigned long long L = 1;"),
-                                       ("atomicAdd(&s_n[s], len);", "atomicAdd(&s_n[s], 1u);")], oc.SMALL),
-    "x_end_without_plus_1": ([("atomicMax(&s_x1[s], x + len);", "atomicMax(&s_x1[s], x + len - 1u);")], oc.SMALL),
-    "no_slot_path_dropped": ([("else obj_send(&rows[v], len, x, y, x + len, y + 1u, sx, sy);", "")], (oc.own_label,)),
-    "sum_x_accumulated_in_32_bits": ([("atomicAdd(&r->sum_x, sx);", "atomicAdd(reinterpret_cast<unsigned*>(&r->sum_x), (unsigned)sx);")],
+H = "sgs_objects.h"
+MUTANTS = {          # name: ({file of csrc/: [(anchor, replacement)]}, the pictures that are run)
+    "run_continues_across_a_row_end": ({H: [("(lane == 0 || x == 0 || v != prev)", "(lane == 0 || v != prev)")]}, oc.SMALL),
+    "run_head_contributes_length_1": ({H: [("const unsigned long long L = len;", "const unsigned long long L = 1;"),
+                                           ("atomicAdd(&s_n[s], len);", "atomicAdd(&s_n[s], 1u);")]}, oc.SMALL),
+    "x_end_without_plus_1": ({H: [("atomicMax(&s_x1[s], x + len);", "atomicMax(&s_x1[s], x + len - 1u);")]}, oc.SMALL),
+    "no_slot_path_dropped": ({H: [("else obj_send(&rows[v], len, x, y, x + len, y + 1u, sx, sy);", "")]}, (oc.own_label,)),
+    "sum_x_accumulated_in_32_bits": ({H: [("atomicAdd(&r->sum_x, sx);", "atomicAdd(reinterpret_cast<unsigned*>(&r->sum_x), (unsigned)sx);")]},
                                      oc.SMALL + (oc.sum_over_2_32,)),
-    "z_min_admits_negatives": ([("if (lane - d >= seg) z = min(z, o);", "if (lane - d >= seg) z = (unsigned)min((int)z, (int)o);")], oc.SMALL),
-    "clear_kernel_skips_empty_rows": ([("for (long long i = first; i < n_rows; i += step) {", "for (long long i = first; i < 0; i += step) {")], oc.SMALL),
+    "z_min_admits_negatives": ({H: [("if (lane - d >= seg) z = min(z, o);", "if (lane - d >= seg) z = (unsigned)min((int)z, (int)o);")]}, oc.SMALL),
+    "clear_kernel_skips_empty_rows": ({H: [("for (long long i = first; i < n_rows; i += step) {", "for (long long i = first; i < 0; i += step) {")]}, oc.SMALL),
 }
 # The first failing assertion of object_cases.check_pictures on each mutant, with its figures (the tables are deterministic).
 CAUGHT_BY = {
@@ -66,13 +67,9 @@ CHECK_MUTANTS = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("object_mutants")
-    edits = {name: {"sgs_objects.h": e} for name, (e, _) in MUTANTS.items()}
+    edits = {name: e for name, (e, _) in MUTANTS.items()}
     edits.update({name: e for name, (e, _, _) in CHECK_MUTANTS.items()})
-    started = {name: oc.start_emu_copy(root / f"m{k}", e, "libsage_gs_objects_mutant.so") for k, (name, e) in enumerate(edits.items())}
-    for name, (_, p) in started.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return {name: path for name, (path, _) in started.items()}
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("object_mutants"), edits, "libsage_gs_objects_mutant.so")
 
 
 @pytest.mark.parametrize("name", list(MUTANTS))
@@ -112,7 +109,7 @@ def test_object_check_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = oc.AbiObjects(_capi.Lib(oc.emu_lib_path()))
+    d = oc.AbiObjects(_capi.Lib(emu_harness.build_emu()))
     try:
         oc.check_pictures(d, oc.SMALL + oc.PATHS)
         oc.check_misaligned(d)

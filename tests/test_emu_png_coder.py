@@ -5,9 +5,7 @@ package-merge against the unconstrained optimum).  13 pictures built to reach th
 property is asserted from the reference alone, then the file goes through check_file, whose check_strip_coding holds every strip's
 tokens, both codes and the stored / dynamic decision.  14 seeded faults that those checks must catch, each by the assertion named for
 it.  15 padded frame strides, and batches of more than 256 strips.  Figures are printed (pytest -s) and listed in DESIGN.md §12."""
-import os
 import re
-import shutil
 import zlib
 
 import numpy as np
@@ -173,17 +171,19 @@ def test_no_table_has_a_single_code_length_symbol():
 
 
 # ---- 14: seeded faults --------------------------------------------------------------------------------------------------------------------
+H = "sgs_png.h"
 SPLIT = "if (T >= 258u) { t0 = 256u + 258u; n = 1; T -= 258u; }"
-MUTANTS = {          # name: [(anchor, replacement, times the anchor stands in the file)]
-    "clamp_counts_at_limit_minus_1": [("num[A[i] < (unsigned)limit ? A[i] : (unsigned)limit]++", "num[A[i] < (unsigned)limit - 1u ? A[i] : (unsigned)limit]++", 1)],
-    "repair_splits_the_shallowest": [("for (int i = limit - 1; i > 0; --i)\n            if (num[i]) {", "for (int i = 1; i < limit; ++i)\n            if (num[i]) {", 1)],
-    "longest_to_the_most_frequent": [("tab[sym[j++]] = (unsigned)len << 16;", "tab[sym[n - 1 - j++]] = (unsigned)len << 16;", 1)],
-    "carry_dropped": [("pending = T;", "pending = 0;", 1)],
-    "split_at_257": [(SPLIT, SPLIT.replace("258u", "257u"), 2)],
-    "filter_ties_to_the_highest": [(f"if (s{k} < best)", f"if (s{k} <= best)", 1) for k in (1, 2, 3, 4)],
-    "stored_only_when_longer": [("if (len_dyn < len_stored) {", "if (len_dyn <= len_stored) {", 1)],
-    "seven_bit_code_repaired": [("s_cltab, 19, s_num, s_key);", "s_cltab, 19, s_num);", 1)],
-    "hclen_not_trimmed": [("while (hclen > 4 && !(s_cltab[order[hclen - 1]] >> 16)) --hclen;", "", 1)],
+SPLIT_AFTER = ("\n            if (T >= 3u) {", "\n            pending = T;")      # the line stands twice in the file: what follows each
+MUTANTS = {          # name: {file of csrc/: [(anchor, replacement)]}
+    "clamp_counts_at_limit_minus_1": {H: [("num[A[i] < (unsigned)limit ? A[i] : (unsigned)limit]++", "num[A[i] < (unsigned)limit - 1u ? A[i] : (unsigned)limit]++")]},
+    "repair_splits_the_shallowest": {H: [("for (int i = limit - 1; i > 0; --i)\n            if (num[i]) {", "for (int i = 1; i < limit; ++i)\n            if (num[i]) {")]},
+    "longest_to_the_most_frequent": {H: [("tab[sym[j++]] = (unsigned)len << 16;", "tab[sym[n - 1 - j++]] = (unsigned)len << 16;")]},
+    "carry_dropped": {H: [("pending = T;", "pending = 0;")]},
+    "split_at_257": {H: [(SPLIT + after, SPLIT.replace("258u", "257u") + after) for after in SPLIT_AFTER]},
+    "filter_ties_to_the_highest": {H: [(f"if (s{k} < best)", f"if (s{k} <= best)") for k in (1, 2, 3, 4)]},
+    "stored_only_when_longer": {H: [("if (len_dyn < len_stored) {", "if (len_dyn <= len_stored) {")]},
+    "seven_bit_code_repaired": {H: [("s_cltab, 19, s_num, s_key);", "s_cltab, 19, s_num);")]},
+    "hclen_not_trimmed": {H: [("while (hclen > 4 && !(s_cltab[order[hclen - 1]] >> 16)) --hclen;", "")]},
 }
 # `carry = 0;` before the second token pass is not among them: the carry is zero there anyway (the last window's lane 63 has no byte
 # after it, so it never leaves a pending run), and a mutant without the line makes the same bytes.
@@ -205,24 +205,7 @@ CAUGHT_BY = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("png_mutants")
-    procs, libs = {}, {}
-    for k, (name, edits) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        path = base / "pkg" / "csrc" / "sgs_png.h"
-        s = path.read_text()
-        for old, new, times in edits:
-            assert s.count(old) == times, f"mutant anchor found {s.count(old)} times (expected {times}): {old!r}"
-            s = s.replace(old, new)
-        path.write_text(s)
-        libs[name] = str(base / "libsage_gs_png_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("png_mutants"), MUTANTS, "libsage_gs_png_mutant.so")
 
 
 TIE = pc.colour_set()["filter_tie_48x32"]

@@ -7,6 +7,7 @@ the refusals."""
 import numpy as np
 import pytest
 
+import emu_harness
 import png_cases
 import resize_cases as rc
 import resize_ref as ref
@@ -15,7 +16,7 @@ from sage_gs import _capi
 
 @pytest.fixture(scope="module")
 def drv():
-    d = rc.AbiResize(_capi.Lib(rc.emu_lib_path()))
+    d = rc.AbiResize(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 
@@ -37,7 +38,7 @@ def test_batches_and_padded_strides(drv):
 
 def test_a_second_call_with_other_sizes_on_the_same_context():
     """The table cache: sizes seen in turn, and again, on one context of its own; the same axis pair in the other format."""
-    d = rc.AbiResize(_capi.Lib(rc.emu_lib_path()))
+    d = rc.AbiResize(_capi.Lib(emu_harness.build_emu()))
     try:
         for shape in (rc.SHAPES[2], rc.SHAPES[0], rc.SHAPES[2], rc.SHAPES[3], rc.SHAPES[0]):
             W, H, w, h = shape

@@ -1,8 +1,6 @@
 """Seeded faults in the frame resize (csrc/sgs_resize.h, and the pass selection in csrc/sgs_api.hip), under the wave64 emulator: each
 is made in a copy of csrc/, compiled, and must be caught by resize_cases.check_shape — by the assertion named for it."""
-import os
 import re
-import shutil
 
 import pytest
 
@@ -14,14 +12,16 @@ HALF = "int r = 1 << (SGS_RESIZE_BITS - 1), g = r, b = r;"
 MID = "else J.mid[f * J.H * J.w + i] = R | (G << 8) | (B << 16);"
 FLOOR = "else J.mid[f * J.H * J.w + i] = resize_clamp8(r - (1 << (SGS_RESIZE_BITS - 1))) | (resize_clamp8(g - (1 << (SGS_RESIZE_BITS - 1))) << 8) | " \
         "(resize_clamp8(b - (1 << (SGS_RESIZE_BITS - 1))) << 16);"
-MUTANTS = {          # name: (file, [(anchor, replacement, times the anchor stands in the file)])
-    "rounding_term_dropped": ("sgs_resize.h", [(HALF, "int r = 0, g = r, b = r;", 2)]),
-    "window_starts_one_late": ("sgs_resize.h", [("int lo = (int)(c - support + 0.5);", "int lo = (int)(c - support + 0.5) + 1;", 1)]),
-    "weights_not_normalised": ("sgs_resize.h", [("if (ww != 0.0) kk[j] = kk[j] / ww;", "if (ww != 0.0) kk[j] = kk[j];", 1)]),
-    "vertical_pass_fed_unrounded_sums": ("sgs_resize.h", [(MID, FLOOR, 1)]),
-    "levels_by_truncation": ("sgs_resize.h", [("return (int)(unsigned)(c * 255.0f + 0.5f);", "return (int)(unsigned)(c * 255.0f);", 1)]),
-    "skipped_pass_run_with_identity_weights": ("sgs_api.hip", [("const bool do_h = bicubic && J.W != J.w, do_v = bicubic && J.H != J.h;",
-                                                                "const bool do_h = bicubic, do_v = bicubic;", 1)]),
+HALF_AFTER = ("\n        for (int j = 0; j < n; ++j) {", "\n        if (J.v_from_src) {")      # the line stands twice in the file: what follows each
+H, API = "sgs_resize.h", "sgs_api.hip"
+MUTANTS = {          # name: {file of csrc/: [(anchor, replacement)]}
+    "rounding_term_dropped": {H: [(HALF + after, "int r = 0, g = r, b = r;" + after) for after in HALF_AFTER]},
+    "window_starts_one_late": {H: [("int lo = (int)(c - support + 0.5);", "int lo = (int)(c - support + 0.5) + 1;")]},
+    "weights_not_normalised": {H: [("if (ww != 0.0) kk[j] = kk[j] / ww;", "if (ww != 0.0) kk[j] = kk[j];")]},
+    "vertical_pass_fed_unrounded_sums": {H: [(MID, FLOOR)]},
+    "levels_by_truncation": {H: [("return (int)(unsigned)(c * 255.0f + 0.5f);", "return (int)(unsigned)(c * 255.0f);")]},
+    "skipped_pass_run_with_identity_weights": {API: [("const bool do_h = bicubic && J.W != J.w, do_v = bicubic && J.H != J.h;",
+                                                      "const bool do_h = bicubic, do_v = bicubic;")]},
 }
 # The first failing assertion of resize_cases.check_shape on each mutant, with its figures (the bytes are deterministic).  Dropped
 # rounding and floored intermediates read one level low; un-normalised weights of a cut window overflow on the brightest constant; with
@@ -40,24 +40,7 @@ CAUGHT_BY = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("resize_mutants")
-    procs, libs = {}, {}
-    for k, (name, (fname, edits)) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        path = base / "pkg" / "csrc" / fname
-        s = path.read_text()
-        for old, new, times in edits:
-            assert s.count(old) == times, f"mutant anchor found {s.count(old)} times (expected {times}): {old!r}"
-            s = s.replace(old, new)
-        path.write_text(s)
-        libs[name] = str(base / "libsage_gs_resize_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("resize_mutants"), MUTANTS, "libsage_gs_resize_mutant.so")
 
 
 def _checks(d):
@@ -81,7 +64,7 @@ def test_resize_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = rc.AbiResize(_capi.Lib(rc.emu_lib_path()))
+    d = rc.AbiResize(_capi.Lib(emu_harness.build_emu()))
     try:
         _checks(d)
     finally:

@@ -6,6 +6,7 @@ import ctypes as C
 
 import pytest
 
+import emu_harness
 import similarity_cases as sc
 import similarity_ref as ref
 from sage_gs import _capi
@@ -13,7 +14,7 @@ from sage_gs import _capi
 
 @pytest.fixture(scope="module")
 def drv():
-    d = sc.AbiSimilarity(_capi.Lib(sc.emu_lib_path()))
+    d = sc.AbiSimilarity(_capi.Lib(emu_harness.build_emu()))
     yield d
     d.close()
 

@@ -1,9 +1,7 @@
 """Seeded faults in the image similarity (csrc/sgs_similarity.h, and the launch in csrc/sgs_api.hip), under the wave64 emulator: each
 is made in a copy of csrc/, compiled, and must be caught by similarity_cases' checks — by the assertion named for it.  A copy whose
 only change is SGS_SIM_MAX_FRAMES = 4 is compiled beside them: the split of a call into launches, which no seeded fault concerns."""
-import os
 import re
-import shutil
 
 import pytest
 
@@ -13,21 +11,21 @@ from sage_gs import _capi
 
 H, API = "sgs_similarity.h", "sgs_api.hip"
 SPLIT_CHUNK = 4
-MUTANTS = {          # name: (file, anchor, replacement)
-    "tap_changed_on_one_side": (H, "{2, 16, 74, 224, 436, 544, 436, 224, 74, 16, 2}", "{2, 17, 74, 224, 436, 544, 436, 224, 74, 16, 2}"),
-    "window_starts_one_late": (H, "const int px = x0 + lx;", "const int px = x0 + lx + 1;"),
-    "c1_used_for_c2": (H, "const long long c1 = SGS_SIM_C1, c2 = SGS_SIM_C2;", "const long long c1 = SGS_SIM_C1, c2 = SGS_SIM_C1;"),
-    "covariance_term_unsigned": (H, "((double)n1 * (double)n2)", "((double)n1 * (double)(unsigned long long)n2)"),
-    "q_by_truncation": (H, "return (long long)floor(v);", "return (long long)v;"),
-    "second_moment_in_32_bits_vertically": (H, "return acc + (unsigned long long)w * v;", "return acc + (unsigned long long)(w * v);"),
-    "last_tile_column_dropped": (API, "const int tiles_x = (nwx + SGS_SIM_TILE_W - 1) / SGS_SIM_TILE_W;", "const int tiles_x = nwx / SGS_SIM_TILE_W;"),
-    "shared_target_stride_ignored": (H, "const unsigned char* tgt = J.target + f * J.target_stride;",
-                                     "const unsigned char* tgt = J.target + f * (J.target_stride ? J.target_stride : 3ll * J.W * J.H);"),
-    "clear_skipped": (API, "hipLaunchKernelGGL(sgs::k_sim_clear, dim3(clear_blocks), dim3(SGS_SIM_THREADS), 0, st, J);", "(void)clear_blocks;"),
-    "sse_over_windows": (H, "const bool owned = in && (lx < SGS_SIM_TILE_W || last_x) && (ly < SGS_SIM_TILE_H || last_y);",
-                         "const bool owned = in && lx < SGS_SIM_TILE_W && ly < SGS_SIM_TILE_H && px < nwx && py < nwy;"),
-    "split_chunk_4": (H, "#define SGS_SIM_MAX_FRAMES 65535 ", f"#define SGS_SIM_MAX_FRAMES {SPLIT_CHUNK} "),      # (no fault)
+MUTANTS = {          # name: {file of csrc/: [(anchor, replacement)]}
+    "tap_changed_on_one_side": {H: [("{2, 16, 74, 224, 436, 544, 436, 224, 74, 16, 2}", "{2, 17, 74, 224, 436, 544, 436, 224, 74, 16, 2}")]},
+    "window_starts_one_late": {H: [("const int px = x0 + lx;", "const int px = x0 + lx + 1;")]},
+    "c1_used_for_c2": {H: [("const long long c1 = SGS_SIM_C1, c2 = SGS_SIM_C2;", "const long long c1 = SGS_SIM_C1, c2 = SGS_SIM_C1;")]},
+    "covariance_term_unsigned": {H: [("((double)n1 * (double)n2)", "((double)n1 * (double)(unsigned long long)n2)")]},
+    "q_by_truncation": {H: [("return (long long)floor(v);", "return (long long)v;")]},
+    "second_moment_in_32_bits_vertically": {H: [("return acc + (unsigned long long)w * v;", "return acc + (unsigned long long)(w * v);")]},
+    "last_tile_column_dropped": {API: [("const int tiles_x = (nwx + SGS_SIM_TILE_W - 1) / SGS_SIM_TILE_W;", "const int tiles_x = nwx / SGS_SIM_TILE_W;")]},
+    "shared_target_stride_ignored": {H: [("const unsigned char* tgt = J.target + f * J.target_stride;",
+                                         "const unsigned char* tgt = J.target + f * (J.target_stride ? J.target_stride : 3ll * J.W * J.H);")]},
+    "clear_skipped": {API: [("hipLaunchKernelGGL(sgs::k_sim_clear, dim3(clear_blocks), dim3(SGS_SIM_THREADS), 0, st, J);", "(void)clear_blocks;")]},
+    "sse_over_windows": {H: [("const bool owned = in && (lx < SGS_SIM_TILE_W || last_x) && (ly < SGS_SIM_TILE_H || last_y);",
+                             "const bool owned = in && lx < SGS_SIM_TILE_W && ly < SGS_SIM_TILE_H && px < nwx && py < nwy;")]},
 }
+SPLIT = {H: [("#define SGS_SIM_MAX_FRAMES 65535 ", f"#define SGS_SIM_MAX_FRAMES {SPLIT_CHUNK} ")]}      # (no fault)
 # The first failing assertion of the checks below on each mutant (the values are deterministic).
 CAUGHT_BY = {
     "tap_changed_on_one_side": r"11x11 noise_pair: ssim_q is ",            # (identical pictures score 1 under any window)
@@ -45,22 +43,12 @@ CAUGHT_BY = {
 
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
-    """Every mutant's emulator library, compiled side by side (one g++ each)."""
+    """Every mutant's emulator library and the copy with launches of 4 frames, compiled side by side (one g++ each)."""
     root = tmp_path_factory.mktemp("similarity_mutants")
-    procs, libs = {}, {}
-    for k, (name, (fname, old, new)) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        path = base / "pkg" / "csrc" / fname
-        s = path.read_text()
-        assert s.count(old) == 1, f"{name}: anchor found {s.count(old)} times: {old!r}"
-        path.write_text(s.replace(old, new))
-        libs[name] = str(base / "libsage_gs_similarity_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the copy does not compile"
+    split, proc = emu_harness.start_emu_copy(root / "split", SPLIT, "libsage_gs_similarity_split.so")
+    libs = emu_harness.build_mutants(root, MUTANTS, "libsage_gs_similarity_mutant.so")
+    assert proc.wait() == 0, "split_chunk_4: the copy does not compile"
+    libs["split_chunk_4"] = split
     return libs
 
 
@@ -86,7 +74,7 @@ def test_similarity_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = sc.AbiSimilarity(_capi.Lib(sc.emu_lib_path()))
+    d = sc.AbiSimilarity(_capi.Lib(emu_harness.build_emu()))
     try:
         _checks(d)
     finally:

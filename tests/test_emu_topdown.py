@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import emu_harness
 import topdown_cases as tc
 import topdown_ref as ref
 from sage_gs import _capi
@@ -18,8 +19,8 @@ SPLIT_CHUNK = 4
 @pytest.fixture(scope="module")
 def libs(tmp_path_factory):
     """(the emulator library, a build of a copy of csrc/ whose SGS_TOPDOWN_MAX_FRAMES is 4), compiled side by side."""
-    path, proc = tc.start_emu_copy(tmp_path_factory.mktemp("topdown_split"), {"sgs_topdown.h": [tc.chunk_edit(SPLIT_CHUNK)]})
-    main = tc.emu_lib_path()
+    path, proc = emu_harness.start_emu_copy(tmp_path_factory.mktemp("topdown_split"), {"sgs_topdown.h": [tc.chunk_edit(SPLIT_CHUNK)]})
+    main = emu_harness.build_emu()
     assert proc.wait() == 0, "the copy with launches of 4 frames does not compile"
     return main, path
 

@@ -13,6 +13,7 @@ import re
 
 import pytest
 
+import emu_harness
 import topdown_cases as tc
 from sage_gs import _capi
 
@@ -54,11 +55,8 @@ MUTANTS = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("topdown_mutants")
-    started = {name: tc.start_emu_copy(root / f"m{k}", edits, "libsage_gs_topdown_mutant.so") for k, (name, (edits, _, _)) in enumerate(MUTANTS.items())}
-    for name, (_, p) in started.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return {name: path for name, (path, _) in started.items()}
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("topdown_mutants"), {name: edits for name, (edits, _, _) in MUTANTS.items()},
+                                     "libsage_gs_topdown_mutant.so")
 
 
 @pytest.mark.parametrize("name", list(MUTANTS))
@@ -75,7 +73,7 @@ def test_topdown_mutant_is_caught(mutant_libs, name):
 
 
 def test_the_unmutated_library_passes_the_mutants_checks():
-    d = tc.AbiTopdown(_capi.Lib(tc.emu_lib_path()))
+    d = tc.AbiTopdown(_capi.Lib(emu_harness.build_emu()))
     try:
         tc.check_pictures(d, (tc.sizes, tc.wall, tc.own_cell, tc.mixed_paths, tc.depth_specials, tc.borders))
         tc.check_misaligned(d)

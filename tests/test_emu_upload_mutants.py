@@ -7,7 +7,6 @@ test_compressed_upload_decodes_on_the_device_and_sorts_in_z_order and parity_cas
 printed, asserted and written down in DESIGN.md §9: a frame does not depend on the layout, so they see almost none."""
 import os
 import re
-import shutil
 
 import pytest
 
@@ -16,24 +15,24 @@ import parity_cases as pc
 import upload_cases as uc
 
 K, API = "sgs_kernels.h", "sgs_api.hip"
-MUTANTS = {          # name: (file, anchor, replacement[, file, anchor, replacement])
-    "spread_mask_off": (K, "v = (v | v << 4) & 0x10c30c30c30c30c3ull;", "v = (v | v << 4) & 0x10c30c30c30c30c1ull;"),
-    "y_shift_dropped": (K, "| sgs_spread21(q[1]) << 1 |", "| sgs_spread21(q[1]) |"),
-    "seven_passes": (API, "for (int shift = 0; shift < 64; shift += 8, cur ^= 1) {", "for (int shift = 0; shift < 56; shift += 8, cur ^= 1) {"),
-    "rank_reversed_within_a_run": (K, "if (valid) { keys_out[dst + rank] = k; idx_out[dst + rank] = v; }",
-                                   "if (valid) { const unsigned rr = (unsigned)__popcll(peers) - 1u - rank; keys_out[dst + rr] = k; idx_out[dst + rr] = v; }"),
+MUTANTS = {          # name: {file of csrc/: [(anchor, replacement)]}
+    "spread_mask_off": {K: [("v = (v | v << 4) & 0x10c30c30c30c30c3ull;", "v = (v | v << 4) & 0x10c30c30c30c30c1ull;")]},
+    "y_shift_dropped": {K: [("| sgs_spread21(q[1]) << 1 |", "| sgs_spread21(q[1]) |")]},
+    "seven_passes": {API: [("for (int shift = 0; shift < 64; shift += 8, cur ^= 1) {", "for (int shift = 0; shift < 56; shift += 8, cur ^= 1) {")]},
+    "rank_reversed_within_a_run": {K: [("if (valid) { keys_out[dst + rank] = k; idx_out[dst + rank] = v; }",
+                                        "if (valid) { const unsigned rr = (unsigned)__popcll(peers) - 1u - rank; keys_out[dst + rr] = k; idx_out[dst + rr] = v; }")]},
     # (keys then collide and leave holes in the sort's output; the second patch is no fault: it zeroes the sort's buffers, so that a hole
     #  reads as Gaussian 0 and not as whatever the heap held — the fault must fail an assertion, not read the scene out of bounds)
-    "bsum_not_added": (K, "for (unsigned g = 0; g < at / SGS_RSCAN_SPAN; ++g) run += bsum[g];", "(void)bsum;",
-                       API, "keys[k] = own_keys[k].p; idx[k] = own_idx[k].p;",
-                       "keys[k] = own_keys[k].p; idx[k] = own_idx[k].p; hipMemset(keys[k], 0, (size_t)n * 8); hipMemset(idx[k], 0, (size_t)n * 4);"),
-    "wave_base_from_the_wrong_quarter": (K, "for (int w = 0; w < 4; ++w) { const unsigned c = s_cur[w][tid]; s_cur[w][tid] = run; run += c; }",
-                                         "for (int w = 3; w >= 0; --w) { const unsigned c = s_cur[w][tid]; s_cur[w][tid] = run; run += c; }"),
-    "finite_test_removed_from_the_bounds": (K, "if (fabsf(m[c]) < 3.0e38f) { const unsigned k = sgs_ordered(m[c]);", "if (true) { const unsigned k = sgs_ordered(m[c]);"),
-    "padding_lanes_in_the_chunk_bounds": (K, "const bool real = pos < n;  ", "const bool real = pos < n || true;  "),
-    "radius_padding_0_999": (K, "r = r * 1.0001f + 1.0e-6f", "r = r * 0.999f + 1.0e-6f"),
-    "s_max_by_fminf": (K, "sm = fmaxf(sm, __shfl_xor(sm, d));", "sm = fminf(sm, __shfl_xor(sm, d));"),
-    "radius_always_inf": (K, "if (__ballot(bad) != 0ull || !(r < 3.0e37f)", "if (true || __ballot(bad) != 0ull || !(r < 3.0e37f)"),
+    "bsum_not_added": {K: [("for (unsigned g = 0; g < at / SGS_RSCAN_SPAN; ++g) run += bsum[g];", "(void)bsum;")],
+                       API: [("keys[k] = own_keys[k].p; idx[k] = own_idx[k].p;",
+                              "keys[k] = own_keys[k].p; idx[k] = own_idx[k].p; hipMemset(keys[k], 0, (size_t)n * 8); hipMemset(idx[k], 0, (size_t)n * 4);")]},
+    "wave_base_from_the_wrong_quarter": {K: [("for (int w = 0; w < 4; ++w) { const unsigned c = s_cur[w][tid]; s_cur[w][tid] = run; run += c; }",
+                                              "for (int w = 3; w >= 0; --w) { const unsigned c = s_cur[w][tid]; s_cur[w][tid] = run; run += c; }")]},
+    "finite_test_removed_from_the_bounds": {K: [("if (fabsf(m[c]) < 3.0e38f) { const unsigned k = sgs_ordered(m[c]);", "if (true) { const unsigned k = sgs_ordered(m[c]);")]},
+    "padding_lanes_in_the_chunk_bounds": {K: [("const bool real = pos < n;  ", "const bool real = pos < n || true;  ")]},
+    "radius_padding_0_999": {K: [("r = r * 1.0001f + 1.0e-6f", "r = r * 0.999f + 1.0e-6f")]},
+    "s_max_by_fminf": {K: [("sm = fmaxf(sm, __shfl_xor(sm, d));", "sm = fminf(sm, __shfl_xor(sm, d));")]},
+    "radius_always_inf": {K: [("if (__ballot(bad) != 0ull || !(r < 3.0e37f)", "if (true || __ballot(bad) != 0ull || !(r < 3.0e37f)")]},
 }
 # The cases the mutants go through, in this order (the unmutated library passes them all), and the first assertion that fails on each.
 CHECKS = ("size_65", "size_513", "size_2049", "every_mean_equal", "two_points_interleaved") + tuple(f"one_digit_{j}" for j in range(8)) + \
@@ -70,23 +69,7 @@ OLD_TESTS_CATCH = {
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("upload_mutants")
-    procs, libs = {}, {}
-    for k, (name, patches) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        for fname, old, new in zip(patches[0::3], patches[1::3], patches[2::3]):
-            path = base / "pkg" / "csrc" / fname
-            s = path.read_text()
-            assert s.count(old) == 1, f"{name}: anchor found {s.count(old)} times: {old!r}"
-            path.write_text(s.replace(old, new))
-        libs[name] = str(base / "libsage_gs_upload_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the copy does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("upload_mutants"), MUTANTS, "libsage_gs_upload_mutant.so")
 
 
 def _checks(d):

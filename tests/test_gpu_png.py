@@ -14,10 +14,6 @@ import png_ref
 pytestmark = pytest.mark.gpu
 
 
-class GpuPng(jpeg_cases.GpuBuffers, pc.AbiPng):
-    """png_cases.AbiPng over torch device buffers, on a Renderer's context."""
-
-
 @pytest.fixture(scope="module")
 def r():
     from sage_gs import Renderer
@@ -36,7 +32,7 @@ def _packed(r, img):
 
 def test_synthetic_set_on_the_gpu(r):
     """Checks 1-5 on the emulator tests' own pictures through the GPU build; the colour reference starts from pack_rgba8."""
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     for name, img in pc.colour_set().items():
         h, w = img.shape[:2]
         fig = pc.check_file(d.encode_one(img, "rgb8"), _packed(r, img), d.bound(w, h, "rgb8"), name)
@@ -53,7 +49,7 @@ def test_issue_independence_on_the_gpu(r):
     """Test 6: a batch of 5 different frames yields the bytes each yields alone; two calls yield the same bytes; a permuted batch
     yields permuted files; so does a batch of 64 through Renderer.encode_png."""
     import torch
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     frames = np.stack([jpeg_cases.gradient_noise(187, 250, seed=s) * (0.5 + 0.1 * s) for s in range(5)])
     for fmt, fr in (("rgb8", frames), ("depth16", np.ascontiguousarray(frames[..., 0] * 7.0))):
         batch = d.encode(fr, fmt)
@@ -68,7 +64,7 @@ def test_issue_independence_on_the_gpu(r):
 
 
 def test_capacity_on_the_gpu(r):
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     frames = np.stack([jpeg_cases.gradient_noise(40, 56, seed=s) for s in range(3)])
     full = d.encode(frames, "rgb8")
     assert full["rc"] == 0
@@ -86,7 +82,7 @@ def test_gpu_bytes_equal_the_emulators(r):
     not).  From the samples on the encoder is integer-only, so the files must be equal byte for byte."""
     from sage_gs import _capi
     emu = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     try:
         for name, img in pc.depth_set().items():
             assert d.encode_one(img, "depth16") == emu.encode_one(img, "depth16"), f"{name}: the GPU's file is not the emulator's"
@@ -100,7 +96,7 @@ def test_gpu_bytes_equal_the_emulators(r):
 def test_rendered_colour(r):
     """Test 9, colour: make_room and make_trained_like at 320x240 through checks 1-5; Renderer.encode_png gives the ABI's bytes."""
     from sage_gs import scenes
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     for name, make in (("make_room", scenes.make_room), ("make_trained_like", scenes.make_trained_like)):
         sc = make(30_000, seed=6)
         scene = r.upload(scenes.to_gaussians(sc, "cuda:0"))
@@ -119,7 +115,7 @@ def test_rendered_mesh_depth(r):
     far plane at the median depth of its own view so that it sees +inf pixels, through Renderer.render_mesh_depth ->
     encode_png(format="depth16") and checks 1-5."""
     from sage_gs import RenderConfig, scenes
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     room = scenes.make_room_mesh(50_000, seed=1)
     mesh = r.upload_mesh(room.vertices, room.triangles)
     for (w, h) in ((320, 240), (640, 480)):
@@ -174,7 +170,7 @@ def test_coder_pictures_on_the_gpu(r):
     bytes.  The colour input is on the levels, so the reference's samples are the build's."""
     from sage_gs import _capi
     emu = pc.AbiPng(_capi.Lib(emu_harness.build_emu()))
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     try:
         for name, case in pc.coder_set().items():
             want = pc.check_coder_case(name, case)          # before the library's output is looked at
@@ -194,7 +190,7 @@ def test_coder_pictures_on_the_gpu(r):
 def test_padded_stride_and_long_scan_on_the_gpu(r):
     """test_emu_png_coder.py's test 15 through the GPU build, and its files against the emulator's (input on the levels)."""
     from sage_gs import _capi
-    d = GpuPng(r)
+    d = pc.GpuPng(r)
     frames = png_ref.rgb_samples(pc.long_scan_frames()).astype(np.float32) / np.float32(255.0)
     batch = jpeg_cases.check_stride_and_long_scan(d.encode, frames, 256, 2, fmt="rgb8")
     for i in (0, 1, 63, 64, 127, 128):

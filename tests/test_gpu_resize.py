@@ -4,16 +4,13 @@ values against the emulator's, and the layers above the C ABI — Renderer.resiz
 import numpy as np
 import pytest
 
+import emu_harness
 import png_cases
 import resize_cases as rc
 import resize_ref as ref
 
 pytestmark = pytest.mark.gpu
 POSE = None
-
-
-class GpuPng(rc.jpeg_cases.GpuBuffers, png_cases.AbiPng):
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -37,7 +34,7 @@ def test_shape_pairs_on_the_gpu(drv, shape):
 
 def test_resized_frames_pack_and_encode_on_the_gpu(r, drv):
     for shape in (rc.SHAPES[0], rc.SHAPES[2], rc.SHAPES[6]):
-        rc.check_downstream(drv, GpuPng(r), shape, levels_of=drv.pack)
+        rc.check_downstream(drv, png_cases.GpuPng(r), shape, levels_of=drv.pack)
 
 
 def test_batches_strides_and_refusals_on_the_gpu(drv):
@@ -48,7 +45,7 @@ def test_batches_strides_and_refusals_on_the_gpu(drv):
 def test_gpu_values_equal_the_emulators(drv):
     """Input on the levels (k / 255: where fusing x * 255 + 0.5 changes nothing) and depth: bit for bit the emulator's frames."""
     from sage_gs import _capi
-    emu = rc.AbiResize(_capi.Lib(rc.emu_lib_path()))
+    emu = rc.AbiResize(_capi.Lib(emu_harness.build_emu()))
     try:
         for shape in rc.SHAPES[:6]:
             W, H, w, h = shape

@@ -4,6 +4,7 @@ on a caller's stream, and the layers above the C ABI — Renderer.image_similari
 import numpy as np
 import pytest
 
+import emu_harness
 import similarity_cases as sc
 import similarity_ref as ref
 
@@ -38,7 +39,7 @@ def test_gpu_rows_equal_the_emulators(drv):
     """Frames on the levels (k / 255: where fusing x * 255 + 0.5 changes nothing): bit for bit the emulator's rows, per picture and
     for the batch of nine with padded strides."""
     from sage_gs import _capi
-    emu = sc.AbiSimilarity(_capi.Lib(sc.emu_lib_path()))
+    emu = sc.AbiSimilarity(_capi.Lib(emu_harness.build_emu()))
     try:
         for shape in sc.SHAPES:
             for name, (frame, target) in sc.pictures_of(shape).items():

@@ -4,9 +4,7 @@ As test_checker_sensitivity.py does for the splat path: each mutant is csrc/ wit
 emulator library of its own (never for gfx950), and the mesh case that targets it must fail with an AssertionError — not a crash, not a
 refusal.  The anchor of every patch must be found exactly once, so that a refactor of the kernels cannot make a mutant vanish silently.
 """
-import os
 import re
-import shutil
 
 import pytest
 
@@ -27,28 +25,29 @@ EDGE_PLANE = ("const MeshD3 e = swap ? mesh_cross_rn(p[b], p[a]) : mesh_cross_rn
               "                        const double s = swap ? -sg : sg;")
 EDGE_PLANE64 = "const MeshD3 e = mesh_cross_rn(u, v);"             # mesh_inside64's plane (its sign comes from the record)
 
-# mutant -> [(anchor in sgs_mesh.h, replacement)]
+H = "sgs_mesh.h"
+# mutant -> {file of csrc/: [(anchor, replacement)]}
 MUTANTS = {
     # an edge on the line through a pixel centre belongs to neither triangle (the fp32 test and its fp64 recheck)
-    "exclusive_edges": [("bool in = s0 >= 0.f && s1 >= 0.f && s2 >= 0.f;", "bool in = s0 > 0.f && s1 > 0.f && s2 > 0.f;"),
-                        ("if (s[k] >= 0.f) continue;", "if (s[k] > 0.f) continue;"),
-                        ("if (!(g >= -0x1p-50 * fma(Px, ax, fma(Py, ay, Pz)))) return false;", "if (!(g > 0.0)) return false;")],
+    "exclusive_edges": {H: [("bool in = s0 >= 0.f && s1 >= 0.f && s2 >= 0.f;", "bool in = s0 > 0.f && s1 > 0.f && s2 > 0.f;"),
+                            ("if (s[k] >= 0.f) continue;", "if (s[k] > 0.f) continue;"),
+                            ("if (!(g >= -0x1p-50 * fma(Px, ax, fma(Py, ay, Pz)))) return false;", "if (!(g > 0.0)) return false;")]},
     # each triangle builds its edge planes in its own vertex order with a fused fp64 cross product (the record and the recheck)
-    "fused_cross_triangle_order": [(CROSS_ANCHOR, FMA_CROSS + CROSS_ANCHOR),
-                                   (EDGE_PLANE, "const MeshD3 e = mesh_cross_fma(p[a], p[b]);\n                        const double s = sg;"),
-                                   (EDGE_PLANE64, "const MeshD3 e = mesh_cross_fma(p[a], p[b]);")],
+    "fused_cross_triangle_order": {H: [(CROSS_ANCHOR, FMA_CROSS + CROSS_ANCHOR),
+                                       (EDGE_PLANE, "const MeshD3 e = mesh_cross_fma(p[a], p[b]);\n                        const double s = sg;"),
+                                       (EDGE_PLANE64, "const MeshD3 e = mesh_cross_fma(p[a], p[b]);")]},
     # the same in fp32 (a setup moved to single precision): the two sides of a shared edge differ by an ulp
-    "fp32_cross_triangle_order": [(CROSS_ANCHOR, FMA_CROSS + CROSS_ANCHOR),
-                                  (EDGE_PLANE, "const MeshD3 e = mesh_cross_f32(p[a], p[b]);\n                        const double s = sg;"),
-                                  (EDGE_PLANE64, "const MeshD3 e = mesh_cross_f32(p[a], p[b]);")],
+    "fp32_cross_triangle_order": {H: [(CROSS_ANCHOR, FMA_CROSS + CROSS_ANCHOR),
+                                      (EDGE_PLANE, "const MeshD3 e = mesh_cross_f32(p[a], p[b]);\n                        const double s = sg;"),
+                                      (EDGE_PLANE64, "const MeshD3 e = mesh_cross_f32(p[a], p[b]);")]},
     # the fp64 recheck of edges within rounding of 0 is gone: a vertex's fan can leave its pixel unclaimed
-    "no_fp64_recheck": [("if (!in && fmaf(e0.w, rmax,", "if (false && fmaf(e0.w, rmax,")],
-    "far_exclusive": [("if (z > near_z && z <= far_z) best", "if (z > near_z && z < far_z) best")],
-    "near_inclusive": [("if (z > near_z && z <= far_z) best", "if (z >= near_z && z <= far_z) best")],
+    "no_fp64_recheck": {H: [("if (!in && fmaf(e0.w, rmax,", "if (false && fmaf(e0.w, rmax,")]},
+    "far_exclusive": {H: [("if (z > near_z && z <= far_z) best", "if (z > near_z && z < far_z) best")]},
+    "near_inclusive": {H: [("if (z > near_z && z <= far_z) best", "if (z >= near_z && z <= far_z) best")]},
     # k_mesh_scan: the running sum of the blocks before is not carried into the next block of 1024 tiles
-    "scan_carry_lost": [("const unsigned carry = s_carry;", "const unsigned carry = 0u * s_carry;")],
+    "scan_carry_lost": {H: [("const unsigned carry = s_carry;", "const unsigned carry = 0u * s_carry;")]},
     # k_mesh_depth: only the first LDS chunk (256 records) of a tile's list is read
-    "first_chunk_only": [("for (unsigned long long b = begin; b < end; b += 256) {", "for (unsigned long long b = begin; b < end; b = end) {")],
+    "first_chunk_only": {H: [("for (unsigned long long b = begin; b < end; b += 256) {", "for (unsigned long long b = begin; b < end; b = end) {")]},
 }
 
 
@@ -95,31 +94,10 @@ CAUGHT_BY = {
 XFAIL = {"fused_cross_triangle_order": "the fused fp64 cross product rounds to the same fp32 edge plane as the unfused one: no crack"}
 
 
-def _patch(src_dir, edits):
-    path = os.path.join(src_dir, "sgs_mesh.h")
-    s = open(path).read()
-    for old, new in edits:
-        assert s.count(old) == 1, f"mutant anchor found {s.count(old)} times (expected once): {old!r}"
-        s = s.replace(old, new)
-    open(path, "w").write(s)
-
-
 @pytest.fixture(scope="module")
 def mutant_libs(tmp_path_factory):
     """Every mutant's emulator library, compiled side by side (one g++ each)."""
-    root = tmp_path_factory.mktemp("mesh_mutants")
-    procs, libs = {}, {}
-    for k, (name, edits) in enumerate(MUTANTS.items()):
-        base = root / f"m{k}"
-        shutil.copytree(os.path.join(emu_harness.PKG, "csrc"), base / "pkg" / "csrc")
-        os.makedirs(base / "include")
-        shutil.copy(os.path.join(emu_harness.ROOT, "include", "sage_gs.h"), base / "include" / "sage_gs.h")     # (../../include/sage_gs.h)
-        _patch(str(base / "pkg" / "csrc"), edits)
-        libs[name] = str(base / "libsage_gs_mesh_mutant.so")
-        procs[name] = emu_harness.build_emu(src_dir=base / "pkg" / "csrc", out=libs[name], wait=False)
-    for name, p in procs.items():
-        assert p.wait() == 0, f"{name}: the mutant does not compile"
-    return libs
+    return emu_harness.build_mutants(tmp_path_factory.mktemp("mesh_mutants"), MUTANTS, "libsage_gs_mesh_mutant.so")
 
 
 @pytest.mark.parametrize("name", [pytest.param(n, marks=pytest.mark.xfail(strict=True, reason=XFAIL[n]))

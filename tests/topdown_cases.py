@@ -11,10 +11,9 @@ import numpy as np
 
 import jpeg_cases
 import topdown_ref as ref
+from abi_driver import POISON, SENTINEL, AbiDriver, GpuBuffers      # POISON: grid, out_counts and out before every call
 
 F = np.float32
-SENTINEL = jpeg_cases.SENTINEL
-POISON = 0xA5A5A5A5                       # grid, out_counts and out before every call (SENTINEL bytes)
 INF = float("inf")
 
 
@@ -34,20 +33,6 @@ REGION, SLOT_BITS, SLOTS, HASH, MAX_FRAMES, SUM_BLOCKS, THREADS = _constants()
 
 def slot_of(key):
     return ((int(key) * HASH) & 0xFFFFFFFF) >> (32 - SLOT_BITS)
-
-
-def emu_lib_path():
-    """The emulator library, rebuilt when csrc/sgs_topdown.h is newer than it (emu_harness's staleness list predates the header)."""
-    import emu_harness
-    hdr = os.path.join(emu_harness.PKG, "csrc", "sgs_topdown.h")
-    stale = os.path.exists(emu_harness.EMU_LIB) and os.path.getmtime(hdr) > os.path.getmtime(emu_harness.EMU_LIB)
-    return emu_harness.build_emu(force=stale)
-
-
-def start_emu_copy(base, edits, name="libsage_gs_topdown_copy.so"):
-    """object_cases.start_emu_copy: a copy of csrc/ under `base` with edits made in it, and its emulator build started."""
-    import object_cases
-    return object_cases.start_emu_copy(base, edits, name)
 
 
 def chunk_edit(chunk):
@@ -311,12 +296,8 @@ def c_params(p: ref.Params):
                                   p.flags, p.reserved)
 
 
-class AbiTopdown(jpeg_cases.AbiEncoder):
+class AbiTopdown(AbiDriver):
     """sgs_topdown_map and sgs_topdown_summary over host buffers; a GPU driver overrides the buffer hooks (GpuTopdown)."""
-
-    def _fill(self, keep, words):
-        """Writes uint32 `words` at the start of the buffer `keep` that _bytes made."""
-        keep[:4 * len(words)] = np.ascontiguousarray(words, np.uint32).view(np.uint8)
 
     def call(self, depth_ptr, W, H, n, stride, P_ptr, params, grid_ptr, counts_ptr, stream=None):
         cp = None if params is None else C.byref(params if not isinstance(params, ref.Params) else c_params(params))
@@ -337,7 +318,7 @@ class AbiTopdown(jpeg_cases.AbiEncoder):
         g_bytes, c_bytes = 8 * p.nx * p.ny, 16 * n
         keep_g, g_ptr, g_get = self._bytes(g_bytes + slack)
         if before is not None:
-            self._fill(keep_g, np.asarray(before, np.uint32).reshape(-1))
+            self._fill(keep_g, np.ascontiguousarray(before, np.uint32).reshape(-1).view(np.uint8))
         keep_c, c_ptr, c_get = self._bytes(c_bytes + slack)
         self.lib.check(self.call(d_ptr, W, H, n, st, p_ptr, p, g_ptr, c_ptr, stream), self.ctx)
         self._sync()
@@ -349,8 +330,7 @@ class AbiTopdown(jpeg_cases.AbiEncoder):
     def summary(self, grid, min_hits=1, slack=64):
         g = np.ascontiguousarray(grid, np.uint32)
         ny, nx = g.shape[:2]
-        keep_g, g_ptr, _ = self._bytes(g.nbytes)
-        self._fill(keep_g, g.reshape(-1))
+        keep_g, g_ptr, _ = self._put(g)
         keep_o, o_ptr, o_get = self._bytes(32 + slack)
         self.lib.check(self.call_summary(g_ptr, nx, ny, min_hits, o_ptr), self.ctx)
         self._sync()
@@ -359,13 +339,8 @@ class AbiTopdown(jpeg_cases.AbiEncoder):
         return [int(v) for v in ob[:32].view(np.uint64)]
 
 
-class GpuTopdown(jpeg_cases.GpuBuffers, AbiTopdown):
+class GpuTopdown(GpuBuffers, AbiTopdown):
     """AbiTopdown over torch device buffers, on a Renderer's context."""
-
-    def _fill(self, keep, words):
-        import torch
-        w = np.ascontiguousarray(words, np.uint32).view(np.uint8)
-        keep[:len(w)] = torch.from_numpy(w.copy()).to(keep.device)
 
 
 def check_against(name, grid, counts, depth, P, p, before=None):
