@@ -235,7 +235,55 @@ struct sgs_ctx {
                      hipGetErrorString(e_));                                                   \
     } while (0)
 
+#define SGS_TRY(check) do { if (const int rc_ = (check)) return rc_; } while (0)
+
 namespace {
+
+// The argument checks of the operator entry points (sgs_resize .. sgs_geodesic_path): each is SGS_OK, or the context's message and
+// SGS_ERR_INVALID.  An entry point lists them in the order it refuses in; what these cannot say is a plain SGS_FAIL beside them.
+// non_null and aligned take any number of (pointer, name) pairs and judge them in the order given.  The object table, the top-down
+// map and the clearance map spell their alignment tests out: tests/test_emu_*_mutants.py take those lines out by their text.
+struct Args {
+    sgs_ctx* ctx;
+    const char* who;
+    int non_null() const { return SGS_OK; }
+    template <class... More>
+    int non_null(const void* p, const char* name, More... more) const {
+        if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null %s", who, name);
+        return non_null(more...);
+    }
+    int aligned(int) const { return SGS_OK; }
+    template <class... More>
+    int aligned(int bytes, const void* p, const char* name, More... more) const {          // (a null pointer is aligned: whether it may be null is non_null's to say)
+        if (reinterpret_cast<uintptr_t>(p) % bytes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s %p is not %d-byte aligned", who, name, p, bytes);
+        return aligned(bytes, more...);
+    }
+    // Frames (maps) a stride apart, of `need` elements each, do not overlap.  `text` is the entry point's own wording of the refusal
+    // after "<who>: ", with two %lld: the stride and `need`.
+    int frames_fit(int64_t stride, int64_t need, const char* text) const {
+        if (stride < need) SGS_FAIL(ctx, SGS_ERR_INVALID, (std::string("%s: ") + text).c_str(), who, (long long)stride, (long long)need);
+        return SGS_OK;
+    }
+    // The byte ranges [a, a + a_bytes) and [b, b + b_bytes) share a byte.
+    static bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+        const uint64_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+        return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    }
+    int disjoint(const void* a, uint64_t a_bytes, const char* a_name, const void* b, uint64_t b_bytes, const char* b_name) const {
+        if (overlap(a, a_bytes, b, b_bytes)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s %p and %s %p overlap", who, a_name, a, b_name, b);
+        return SGS_OK;
+    }
+    int grid_within(int nx, int ny, int max) const {
+        if (nx < 1 || ny < 1 || nx > max || ny > max) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, nx, ny, max);
+        return SGS_OK;
+    }
+};
+
+// f(first, count) for each run of at most `max` of n frames (maps, words): what one launch takes in gridDim.y or in its arguments.
+template <class F>
+void for_chunks(int n, int max, F f) {
+    for (int first = 0; first < n; first += max) f(first, std::min(max, n - first));
+}
 
 // A counter array that the kernels keep zeroed from then on needs ONE clear, at its allocation.  hipMemset of device memory runs on the
 // NULL stream and may return before it has run; the frames use non-blocking streams that do not order with it — an unfinished clear would
@@ -2031,7 +2079,7 @@ void sgs_resize_params_default(sgs_resize_params* p) {
 int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_frames, int64_t src_frame_stride,
                const sgs_resize_params* p, float* dst, int64_t dst_frame_stride, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_resize";
+    const char* who = "sgs_resize"; const Args a = {ctx, who};
     if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: params is NULL", who);
     if (p->format != SGS_RESIZE_RGB8 && p->format != SGS_RESIZE_F32)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: format %d is neither SGS_RESIZE_RGB8 nor SGS_RESIZE_F32", who, p->format);
@@ -2044,21 +2092,17 @@ int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_fram
         SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: destination %d x %d is outside 1..65535", who, p->dst_width, p->dst_height);
     if (std::isnan(p->clip_lo) || std::isnan(p->clip_hi)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: clip bound is NaN", who);
     if (p->clip_lo > p->clip_hi) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: clip_lo %g is above clip_hi %g", who, (double)p->clip_lo, (double)p->clip_hi);
-    if (n_frames == 0) return SGS_OK;
-    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
-    if (!dst) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dst", who);
+    if (n_frames == 0) return SGS_OK;          // nothing to do, whatever the pointers are: only the parameters are judged
+    SGS_TRY(a.non_null(src, "src", dst, "dst"));
     const int ch = p->format == SGS_RESIZE_RGB8 ? 3 : 1;
     const int64_t src_floats = (int64_t)width * height * ch, dst_floats = (int64_t)p->dst_width * p->dst_height * ch;
-    if (n_frames > 1 && src_frame_stride < src_floats)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src frames overlap (stride %lld floats, a frame has %lld)", who, (long long)src_frame_stride, (long long)src_floats);
-    if (n_frames > 1 && dst_frame_stride < dst_floats)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dst frames overlap (stride %lld floats, a frame has %lld)", who, (long long)dst_frame_stride, (long long)dst_floats);
-    {
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(src), d0 = reinterpret_cast<uintptr_t>(dst);
-        const uintptr_t s1 = s0 + (uintptr_t)(((int64_t)(n_frames - 1) * src_frame_stride + src_floats) * 4);
-        const uintptr_t d1 = d0 + (uintptr_t)(((int64_t)(n_frames - 1) * dst_frame_stride + dst_floats) * 4);
-        if (s0 < d1 && d0 < s1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src and dst overlap", who);
+    if (n_frames > 1) {                        // one frame has no stride to judge (sgs_object_table and sgs_topdown_map judge it all the same)
+        SGS_TRY(a.frames_fit(src_frame_stride, src_floats, "src frames overlap (stride %lld floats, a frame has %lld)"));
+        SGS_TRY(a.frames_fit(dst_frame_stride, dst_floats, "dst frames overlap (stride %lld floats, a frame has %lld)"));
     }
+    if (Args::overlap(src, (uint64_t)(((int64_t)(n_frames - 1) * src_frame_stride + src_floats) * 4),
+                      dst, (uint64_t)(((int64_t)(n_frames - 1) * dst_frame_stride + dst_floats) * 4)))
+        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src and dst overlap", who);       // (without the pointers, unlike disjoint's)
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     sgs::ResizeJob J;
     memset(&J, 0, sizeof J);
@@ -2074,12 +2118,11 @@ int sgs_resize(sgs_ctx* ctx, const float* src, int width, int height, int n_fram
     if (do_h && do_v) SGS_HIP(ctx, ctx->resize.mid.grow((int64_t)std::min(n_frames, kMaxFrames) * J.H * J.w, Grow::geometric));
     J.mid = ctx->resize.mid.p;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    for (int f0 = 0; f0 < n_frames; f0 += kMaxFrames) {
+    for_chunks(n_frames, kMaxFrames, [&](int f0, int n) {
         J.src = src + (int64_t)f0 * src_frame_stride; J.dst = dst + (int64_t)f0 * dst_frame_stride;
-        const int n = std::min(kMaxFrames, n_frames - f0);
         if (p->format == SGS_RESIZE_RGB8) resize_launch<sgs::RESIZE_RGB8>(J, p->filter, do_h, do_v, n, st);
         else resize_launch<sgs::RESIZE_F32>(J, p->filter, do_h, do_v, n, st);
-    }
+    });
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }
@@ -2094,16 +2137,13 @@ extern "C" {
 int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n_frames, int height, int width, int64_t frame_stride,
                      int32_t n_labels, sgs_object_row* out_rows, uint32_t* out_counts, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_object_table";
-    if (!ids) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null ids", who);
-    if (!out_rows) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_rows", who);
-    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    const char* who = "sgs_object_table"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(ids, "ids", out_rows, "out_rows", out_counts, "out_counts"));          // depth may be null (no depth channel); if given it is aligned, below
     if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
     if (height < 1 || width < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d", who, width, height);
     const int64_t pixels = (int64_t)height * width;
     if (pixels > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d has more than 2^31 - 1 pixels", who, width, height);
-    if (frame_stride < pixels)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (stride %lld elements, a frame has %lld)", who, (long long)frame_stride, (long long)pixels);
+    SGS_TRY(a.frames_fit(frame_stride, pixels, "frames overlap (stride %lld elements, a frame has %lld)"));      // for one frame too
     if (n_labels < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_labels = %d", who, (int)n_labels);
     // the kernels' atomics are 64-bit on sum_x / sum_y and 32-bit elsewhere; a misaligned one must never reach the device
     if (reinterpret_cast<uintptr_t>(out_rows) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_rows %p is not 8-byte aligned", who, (const void*)out_rows);
@@ -2119,13 +2159,12 @@ int sgs_object_table(sgs_ctx* ctx, const int32_t* ids, const float* depth, int n
     const int64_t clear_blocks = std::min<int64_t>((std::max<int64_t>(n_rows, 2ll * n_frames) + SGS_OBJ_THREADS - 1) / SGS_OBJ_THREADS, 65536);
     hipLaunchKernelGGL(sgs::k_obj_clear, dim3((unsigned)clear_blocks), dim3(SGS_OBJ_THREADS), 0, st, J);
     const unsigned regions = (unsigned)((pixels + SGS_OBJ_REGION - 1) / SGS_OBJ_REGION);
-    for (int f0 = 0; f0 < n_frames; f0 += SGS_OBJ_MAX_FRAMES) {
+    for_chunks(n_frames, SGS_OBJ_MAX_FRAMES, [&](int f0, int n) {
         sgs::ObjJob K = J;
         K.ids = ids + (int64_t)f0 * frame_stride; K.depth = depth ? depth + (int64_t)f0 * frame_stride : nullptr;
-        K.rows = J.rows + (int64_t)f0 * n_labels; K.counts = out_counts + 2ll * f0;
-        K.n_frames = std::min(SGS_OBJ_MAX_FRAMES, n_frames - f0);
-        hipLaunchKernelGGL(sgs::k_obj_reduce, dim3(regions, (unsigned)K.n_frames), dim3(SGS_OBJ_THREADS), 0, st, K);
-    }
+        K.rows = J.rows + (int64_t)f0 * n_labels; K.counts = out_counts + 2ll * f0; K.n_frames = n;
+        hipLaunchKernelGGL(sgs::k_obj_reduce, dim3(regions, (unsigned)n), dim3(SGS_OBJ_THREADS), 0, st, K);
+    });
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }
@@ -2140,22 +2179,18 @@ extern "C" {
 int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, int n_frames, int64_t rgb_frame_stride,
                          const uint8_t* target, int64_t target_frame_stride, sgs_similarity_row* out_rows, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_image_similarity";
-    if (!rgb) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null rgb", who);
-    if (!target) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null target", who);
-    if (!out_rows) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_rows", who);
+    const char* who = "sgs_image_similarity"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(rgb, "rgb", target, "target", out_rows, "out_rows"));
     if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
     if (width < SGS_SIM_WINDOW || width > 65535) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: width %d is outside %d..65535 (a window is %d pixels wide)", who, width, SGS_SIM_WINDOW, SGS_SIM_WINDOW);
     if (height < SGS_SIM_WINDOW || height > 65535) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: height %d is outside %d..65535 (a window is %d pixels high)", who, height, SGS_SIM_WINDOW, SGS_SIM_WINDOW);
     const int64_t frame = 3ll * width * height;
-    if (rgb_frame_stride < frame)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rgb_frame_stride %lld floats is smaller than a frame (%lld)", who, (long long)rgb_frame_stride, (long long)frame);
+    SGS_TRY(a.frames_fit(rgb_frame_stride, frame, "rgb_frame_stride %lld floats is smaller than a frame (%lld)"));       // for one frame too
     if (target_frame_stride != 0 && target_frame_stride < frame)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: target_frame_stride %lld bytes is neither 0 nor a frame (%lld) or more", who, (long long)target_frame_stride, (long long)frame);
     // the rows are updated with 64-bit atomics; a misaligned one must never reach the device
-    const uintptr_t rows_at = reinterpret_cast<uintptr_t>(out_rows), rgb_at = reinterpret_cast<uintptr_t>(rgb);
-    if (rows_at % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_rows %p is not 8-byte aligned", who, (const void*)out_rows);
-    if (rgb_at % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rgb %p is not 4-byte aligned", who, (const void*)rgb);
+    SGS_TRY(a.aligned(8, out_rows, "out_rows"));
+    SGS_TRY(a.aligned(4, rgb, "rgb"));
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     sgs::SimJob J;
@@ -2167,12 +2202,11 @@ int sgs_image_similarity(sgs_ctx* ctx, const float* rgb, int width, int height, 
     J.tiles_x = tiles_x;
     const unsigned clear_blocks = (unsigned)std::min<int64_t>(((int64_t)n_frames + SGS_SIM_THREADS - 1) / SGS_SIM_THREADS, 65536);
     hipLaunchKernelGGL(sgs::k_sim_clear, dim3(clear_blocks), dim3(SGS_SIM_THREADS), 0, st, J);
-    for (int f0 = 0; f0 < n_frames; f0 += SGS_SIM_MAX_FRAMES) {
+    for_chunks(n_frames, SGS_SIM_MAX_FRAMES, [&](int f0, int n) {
         sgs::SimJob K = J;
-        K.rgb = rgb + (int64_t)f0 * rgb_frame_stride; K.target = target + (int64_t)f0 * target_frame_stride; K.rows = J.rows + f0;
-        K.n_frames = std::min(SGS_SIM_MAX_FRAMES, n_frames - f0);
-        hipLaunchKernelGGL(sgs::k_sim_reduce, dim3((unsigned)(tiles_x * tiles_y), (unsigned)K.n_frames), dim3(SGS_SIM_THREADS), 0, st, K);
-    }
+        K.rgb = rgb + (int64_t)f0 * rgb_frame_stride; K.target = target + (int64_t)f0 * target_frame_stride; K.rows = J.rows + f0; K.n_frames = n;
+        hipLaunchKernelGGL(sgs::k_sim_reduce, dim3((unsigned)(tiles_x * tiles_y), (unsigned)n), dim3(SGS_SIM_THREADS), 0, st, K);
+    });
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }
@@ -2194,18 +2228,13 @@ void sgs_topdown_params_default(sgs_topdown_params* p) {
 int sgs_topdown_map(sgs_ctx* ctx, const float* depth, int width, int height, int n_frames, int64_t frame_stride,
                     const float* pix_to_map, const sgs_topdown_params* p, uint32_t* grid, uint32_t* out_counts, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_topdown_map";
-    if (!depth) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null depth", who);
-    if (!pix_to_map) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null pix_to_map", who);
-    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
-    if (!grid) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null grid", who);
-    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    const char* who = "sgs_topdown_map"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(depth, "depth", pix_to_map, "pix_to_map", p, "params", grid, "grid", out_counts, "out_counts"));
     if (n_frames < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames = %d", who, n_frames);
     if (height < 1 || width < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d", who, width, height);
     const int64_t pixels = (int64_t)height * width;
     if (pixels > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frame %d x %d has more than 2^31 - 1 pixels", who, width, height);
-    if (frame_stride < pixels)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: frames overlap (frame_stride %lld elements, a frame has %lld)", who, (long long)frame_stride, (long long)pixels);
+    SGS_TRY(a.frames_fit(frame_stride, pixels, "frames overlap (frame_stride %lld elements, a frame has %lld)"));        // for one frame too
     if ((int64_t)n_frames * pixels > 0xFFFFFFFFll)
         SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_frames * height * width = %lld could pass 2^32 - 1 hits in one cell", who, (long long)((int64_t)n_frames * pixels));
     if (p->nx < 1 || p->ny < 1 || 2ll * p->nx * p->ny > 0x7FFFFFFFll)
@@ -2236,22 +2265,19 @@ int sgs_topdown_map(sgs_ctx* ctx, const float* depth, int width, int height, int
     const int64_t clear_blocks = std::min<int64_t>((clear_words + SGS_TOPDOWN_THREADS - 1) / SGS_TOPDOWN_THREADS, 65536);
     hipLaunchKernelGGL(sgs::k_topdown_clear, dim3((unsigned)clear_blocks), dim3(SGS_TOPDOWN_THREADS), 0, st, J);
     const unsigned regions = (unsigned)((pixels + SGS_TOPDOWN_REGION - 1) / SGS_TOPDOWN_REGION);
-    for (int f0 = 0; f0 < n_frames; f0 += SGS_TOPDOWN_MAX_FRAMES) {
+    for_chunks(n_frames, SGS_TOPDOWN_MAX_FRAMES, [&](int f0, int n) {
         sgs::TopdownJob K = J;
-        K.depth = depth + (int64_t)f0 * frame_stride; K.P = pix_to_map + 12ll * f0;
-        K.counts = out_counts + 4ll * f0;
-        K.n_frames = std::min(SGS_TOPDOWN_MAX_FRAMES, n_frames - f0);
-        hipLaunchKernelGGL(sgs::k_topdown_map, dim3(regions, (unsigned)K.n_frames), dim3(SGS_TOPDOWN_THREADS), 0, st, K);
-    }
+        K.depth = depth + (int64_t)f0 * frame_stride; K.P = pix_to_map + 12ll * f0; K.counts = out_counts + 4ll * f0; K.n_frames = n;
+        hipLaunchKernelGGL(sgs::k_topdown_map, dim3(regions, (unsigned)n), dim3(SGS_TOPDOWN_THREADS), 0, st, K);
+    });
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }
 
 int sgs_topdown_summary(sgs_ctx* ctx, const uint32_t* grid, int nx, int ny, uint32_t min_hits, uint64_t* out, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_topdown_summary";
-    if (!grid) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null grid", who);
-    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out", who);
+    const char* who = "sgs_topdown_summary"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(grid, "grid", out, "out"));
     if (nx < 1 || ny < 1 || 2ll * nx * ny > 0x7FFFFFFFll) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny and 2 nx ny <= 2^31 - 1)", who, nx, ny);
     if (min_hits < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min_hits = 0", who);
     if (reinterpret_cast<uintptr_t>(grid) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: grid %p is not 4-byte aligned", who, (const void*)grid);
@@ -2282,27 +2308,20 @@ extern "C" {
 int sgs_clearance_map(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_clearance_params* p,
                       uint32_t* work, uint32_t* d2, uint32_t* out_counts, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_clearance_map";
-    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
-    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
-    if (!work) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null work", who);
-    if (!d2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null d2", who);
-    if (!out_counts) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_counts", who);
+    const char* who = "sgs_clearance_map"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(src, "src", p, "params", work, "work", d2, "d2", out_counts, "out_counts"));
     if (n_maps < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_maps = %d", who, n_maps);
-    if (p->nx < 1 || p->ny < 1 || p->nx > SGS_CLEAR_MAX_NX || p->ny > SGS_CLEAR_MAX_NX)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, (int)p->nx, (int)p->ny, SGS_CLEAR_MAX_NX);
+    SGS_TRY(a.grid_within(p->nx, p->ny, SGS_CLEAR_MAX_NX));
     if (p->source != SGS_CLEARANCE_SRC_MASK8 && p->source != SGS_CLEARANCE_SRC_TOPDOWN) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
     const bool topdown = p->source == SGS_CLEARANCE_SRC_TOPDOWN;
     const int64_t cells = (int64_t)p->nx * p->ny, map_elements = topdown ? 2 * cells : cells;
-    if (map_stride < map_elements)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: maps overlap (map_stride %lld elements, a map has %lld)", who, (long long)map_stride, (long long)map_elements);
+    SGS_TRY(a.frames_fit(map_stride, map_elements, "maps overlap (map_stride %lld elements, a map has %lld)"));          // for one map too
     if ((p->flags & ~SGS_CLEARANCE_UNSEEN_BLOCKS) || (p->flags && !topdown)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x for source %d", who, (unsigned)p->flags, (int)p->source);
     if (topdown && p->min_hits < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min_hits = 0", who);
     if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
-    const uintptr_t a_d2 = reinterpret_cast<uintptr_t>(d2), a_work = reinterpret_cast<uintptr_t>(work);
     const uint64_t out_bytes = 4ull * (uint64_t)n_maps * (uint64_t)cells;
-    if (a_d2 < a_work + out_bytes && a_work < a_d2 + out_bytes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: d2 %p and work %p overlap", who, (void*)d2, (void*)work);
-    // the kernels' loads, stores and atomics are 32-bit; a misaligned one must never reach the device
+    SGS_TRY(a.disjoint(d2, out_bytes, "d2", work, out_bytes, "work"));
+    // the kernels' loads, stores and atomics are 32-bit; a misaligned one must never reach the device (src: a seen map only, a mask is bytes)
     const struct { const void* at; const char* name; bool words; } buffers[] = {{src, "src", topdown}, {work, "work", true}, {d2, "d2", true}, {out_counts, "out_counts", true}};
     for (const auto& b : buffers)
         if (b.words && reinterpret_cast<uintptr_t>(b.at) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: %s %p is not 4-byte aligned", who, b.name, b.at);
@@ -2316,13 +2335,12 @@ int sgs_clearance_map(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
     const unsigned clear_blocks = (unsigned)std::min<int64_t>((count_words + SGS_CLEAR_THREADS - 1) / SGS_CLEAR_THREADS, 1024);
     hipLaunchKernelGGL(sgs::k_clear_counts, dim3(clear_blocks), dim3(SGS_CLEAR_THREADS), 0, st, out_counts, (long long)count_words);
     const unsigned row_groups = (unsigned)((p->ny + SGS_CLEAR_ROWS - 1) / SGS_CLEAR_ROWS), words = (unsigned)((p->nx + 63) / 64);
-    for (int m0 = 0; m0 < n_maps; m0 += SGS_CLEAR_MAX_MAPS) {
+    for_chunks(n_maps, SGS_CLEAR_MAX_MAPS, [&](int m0, int n) {
         sgs::ClearanceJob K = J;
-        K.map0 = m0;
-        K.n_maps = std::min(SGS_CLEAR_MAX_MAPS, n_maps - m0);
-        hipLaunchKernelGGL(sgs::k_clear_rows, dim3(row_groups, (unsigned)K.n_maps), dim3(SGS_CLEAR_THREADS), 0, st, K);
-        hipLaunchKernelGGL(sgs::k_clear_cols, dim3(words, row_groups, (unsigned)K.n_maps), dim3(SGS_CLEAR_THREADS), 0, st, K);
-    }
+        K.map0 = m0; K.n_maps = n;
+        hipLaunchKernelGGL(sgs::k_clear_rows, dim3(row_groups, (unsigned)n), dim3(SGS_CLEAR_THREADS), 0, st, K);
+        hipLaunchKernelGGL(sgs::k_clear_cols, dim3(words, row_groups, (unsigned)n), dim3(SGS_CLEAR_THREADS), 0, st, K);
+    });
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }
@@ -2330,13 +2348,10 @@ int sgs_clearance_map(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
 int sgs_clearance_query(sgs_ctx* ctx, const uint32_t* d2, int nx, int ny, const double* segs, int n,
                         const sgs_clearance_frame* f, uint32_t* out, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_clearance_query";
-    if (!d2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null d2", who);
-    if (!segs) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null segs", who);
-    if (!f) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null frame", who);
-    if (!out) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out", who);
+    const char* who = "sgs_clearance_query"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(d2, "d2", segs, "segs", f, "frame", out, "out"));
     if (n < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n = %d", who, n);
-    if (nx < 1 || ny < 1 || nx > SGS_CLEAR_MAX_NX || ny > SGS_CLEAR_MAX_NX) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, nx, ny, SGS_CLEAR_MAX_NX);
+    SGS_TRY(a.grid_within(nx, ny, SGS_CLEAR_MAX_NX));
     if (!std::isfinite(f->scale) || f->scale <= 0.0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: scale = %g (finite and > 0)", who, f->scale);
     if (!std::isfinite(f->min_x) || !std::isfinite(f->min_y)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: min (%g, %g) is not finite", who, f->min_x, f->min_y);
     if (!std::isfinite(f->sum_x) || !std::isfinite(f->sum_y)) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: sum (%g, %g) is not finite", who, f->sum_x, f->sum_y);
@@ -2365,24 +2380,20 @@ static_assert(SGS_GEODESIC_NONE == SGS_GEO_NONE && SGS_GEODESIC_SRC_MASK8 == SGS
               "the kernels' constants are the header's");
 
 // What sgs_geodesic_field and sgs_geodesic_path refuse alike: the map, the params and the field table (a HOST array).
-static int geodesic_check(sgs_ctx* ctx, const char* who, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* p,
+static int geodesic_check(const Args& a, const void* src, int n_maps, int64_t map_stride, const sgs_geodesic_params* p,
                           const int32_t* field_map, int n_fields, int max_fields) {
-    if (!src) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null src", who);
-    if (!p) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null params", who);
-    if (!field_map) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null field_map", who);
+    sgs_ctx* ctx = a.ctx; const char* who = a.who;
+    SGS_TRY(a.non_null(src, "src", p, "params", field_map, "field_map"));
     if (n_maps < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_maps = %d", who, n_maps);
     if (n_fields < 1 || n_fields > max_fields) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_fields = %d (1 <= n_fields <= %d)", who, n_fields, max_fields);
-    if (p->nx < 1 || p->ny < 1 || p->nx > SGS_GEO_MAX_N || p->ny > SGS_GEO_MAX_N)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: nx = %d, ny = %d (1 <= nx, ny <= %d)", who, (int)p->nx, (int)p->ny, SGS_GEO_MAX_N);
+    SGS_TRY(a.grid_within(p->nx, p->ny, SGS_GEO_MAX_N));
     if (p->source != SGS_GEODESIC_SRC_MASK8 && p->source != SGS_GEODESIC_SRC_D2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
     if (p->flags & ~SGS_GEODESIC_CONTINUE) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
     if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
-    if (map_stride < (int64_t)p->nx * p->ny)
-        SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: maps overlap (map_stride %lld elements, a map has %lld)", who, (long long)map_stride, (long long)p->nx * p->ny);
-    for (int f = 0; f < n_fields; ++f)
+    SGS_TRY(a.frames_fit(map_stride, (int64_t)p->nx * p->ny, "maps overlap (map_stride %lld elements, a map has %lld)"));
+    for (int f = 0; f < n_fields; ++f)         // field_map is a HOST array, read here: nothing has been enqueued yet
         if (field_map[f] < 0 || field_map[f] >= n_maps) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: field_map[%d] = %d (n_maps = %d)", who, f, (int)field_map[f], n_maps);
-    if (p->source == SGS_GEODESIC_SRC_D2 && reinterpret_cast<uintptr_t>(src) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: src %p is not 4-byte aligned", who, src);
-    return SGS_OK;
+    return p->source == SGS_GEODESIC_SRC_D2 ? a.aligned(4, src, "src") : SGS_OK;              // a mask is read byte by byte
 }
 
 extern "C" {
@@ -2399,27 +2410,21 @@ int sgs_geodesic_field(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_st
                        const int32_t* field_map, int n_fields, const int32_t* seeds, int n_seeds,
                        uint32_t* dist, uint32_t* state, int rounds, uint32_t* status, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_geodesic_field";
-    if (const int rc = geodesic_check(ctx, who, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_MAX_FIELDS)) return rc;
-    if (!seeds) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null seeds", who);
-    if (!dist) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dist", who);
-    if (!state) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null state", who);
-    if (!status) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null status", who);
+    const char* who = "sgs_geodesic_field"; const Args a = {ctx, who};
+    SGS_TRY(geodesic_check(a, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_MAX_FIELDS));
+    SGS_TRY(a.non_null(seeds, "seeds", dist, "dist", state, "state", status, "status"));
     if (n_seeds < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_seeds = %d", who, n_seeds);
     if (rounds < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: rounds = %d", who, rounds);
-    for (int s = 0; s < n_seeds; ++s) {
+    for (int s = 0; s < n_seeds; ++s) {        // seeds is a HOST array, as field_map is
         const int32_t* e = seeds + 3 * (size_t)s;
         if (e[0] < 0 || e[0] >= n_fields) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: seeds[%d] names field %d (n_fields = %d)", who, s, (int)e[0], n_fields);
         if (e[1] < 0 || e[1] >= p->nx || e[2] < 0 || e[2] >= p->ny)
             SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: seeds[%d] = (%d, %d) is outside the grid %d x %d", who, s, (int)e[1], (int)e[2], (int)p->nx, (int)p->ny);
     }
-    if (reinterpret_cast<uintptr_t>(dist) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p is not 8-byte aligned", who, (void*)dist);
-    if (reinterpret_cast<uintptr_t>(state) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: state %p is not 4-byte aligned", who, (void*)state);
-    if (reinterpret_cast<uintptr_t>(status) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: status %p is not 4-byte aligned", who, (void*)status);
+    SGS_TRY(a.aligned(8, dist, "dist"));
+    SGS_TRY(a.aligned(4, state, "state", status, "status"));
     const int64_t cells = (int64_t)p->nx * p->ny, state_words = sgs_geodesic_state_words(p->nx, p->ny, n_fields);
-    const uintptr_t a_dist = reinterpret_cast<uintptr_t>(dist), a_state = reinterpret_cast<uintptr_t>(state);
-    const uint64_t dist_bytes = 8ull * (uint64_t)n_fields * (uint64_t)cells, state_bytes = 4ull * (uint64_t)state_words;
-    if (a_dist < a_state + state_bytes && a_state < a_dist + dist_bytes) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p and state %p overlap", who, (void*)dist, (void*)state);
+    SGS_TRY(a.disjoint(dist, 8ull * (uint64_t)n_fields * (uint64_t)cells, "dist", state, 4ull * (uint64_t)state_words, "state"));
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     sgs::GeodesicJob J;
@@ -2431,19 +2436,17 @@ int sgs_geodesic_field(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_st
         const int64_t pairs = (int64_t)n_fields * cells, zero_words = state_words - n_fields;
         const unsigned blocks = (unsigned)std::min<int64_t>((std::max(pairs, zero_words) + SGS_GEO_THREADS - 1) / SGS_GEO_THREADS, 4096);
         hipLaunchKernelGGL(sgs::k_geo_fill, dim3(blocks), dim3(SGS_GEO_THREADS), 0, st, J.dist, (long long)pairs, state + n_fields, (long long)zero_words);
-        for (int f0 = 0; f0 < n_fields; f0 += SGS_GEO_PUT_WORDS) {                   // the field table travels in kernel arguments: no host buffer outlives the call
+        for_chunks(n_fields, SGS_GEO_PUT_WORDS, [&](int f0, int n) {                 // the field table travels in kernel arguments: no host buffer outlives the call
             sgs::GeodesicWords W;
-            const int n = std::min(SGS_GEO_PUT_WORDS, n_fields - f0);
             for (int k = 0; k < SGS_GEO_PUT_WORDS; ++k) W.w[k] = k < n ? (unsigned)field_map[f0 + k] : 0u;
             hipLaunchKernelGGL(sgs::k_geo_put, dim3(1), dim3(SGS_GEO_PUT_WORDS), 0, st, state + f0, W, n);
-        }
-        for (int s0 = 0; s0 < n_seeds; s0 += SGS_GEO_SEEDS_PER_LAUNCH) {
+        });
+        for_chunks(n_seeds, SGS_GEO_SEEDS_PER_LAUNCH, [&](int s0, int n) {
             sgs::GeodesicSeeds S;
-            const int n = std::min(SGS_GEO_SEEDS_PER_LAUNCH, n_seeds - s0);
             for (int k = 0; k < SGS_GEO_SEEDS_PER_LAUNCH; ++k)
                 for (int c = 0; c < 3; ++c) S.s[k][c] = k < n ? seeds[3 * (size_t)(s0 + k) + c] : 0;
             hipLaunchKernelGGL(sgs::k_geo_seed, dim3(1), dim3(SGS_GEO_SEEDS_PER_LAUNCH), 0, st, J, S, n);
-        }
+        });
     }
     for (int r = 0; r < rounds; ++r)
         for (int colour = 0; colour < 4; ++colour) {
@@ -2462,19 +2465,14 @@ int sgs_geodesic_path(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
                       const int32_t* field_map, int n_fields, const uint32_t* dist, const int32_t* queries, int n_queries,
                       int max_len, int32_t* out_cells, uint32_t* out_info, void* hip_stream) {
     if (!ctx) return SGS_ERR_INVALID;
-    const char* who = "sgs_geodesic_path";
-    if (const int rc = geodesic_check(ctx, who, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_PATH_MAX_FIELDS)) return rc;
+    const char* who = "sgs_geodesic_path"; const Args a = {ctx, who};
+    SGS_TRY(geodesic_check(a, src, n_maps, map_stride, p, field_map, n_fields, SGS_GEO_PATH_MAX_FIELDS));
     if (p->flags) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
-    if (!dist) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null dist", who);
-    if (!queries) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null queries", who);
-    if (!out_cells) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_cells", who);
-    if (!out_info) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: null out_info", who);
+    SGS_TRY(a.non_null(dist, "dist", queries, "queries", out_cells, "out_cells", out_info, "out_info"));
     if (n_queries < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_queries = %d", who, n_queries);
     if (max_len < 1) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: max_len = %d", who, max_len);
-    if (reinterpret_cast<uintptr_t>(dist) % 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: dist %p is not 8-byte aligned", who, (const void*)dist);
-    if (reinterpret_cast<uintptr_t>(queries) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: queries %p is not 4-byte aligned", who, (const void*)queries);
-    if (reinterpret_cast<uintptr_t>(out_cells) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_cells %p is not 4-byte aligned", who, (void*)out_cells);
-    if (reinterpret_cast<uintptr_t>(out_info) % 4) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: out_info %p is not 4-byte aligned", who, (void*)out_info);
+    SGS_TRY(a.aligned(8, dist, "dist"));
+    SGS_TRY(a.aligned(4, queries, "queries", out_cells, "out_cells", out_info, "out_info"));
     SGS_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     sgs::GeodesicPathJob Q;

@@ -213,6 +213,78 @@ def _as_f32(t: torch.Tensor, device, shape_tail):
     return t
 
 
+# -- the frame operators' argument checks (DESIGN.md §3 "What the operators check"): the device is an argument, so they run where
+# there is no GPU.  Each raises ValueError before any library call; a refusal they cannot say is a plain ValueError in the method.
+def _dtype_name(dtype) -> str:
+    return str(dtype).split(".")[-1]
+
+
+def _frames_arg(t, device, dtype, tail, what, min_frames=0):
+    """(frames [B, *frame], single) of `t`: a `dtype` tensor on `device` holding one frame [*frame] (single) or a batch [B, *frame].
+    `tail` is a frame's shape, None where a size is free.  B >= min_frames, and where a frame is asked for it holds an element.  Each
+    frame is contiguous; the batch stride is free (see _frame_stride)."""
+    ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == device and t.dim() in (len(tail), len(tail) + 1)
+    single = ok and t.dim() == len(tail)
+    if single:
+        t = t.unsqueeze(0)
+    if (not ok or any(want is not None and have != want for have, want in zip(t.shape[1:], tail)) or t.shape[0] < min_frames
+            or (min_frames > 0 and t.numel() == 0) or (t.shape[0] > 0 and not t[0].is_contiguous())):
+        dims = ",".join("HW"[k] if want is None else str(want) for k, want in enumerate(tail))
+        raise ValueError(f"{what} must be {_dtype_name(dtype)} [{dims}] or [B,{dims}] on the renderer's device with contiguous frames"
+                         + (f", at least {min_frames} of them and none empty" if min_frames else ""))
+    return t, single
+
+
+def _frame_stride(frames, frame_elements: int) -> int:
+    """The batch stride the library is given, in elements: stride(0) of a batch, and for ONE frame the frame's element count whatever
+    its stride(0) says — a one-frame view cut from a strided batch (big[::2][:1]) carries the batch's stride or any other, and
+    sgs_object_table / sgs_topdown_map test the stride even for one frame."""
+    return int(frames.stride(0)) if frames.shape[0] > 1 else int(frame_elements)
+
+
+def _out_arg(out, device, shape, dtype, name, zero=False):
+    """`out`, checked: a contiguous `dtype` tensor of `shape` on `device`; None allocates it (zeroed if asked)."""
+    if out is None:
+        return (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=device)
+    if out.device != device or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {_dtype_name(dtype)} {list(shape)} tensor on the renderer's device")
+    return out
+
+
+def _maps_arg(src, device, dtype, per_cell, what):
+    """(maps, batched, b, ny, nx, stride) of grids [ny,nx] or [B,ny,nx] — with per_cell = 2, [ny,nx,2] or [B,ny,nx,2] — of `dtype` on
+    `device`; bool stands for uint8 (a view of the same storage).  At least one map, no side empty, every map contiguous, a batch's
+    stride(0) at least a map; `stride` is what the library is given."""
+    if not isinstance(src, torch.Tensor) or src.device != device:
+        raise ValueError("src must be a tensor on the renderer's device")
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)
+    rank = 2 if per_cell == 1 else 3
+    if src.dtype != dtype or src.dim() not in (rank, rank + 1) or (per_cell > 1 and src.shape[-1] != per_cell):
+        raise ValueError(f"{what} must be {_dtype_name(dtype)}{' or bool' if dtype == torch.uint8 else ''} "
+                         + ("[ny,nx] or [B,ny,nx]" if per_cell == 1 else f"[ny,nx,{per_cell}] or [B,ny,nx,{per_cell}]"))
+    batched = src.dim() == rank + 1
+    maps = src if batched else src.unsqueeze(0)
+    b, ny, nx = int(maps.shape[0]), int(maps.shape[1]), int(maps.shape[2])
+    if min(b, ny, nx) < 1 or not maps[0].is_contiguous() or (b > 1 and int(maps.stride(0)) < ny * nx * per_cell):
+        raise ValueError("src must hold at least one map, each contiguous")
+    return maps, batched, b, ny, nx, _frame_stride(maps, ny * nx * per_cell)
+
+
+def _rows_arg(x, device, dtype, width, what):
+    """`x` — a tensor, or anything np.asarray takes — as a contiguous [n,width] tensor of `dtype` on `device`, n >= 1.  Host integers
+    that do not fit `dtype` are refused (a tensor's values are not read)."""
+    if not isinstance(x, torch.Tensor):
+        a = np.asarray(x, np.float64 if dtype.is_floating_point else np.int64)
+        if not dtype.is_floating_point and a.size and np.abs(a).max() > torch.iinfo(dtype).max:
+            raise ValueError(f"{what} must hold {_dtype_name(dtype)} values")
+        x = torch.from_numpy(np.ascontiguousarray(a)).to(dtype)
+    x = x.to(device=device, dtype=dtype).contiguous()
+    if x.dim() != 2 or x.shape[1] != width or x.shape[0] < 1:
+        raise ValueError(f"{what} must be [n,{width}] with n >= 1")
+    return x
+
+
 class Renderer:
     """One rendering context bound to one GPU (one process per GPU is the intended deployment)."""
 
@@ -618,19 +690,11 @@ class Renderer:
         return h.wait()
 
     # -- JPEG files made on the device (include/sage_gs.h sgs_encode_jpeg) ------------------------------------------------------
-    def _jpeg_frames_of(self, rgb: torch.Tensor) -> torch.Tensor:
-        if rgb.dim() == 3:
-            rgb = rgb.unsqueeze(0)
-        if (rgb.device != self.device or rgb.dtype != torch.float32 or rgb.dim() != 4 or rgb.shape[-1] != 3
-                or (rgb.shape[0] > 0 and not rgb[0].is_contiguous())):
-            raise ValueError("rgb must be float32 [H,W,3] or [B,H,W,3] on the renderer's device with contiguous frames")
-        return rgb
-
     def _encode_jpeg_into(self, rgb: torch.Tensor, n: int, params, out: torch.Tensor, meta: torch.Tensor):
         """sgs_encode_jpeg of the first n frames of rgb [B,H,W,3] on the current stream: files into `out` (uint8, device), offsets and
         sizes into the pinned int64 [2, >= n] `meta`.  Does not synchronise."""
         h, w = int(rgb.shape[1]), int(rgb.shape[2])
-        self._lib.check(self._lib.sgs_encode_jpeg(self._ctx, rgb.data_ptr(), w, h, int(n), int(rgb.stride(0)) if rgb.shape[0] > 1 else h * w * 3,
+        self._lib.check(self._lib.sgs_encode_jpeg(self._ctx, rgb.data_ptr(), w, h, int(n), _frame_stride(rgb, h * w * 3),
                                                   C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
                                                   self._stream()), self._ctx)
 
@@ -655,7 +719,7 @@ class Renderer:
         Image.fromarray(get_rgba()[:, :, :3]).save(f, quality=quality) writes for the same picture, same tables, same default
         subsampling (generate_images.py:431-432; vlm_client_modular.py:346-351).  Synchronous: the simple form; jpeg_frames() is the
         pipelined one.  A frame's bytes do not depend on the batch it is encoded in."""
-        rgb = self._jpeg_frames_of(rgb)
+        rgb, _ = _frames_arg(rgb, self.device, torch.float32, (None, None, 3), "rgb")
         n = int(rgb.shape[0])
         if n == 0:
             return []
@@ -680,21 +744,16 @@ class Renderer:
         of the VLM client (vlm_client_modular.py:354-365).  Lossless; synchronous; a frame's bytes do not depend on the batch it is
         encoded in."""
         params = _capi.png_params(format, depth_scale, depth_max)
-        tail = 1 if params.format == _capi.PNG_RGB8 else 0
-        if frames.dim() == 2 + tail:
-            frames = frames.unsqueeze(0)
-        if (frames.device != self.device or frames.dtype != torch.float32 or frames.dim() != 3 + tail or (tail and frames.shape[-1] != 3)
-                or (frames.shape[0] > 0 and not frames[0].is_contiguous())):
-            raise ValueError("frames must be float32 [H,W,3] / [n,H,W,3] (rgb8) or [H,W] / [n,H,W] (depth16) on the renderer's device "
-                             "with contiguous frames")
+        rgb = params.format == _capi.PNG_RGB8
+        frames, _ = _frames_arg(frames, self.device, torch.float32, (None, None, 3) if rgb else (None, None), "frames")
         n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         if n == 0:
             return []
-        frame_floats = h * w * (3 if tail else 1)
+        frame_floats = h * w * (3 if rgb else 1)
         cap = n * max(1 << 12, frame_floats // 2)                             # half a byte a sample to begin with; the sizes say what fits
 
         def issue(out, meta):
-            self._lib.check(self._lib.sgs_encode_png(self._ctx, frames.data_ptr(), w, h, n, int(frames.stride(0)) if n > 1 else frame_floats,
+            self._lib.check(self._lib.sgs_encode_png(self._ctx, frames.data_ptr(), w, h, n, _frame_stride(frames, frame_floats),
                                                      C.byref(params), out.data_ptr(), int(out.numel()), meta[0].data_ptr(), meta[1].data_ptr(),
                                                      self._stream()), self._ctx)
         return self._encode_files(n, cap, issue)
@@ -717,26 +776,14 @@ class Renderer:
         lo, hi = (float("-inf"), float("inf")) if clip is None else (float(clip[0]), float(clip[1]))
         w, h = int(size[0]), int(size[1])
         params = _capi.resize_params("rgb8" if tail else "f32", filter, w, h, lo, hi)
-        single = frames.dim() == 2 + tail
-        if single:
-            frames = frames.unsqueeze(0)
-        if (frames.device != self.device or frames.dtype != torch.float32 or frames.dim() != 3 + tail or (tail and frames.shape[-1] != 3)
-                or (frames.shape[0] > 0 and not frames[0].is_contiguous())):
-            raise ValueError("frames must be float32 [H,W,3] / [n,H,W,3] (rgb) or [H,W] / [n,H,W] (depth) on the renderer's device "
-                             "with contiguous frames")
+        frames, single = _frames_arg(frames, self.device, torch.float32, (None, None, 3) if tail else (None, None), "frames")
         n, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         shape = (n, h, w, 3) if tail else (n, h, w)
-        if out is None:
-            res = torch.empty(shape, dtype=torch.float32, device=self.device)
-        else:
-            if (out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous()
-                    or tuple(out.shape) != (shape[1:] if single else shape)):
-                raise ValueError("out must be a contiguous float32 tensor of the result's shape on the renderer's device")
-            res = out.unsqueeze(0) if single else out
+        res = _out_arg(out, self.device, shape[1:] if single else shape, torch.float32, "out")
         ch = 3 if tail else 1
-        self._lib.check(self._lib.sgs_resize(self._ctx, frames.data_ptr(), W, H, n, int(frames.stride(0)) if n > 1 else H * W * ch,
+        self._lib.check(self._lib.sgs_resize(self._ctx, frames.data_ptr(), W, H, n, _frame_stride(frames, H * W * ch),
                                              C.byref(params), res.data_ptr(), h * w * ch, self._stream()), self._ctx)
-        return res[0] if single else res
+        return res
 
     # -- test hooks -------------------------------------------------------------------------------
     def debug_buffer(self, what, dtype):
@@ -804,10 +851,7 @@ class Renderer:
         rows is written (the rest of `out` is left as it was).  Statistics in last_stats."""
         mesh = self._mesh_of(mesh)
         h, w = camera.height, camera.width
-        if out is None:
-            out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
-        elif out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (h, w) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [H, W] tensor on the renderer's device")
+        out = _out_arg(out, self.device, (h, w), torch.float32, "out", zero=True)           # zeros: a band leaves the other rows alone
         r0, r1 = (0, -1) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
         cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
         cam = self._c_camera(camera, mesh)
@@ -828,10 +872,7 @@ class Renderer:
         h, w = cameras[0].height, cameras[0].width
         if any(c.height != h or c.width != w for c in cameras):
             raise ValueError("all cameras of a batch must share a resolution")
-        if out is None:
-            out = torch.zeros((b, h, w), dtype=torch.float32, device=self.device)
-        elif out.device != self.device or out.dtype != torch.float32 or tuple(out.shape) != (b, h, w) or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 [B, H, W] tensor on the renderer's device")
+        out = _out_arg(out, self.device, (b, h, w), torch.float32, "out", zero=True)
         cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
         arr = self._c_cameras(cameras, mesh)
         stats = (_capi.SgsStats * b)()
@@ -868,13 +909,6 @@ class Renderer:
             torch.cuda.synchronize(self.device)
             self._lib.check(self._lib.sgs_mesh_set_labels(self._ctx, mesh.handle, lab.data_ptr() if lab.numel() else None, 1), self._ctx)
 
-    def _ids_out(self, out, shape, dtype, name):
-        if out is None:
-            return torch.zeros(shape, dtype=dtype, device=self.device)
-        if out.device != self.device or out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {str(dtype).split('.')[-1]} {list(shape)} tensor on the renderer's device")
-        return out
-
     def render_mesh_ids(self, camera: Camera, mesh: Mesh, *, config: Optional[RenderConfig] = None, tile_rows=None,
                         out: Optional[torch.Tensor] = None, out_depth: Optional[torch.Tensor] = None, return_depth=False, stats=False,
                         timing=False):
@@ -885,8 +919,8 @@ class Renderer:
         last_stats).  The channel is this project's own definition (the reference has no such observation)."""
         mesh = self._mesh_of(mesh)
         h, w = camera.height, camera.width
-        out = self._ids_out(out, (h, w), torch.int32, "out")
-        depth = self._ids_out(out_depth, (h, w), torch.float32, "out_depth") if (return_depth or out_depth is not None) else None
+        out = _out_arg(out, self.device, (h, w), torch.int32, "out", zero=True)
+        depth = _out_arg(out_depth, self.device, (h, w), torch.float32, "out_depth", zero=True) if (return_depth or out_depth is not None) else None
         r0, r1 = (0, -1) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
         cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
         cam = self._c_camera(camera, mesh)
@@ -912,8 +946,8 @@ class Renderer:
         h, w = cameras[0].height, cameras[0].width
         if any(c.height != h or c.width != w for c in cameras):
             raise ValueError("all cameras of a batch must share a resolution")
-        out = self._ids_out(out, (b, h, w), torch.int32, "out")
-        depth = self._ids_out(out_depth, (b, h, w), torch.float32, "out_depth") if (return_depth or out_depth is not None) else None
+        out = _out_arg(out, self.device, (b, h, w), torch.int32, "out", zero=True)
+        depth = _out_arg(out_depth, self.device, (b, h, w), torch.float32, "out_depth", zero=True) if (return_depth or out_depth is not None) else None
         cfg = self._c_config(config, _capi.FLAG_TIMING if timing else 0)
         arr = self._c_cameras(cameras, mesh)
         st = (_capi.SgsStats * b)()
@@ -928,12 +962,9 @@ class Renderer:
 
     # -- the visible-object table of id frames (include/sage_gs.h sgs_object_table: this project's own definition, as the ids are) ----
     def _id_frames_of(self, ids: torch.Tensor, depth: Optional[torch.Tensor]):
-        if ids.dim() == 2:
-            ids = ids.unsqueeze(0)
-            depth = depth.unsqueeze(0) if depth is not None and depth.dim() == 2 else depth
-        if (ids.device != self.device or ids.dtype != torch.int32 or ids.dim() != 3 or ids.shape[0] < 1 or ids.shape[1] < 1 or ids.shape[2] < 1
-                or not ids[0].is_contiguous()):
-            raise ValueError("ids must be int32 [H,W] or [B,H,W] on the renderer's device with contiguous frames")
+        ids, single = _frames_arg(ids, self.device, torch.int32, (None, None), "ids", min_frames=1)
+        if single and depth is not None and depth.dim() == 2:
+            depth = depth.unsqueeze(0)
         if depth is not None and (depth.device != self.device or depth.dtype != torch.float32 or tuple(depth.shape) != tuple(ids.shape)
                                   or depth.stride() != ids.stride()):
             raise ValueError("depth must be float32 of the ids' shape and strides on the renderer's device")
@@ -953,15 +984,11 @@ class Renderer:
         n_labels = int(n_labels)
         if n_labels < 1:
             raise ValueError("n_labels must be at least 1")
-        if out is None:
-            rows = torch.empty((b, n_labels, _capi.OBJECT_ROW_WORDS), dtype=torch.int32, device=self.device)
-            counts = torch.empty((b, 2), dtype=torch.int32, device=self.device)
-        else:
-            rows, counts = out
-            rows = self._ids_out(rows, (b, n_labels, _capi.OBJECT_ROW_WORDS), torch.int32, "out[0]")
-            counts = self._ids_out(counts, (b, 2), torch.int32, "out[1]")
+        rows, counts = (None, None) if out is None else out
+        rows = _out_arg(rows, self.device, (b, n_labels, _capi.OBJECT_ROW_WORDS), torch.int32, "out[0]")
+        counts = _out_arg(counts, self.device, (b, 2), torch.int32, "out[1]")
         self._lib.check(self._lib.sgs_object_table(self._ctx, ids.data_ptr(), depth.data_ptr() if depth is not None else None, b, h, w,
-                                                   int(ids.stride(0)) if b > 1 else h * w, n_labels, rows.data_ptr(), counts.data_ptr(),
+                                                   _frame_stride(ids, h * w), n_labels, rows.data_ptr(), counts.data_ptr(),
                                                    self._stream()), self._ctx)
         return rows, counts
 
@@ -1009,12 +1036,7 @@ class Renderer:
         ssim_rgb[3], mse (in levels squared) and psnr (dB, inf at zero error).  The frame's levels are the ones get_rgba() shows.
         ValueError on a size or dtype mismatch: nothing is ever resized here.  This project's own definition: the reference names
         the measure for ImgNav (task_types.py:183-208) and returns a placeholder."""
-        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32:
-            raise ValueError("frames must be a float32 tensor")
-        if frames.dim() == 3:
-            frames = frames.unsqueeze(0)
-        if frames.device != self.device or frames.dim() != 4 or frames.shape[-1] != 3 or frames.shape[0] < 1 or not frames[0].is_contiguous():
-            raise ValueError("frames must be float32 [H,W,3] or [B,H,W,3] on the renderer's device with contiguous frames")
+        frames, _ = _frames_arg(frames, self.device, torch.float32, (None, None, 3), "frames", min_frames=1)
         b, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         target = self._target_levels(target)
         if tuple(target.shape[-3:]) != (h, w, 3):
@@ -1024,9 +1046,9 @@ class Renderer:
         if w < _capi.SIMILARITY_WINDOW or h < _capi.SIMILARITY_WINDOW:
             raise ValueError(f"frames of {w} x {h} hold no {_capi.SIMILARITY_WINDOW} x {_capi.SIMILARITY_WINDOW} window")
         size = 3 * h * w
-        t_stride = 0 if target.dim() == 3 else (int(target.stride(0)) if b > 1 else size)
+        t_stride = 0 if target.dim() == 3 else _frame_stride(target, size)
         rows = torch.empty((b, 8), dtype=torch.int64, device=self.device)
-        self._lib.check(self._lib.sgs_image_similarity(self._ctx, frames.data_ptr(), w, h, b, int(frames.stride(0)) if b > 1 else size,
+        self._lib.check(self._lib.sgs_image_similarity(self._ctx, frames.data_ptr(), w, h, b, _frame_stride(frames, size),
                                                        target.data_ptr(), t_stride, rows.data_ptr(), self._stream()), self._ctx)
         raw = np.ascontiguousarray(rows.cpu().numpy()).view(_capi.SIMILARITY_ROW_DTYPE).reshape(b)
         out = np.zeros(b, _capi.SIMILARITY_DTYPE)
@@ -1078,12 +1100,7 @@ class Renderer:
         stream.  Every count is an integer: the map does not depend on the batch, the order of the frames or how they are split
         over calls.  This project's own definition: the reference counts the cells the agent stood in (measures.py:399-437)."""
         g = TopdownGrid() if grid is None else grid
-        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
-            raise ValueError("depth must be a float32 tensor")
-        if depth.dim() == 2:
-            depth = depth.unsqueeze(0)
-        if depth.device != self.device or depth.dim() != 3 or min(depth.shape) < 1 or not depth[0].is_contiguous():
-            raise ValueError("depth must be float32 [H,W] or [B,H,W] on the renderer's device with contiguous frames")
+        depth, _ = _frames_arg(depth, self.device, torch.float32, (None, None), "depth", min_frames=1)
         b, h, w = int(depth.shape[0]), int(depth.shape[1]), int(depth.shape[2])
         if isinstance(cameras_or_P, torch.Tensor):
             P = cameras_or_P
@@ -1094,17 +1111,13 @@ class Renderer:
             if len(cams) != b or any(c.width != w or c.height != h for c in cams):
                 raise ValueError(f"{len(cams)} cameras for {b} frames of {w} x {h}")
             P = self.pix_to_map(cams)
-        if out is None:
-            if not clear:
-                raise ValueError("clear=False adds to a grid: pass it as out=(grid, counts)")
-            cells = torch.empty((int(g.ny), int(g.nx), 2), dtype=torch.int32, device=self.device)
-            counts = torch.empty((b, 4), dtype=torch.int32, device=self.device)
-        else:
-            cells, counts = out
-            cells = self._ids_out(cells, (int(g.ny), int(g.nx), 2), torch.int32, "out[0]")
-            counts = self._ids_out(counts, (b, 4), torch.int32, "out[1]")
+        if out is None and not clear:
+            raise ValueError("clear=False adds to a grid: pass it as out=(grid, counts)")
+        cells, counts = (None, None) if out is None else out
+        cells = _out_arg(cells, self.device, (int(g.ny), int(g.nx), 2), torch.int32, "out[0]")
+        counts = _out_arg(counts, self.device, (b, 4), torch.int32, "out[1]")
         params = g.c_params(clear)
-        self._lib.check(self._lib.sgs_topdown_map(self._ctx, depth.data_ptr(), w, h, b, int(depth.stride(0)) if b > 1 else h * w,
+        self._lib.check(self._lib.sgs_topdown_map(self._ctx, depth.data_ptr(), w, h, b, _frame_stride(depth, h * w),
                                                   P.data_ptr(), C.byref(params), cells.data_ptr(), counts.data_ptr(), self._stream()), self._ctx)
         return cells, counts
 
@@ -1136,42 +1149,27 @@ class Renderer:
         [4] or [B,4]: obstacle cells, cells with 0 < d2 <= max_d2, cells with max_d2 < d2 < NONE, cells equal to NONE.
         out=(d2, counts): contiguous int32 tensors of those shapes.  Nothing is copied to the host; asynchronous on the current
         stream.  All integer: a map's d2 does not depend on the batch it is issued in."""
-        if not isinstance(src, torch.Tensor) or src.device != self.device:
-            raise ValueError("src must be a tensor on the renderer's device")
         if kind is None:
-            kind = "topdown" if src.dtype == torch.int32 else "mask"
+            kind = "topdown" if getattr(src, "dtype", None) == torch.int32 else "mask"
         if kind == "mask":
-            if src.dtype == torch.bool:
-                src = src.view(torch.uint8)
-            if src.dtype != torch.uint8 or src.dim() not in (2, 3):
-                raise ValueError("a mask must be uint8 or bool [ny,nx] or [B,ny,nx]")
-            batched, maps = src.dim() == 3, src if src.dim() == 3 else src.unsqueeze(0)
-            source, per_cell = _capi.CLEARANCE_SRC_MASK8, 1
+            maps, batched, b, ny, nx, stride = _maps_arg(src, self.device, torch.uint8, 1, "a mask")
+            source = _capi.CLEARANCE_SRC_MASK8
             if unseen_blocks:
                 raise ValueError("unseen_blocks has a meaning for a seen map only")
         elif kind == "topdown":
-            if src.dtype != torch.int32 or src.dim() not in (3, 4) or src.shape[-1] != 2:
-                raise ValueError("a seen map must be int32 [ny,nx,2] or [B,ny,nx,2]")
-            batched, maps = src.dim() == 4, src if src.dim() == 4 else src.unsqueeze(0)
-            source, per_cell = _capi.CLEARANCE_SRC_TOPDOWN, 2
+            maps, batched, b, ny, nx, stride = _maps_arg(src, self.device, torch.int32, 2, "a seen map")
+            source = _capi.CLEARANCE_SRC_TOPDOWN
         else:
             raise ValueError(f"unknown kind {kind!r}: 'mask' or 'topdown'")
-        b, ny, nx = int(maps.shape[0]), int(maps.shape[1]), int(maps.shape[2])
-        if min(b, ny, nx) < 1 or not maps[0].is_contiguous() or (b > 1 and int(maps.stride(0)) < ny * nx * per_cell):
-            raise ValueError("src must hold at least one map, each contiguous")
         if not (1 <= int(min_hits) <= 0xFFFFFFFF and 0 <= int(max_d2) <= 0xFFFFFFFF):
             raise ValueError("min_hits must be within 1 .. 2^32 - 1 and max_d2 within 0 .. 2^32 - 1")
         shape, cshape = ((b, ny, nx), (b, 4)) if batched else ((ny, nx), (4,))
-        if out is None:
-            d2 = torch.empty(shape, dtype=torch.int32, device=self.device)
-            counts = torch.empty(cshape, dtype=torch.int32, device=self.device)
-        else:
-            d2 = self._ids_out(out[0], shape, torch.int32, "out[0]")
-            counts = self._ids_out(out[1], cshape, torch.int32, "out[1]")
+        d2 = _out_arg(None if out is None else out[0], self.device, shape, torch.int32, "out[0]")
+        counts = _out_arg(None if out is None else out[1], self.device, cshape, torch.int32, "out[1]")
         work = torch.empty((b, ny, nx), dtype=torch.int32, device=self.device)
         params = _capi.SgsClearanceParams(nx, ny, source, _capi.CLEARANCE_UNSEEN_BLOCKS if unseen_blocks else 0,
                                           int(min_hits) if source == _capi.CLEARANCE_SRC_TOPDOWN else 0, int(max_d2), 0)
-        self._lib.check(self._lib.sgs_clearance_map(self._ctx, maps.data_ptr(), b, int(maps.stride(0)) if b > 1 else ny * nx * per_cell,
+        self._lib.check(self._lib.sgs_clearance_map(self._ctx, maps.data_ptr(), b, stride,
                                                     C.byref(params), work.data_ptr(), d2.data_ptr(), counts.data_ptr(), self._stream()), self._ctx)
         return d2, counts
 
@@ -1183,12 +1181,7 @@ class Renderer:
         np.asarray takes.  n_samples <= 1 checks the end point alone.  A NaN or infinite coordinate collides."""
         if not isinstance(d2, torch.Tensor) or d2.device != self.device or d2.dtype != torch.int32 or d2.dim() != 2 or not d2.is_contiguous():
             raise ValueError("d2 must be a contiguous int32 [ny,nx] tensor on the renderer's device")
-        if isinstance(segments, torch.Tensor):
-            segs = segments.to(device=self.device, dtype=torch.float64).contiguous()
-        else:
-            segs = torch.from_numpy(np.ascontiguousarray(np.asarray(segments, np.float64))).to(self.device)
-        if segs.dim() != 2 or segs.shape[1] != 4 or segs.shape[0] < 1:
-            raise ValueError("segments must be [n,4] with n >= 1")
+        segs = _rows_arg(segments, self.device, torch.float64, 4, "segments")
         n = int(segs.shape[0])
         out = torch.empty((n, 2), dtype=torch.int32, device=self.device)
         f = frame.c_frame(n_samples)
@@ -1198,29 +1191,23 @@ class Renderer:
 
     # -- geodesic fields and shortest paths (include/sage_gs.h sgs_geodesic_field, sgs_geodesic_path) ---------------------------------
     def _geodesic_source(self, src, max_d2):
-        if not isinstance(src, torch.Tensor) or src.device != self.device:
-            raise ValueError("src must be a tensor on the renderer's device")
-        if src.dtype == torch.bool:
-            src = src.view(torch.uint8)
-        if src.dtype == torch.uint8:
+        dtype = getattr(src, "dtype", None)
+        if dtype in (torch.uint8, torch.bool):
             source = _capi.GEODESIC_SRC_MASK8
             if max_d2 is not None:
                 raise ValueError("max_d2 has a meaning for a d2 map only")
-        elif src.dtype == torch.int32:
+        elif dtype == torch.int32:
             source = _capi.GEODESIC_SRC_D2
             if max_d2 is None:
                 raise ValueError("a d2 map needs max_d2: a cell is blocked iff d2 <= max_d2")
         else:
             raise ValueError("src must be a mask (uint8 or bool) or a d2 map (int32 as clearance_map returns it), [ny,nx] or [B,ny,nx]")
-        if src.dim() not in (2, 3):
-            raise ValueError("src must be [ny,nx] or [B,ny,nx]")
-        maps = src if src.dim() == 3 else src.unsqueeze(0)
-        b, ny, nx = (int(v) for v in maps.shape)
-        if min(b, ny, nx) < 1 or max(nx, ny) > _capi.GEODESIC_MAX_N or not maps[0].is_contiguous() or (b > 1 and int(maps.stride(0)) < ny * nx):
-            raise ValueError(f"src must hold at least one map of 1 .. {_capi.GEODESIC_MAX_N} cells a side, each contiguous")
+        maps, _, b, ny, nx, stride = _maps_arg(src, self.device, torch.uint8 if source == _capi.GEODESIC_SRC_MASK8 else torch.int32, 1, "src")
+        if max(nx, ny) > _capi.GEODESIC_MAX_N:
+            raise ValueError(f"src must hold maps of 1 .. {_capi.GEODESIC_MAX_N} cells a side")
         if max_d2 is not None and not 0 <= int(max_d2) <= 0xFFFFFFFF:
             raise ValueError("max_d2 must be within 0 .. 2^32 - 1")
-        return maps, source, b, ny, nx, int(maps.stride(0)) if b > 1 else ny * nx
+        return maps, source, b, ny, nx, stride
 
     @staticmethod
     def _geodesic_table(rows, width, what):
@@ -1277,12 +1264,7 @@ class Renderer:
         if not isinstance(steps, torch.Tensor) or steps.device != self.device or steps.dtype != torch.int32 or not steps.is_contiguous() or \
                 tuple(steps.shape) != (len(fm), ny, nx, 2):
             raise ValueError(f"steps must be a contiguous int32 [{len(fm)},{ny},{nx},2] tensor on the renderer's device")
-        if isinstance(queries, torch.Tensor):
-            q = queries.to(device=self.device, dtype=torch.int32).contiguous()
-        else:
-            q = torch.from_numpy(self._geodesic_table(queries, 3, "queries")).to(self.device)
-        if q.dim() != 2 or q.shape[1] != 3 or q.shape[0] < 1:
-            raise ValueError("queries must be [n,3] with n >= 1")
+        q = _rows_arg(queries if isinstance(queries, torch.Tensor) else np.asarray(queries, np.int64).reshape(-1, 3), self.device, torch.int32, 3, "queries")
         n = int(q.shape[0])
         max_len = nx * ny if max_len is None else int(max_len)
         if max_len < 1:
@@ -1429,7 +1411,7 @@ class JpegFrames:
         self._host_np[k] = self._host[k].numpy()
 
     def submit(self, rgb: torch.Tensor, n: Optional[int] = None) -> "JpegFrames.Handle":
-        rgb = self._r._jpeg_frames_of(rgb)
+        rgb, _ = _frames_arg(rgb, self._r.device, torch.float32, (None, None, 3), "rgb")
         n = int(rgb.shape[0]) if n is None else int(n)
         if not 0 <= n <= min(int(rgb.shape[0]), self.shape[0]) or tuple(rgb.shape[1:3]) != self.shape[1:3]:
             raise ValueError(f"the ring holds up to {self.shape[0]} frames of {self.shape[1]} x {self.shape[2]} pixels")
