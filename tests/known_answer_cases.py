@@ -126,6 +126,7 @@ def case_culling(drv):
     assert nvis([0, 0, -1.0]) == (0, 0)                   # behind the camera
     assert nvis([50.0, 0, 2.0]) == (0, 0)                 # in front but far off-screen: empty tile rect
     assert nvis([0, 0, 10.5], onp.Config(far=10.0))[0] == 0
+    assert nvis([0, 0, 10.0], onp.Config(far=10.0))[0] == 1          # tz == far is kept: the cull is tz > far
 
 
 def case_rect_and_duplicates(drv):

@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 import oracle_c
 import oracle_np as onp
+import frontend_cases as fc
 import parity_cases as pc
 from conftest import assert_frame_close, stored_variants
 from tight_parity import assert_frame_tight
@@ -1327,3 +1328,36 @@ def test_regrown_scratch_of_the_mesh_path_the_encoders_and_the_resize():
         assert (s1[0] == s0).all() and (s_big[0] == s_big[2]).all() and (r.resize(big[1], (100, 70)).cpu().numpy() == s_big[1]).all()
     finally:
         r.close()
+
+
+# ---- the front end's and the HBM sort's integer decisions, each sat on by a deterministic case (frontend_cases.py) ----------------------
+@pytest.mark.parametrize("which", ["identity", "turned", "off_centre"])
+def test_chunk_cull_margins(drv, which):
+    fc.case_chunk_margins(drv, which)
+
+
+def test_near_and_far_plane_at_equality_and_one_ulp_to_either_side(drv):
+    fc.case_near_far_equality(drv)
+
+
+@pytest.mark.parametrize("which", ["identity", "turned", "off_centre"])
+def test_giants_beyond_both_jacobian_clamps_at_every_edge(drv, which):
+    fc.case_clamped_giants(drv, which)
+
+
+def test_needle_determinant_needs_fp64(drv):
+    fc.case_needle_determinant(drv)
+
+
+@pytest.mark.parametrize("resort", [False, True], ids=["runs_up_to_32", "with_a_run_of_33"])
+def test_tie_runs_in_a_bucket_sorted_through_hbm(drv, resort):
+    fc.case_short_tie_runs(drv, resort=resort)
+
+
+def test_batch_groups_of_eight_frames(drv):
+    fc.case_batch_groups_of_eight(drv)
+
+
+@pytest.mark.parametrize("survivor", ["last", "first"])
+def test_deep_tile_window_whose_only_survivor_is_its_last_or_first_record(drv, survivor):
+    fc.case_deep_window_ends(drv, survivor)
