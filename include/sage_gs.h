@@ -812,6 +812,61 @@ int sgs_geodesic_path(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
                       const int32_t* field_map, int n_fields, const uint32_t* dist, const int32_t* queries, int n_queries,
                       int max_len, int32_t* out_cells, uint32_t* out_info, void* hip_stream);
 
+/* ---- Connected regions of a grid — which cells BELONG TOGETHER.  What the reference's semantic_map_builder.py computes with two
+ * scipy.ndimage.label calls per scene (the wall pixels of occupancy.png into wall items, its zero pixels into "Unable Area" items), and
+ * what reachability on a clearance map is: astar_pixel cuts corners, so two free cells have a path exactly when they lie in one
+ * 8-connected region of the free cells.  No new version: no existing struct changes.
+ *
+ *   Set      a cell is in the set iff lo <= v <= hi, v the cell's value.  SGS_REGIONS_SRC_MASK8: v is a byte of a uint8 [ny][nx] map
+ *            (lo = 1, hi = 255: non-zero; lo = hi = wall_value: the reference's occupancy == wall_value).  SGS_REGIONS_SRC_D2: v is a
+ *            uint32 word of the map sgs_clearance_map wrote (lo = max_d2 + 1, hi = 0xFFFFFFFF: where the agent can stand).  Map k
+ *            begins k * map_stride ELEMENTS after map 0.
+ *   Regions  the classes of the set under 8-connectivity (two cells whose coordinates differ by at most 1 in each axis) or
+ *            4-connectivity (params.connectivity).  A diagonal pair is connected whatever its two orthogonal cells hold.
+ *   Labels   int32 [n_maps][ny][nx], dense: 0 for a cell outside the set, otherwise 1 + the number of regions whose least raster
+ *            index j * nx + i is smaller than this region's — scipy.ndimage.label's numbering for both structures.
+ *   Rows     out_rows is sgs_region_row [n_maps][max_regions]; row r describes label r + 1.  Regions with a label above max_regions
+ *            get no row (their cells still carry the right label); rows past the number of regions are empty rows: area 0, x_min =
+ *            y_min = INT32_MAX, x_end = y_end = 0, first = 0xFFFFFFFF, sums 0.  max_regions = 0 with out_rows = NULL: labels only.
+ *   Counters out_counts is uint32 [n_maps][4], written whole by every call: [0] regions found (the true number, which may exceed
+ *            max_regions), [1] cells in the set, [2] the largest area, [3] the least label that has that area (0: the set is empty).
+ *   Exact    everything is an integer minimum, count or sum: a map's output depends on that map and the params alone, not on the
+ *            batch, map_stride, the tiling or the schedule.
+ *   Kernels  sage-3d_official_amd/csrc/sgs_regions.h: a union-find forest whose parents only ever decrease. */
+#define SGS_REGIONS_SRC_MASK8 0
+#define SGS_REGIONS_SRC_D2 1
+#define SGS_REGIONS_MAX_N 4096
+#define SGS_REGIONS_MAX_MAPS 65535
+typedef struct sgs_regions_params {      /* 32 bytes */
+    int32_t  nx, ny;           /* cells; 1 <= nx, ny <= 4096 */
+    int32_t  source;           /* SGS_REGIONS_SRC_* */
+    int32_t  connectivity;     /* 4 or 8 */
+    uint32_t lo, hi;           /* the set: lo <= v <= hi; hi <= 255 for a mask */
+    uint32_t flags;            /* 0 */
+    int32_t  reserved;         /* 0 */
+} sgs_regions_params;
+typedef struct sgs_region_row {          /* 40 bytes, 8-byte aligned */
+    uint32_t area;             /* cells */
+    int32_t  x_min, y_min;     /* the tight box: x_min <= i < x_end, y_min <= j < y_end */
+    int32_t  x_end, y_end;     /* greatest + 1 */
+    uint32_t first;            /* the region's least raster index j * nx + i */
+    uint64_t sum_x, sum_y;     /* of i and of j over the region's cells */
+} sgs_region_row;
+/* The tile edge of the local solve, and the uint32 words of `work` for n_maps maps of nx x ny (-1 for arguments the call would
+ * refuse). */
+int sgs_regions_tile(void);
+int64_t sgs_regions_work_words(int nx, int ny, int n_maps);
+/* src, work, labels, out_rows and out_counts are DEVICE buffers the caller owns; work is scratch of sgs_regions_work_words words
+ * whose contents before and after the call mean nothing.  Stream-ordered and asynchronous: the call never synchronises, owns no
+ * scratch and leaves none behind.  SGS_ERR_INVALID, before anything is enqueued or written, with a message that names the argument:
+ * null src, params, work, labels or out_counts; null out_rows with max_regions > 0, or max_regions < 0; n_maps outside 1 .. 65535;
+ * nx or ny outside 1 .. 4096; an unknown source or connectivity; lo > hi, or hi > 255 with a mask; flags or reserved != 0;
+ * map_stride shorter than a map (nx * ny elements); work, labels, out_counts or a d2 src not 4-byte aligned; out_rows not 8-byte
+ * aligned; labels and work overlapping. */
+int sgs_regions_label(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_regions_params* params,
+                      uint32_t* work, int32_t* labels, sgs_region_row* out_rows, int32_t max_regions,
+                      uint32_t* out_counts, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

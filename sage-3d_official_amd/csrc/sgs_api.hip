@@ -30,6 +30,7 @@
 #include "sgs_topdown.h"
 #include "sgs_clearance.h"
 #include "sgs_geodesic.h"
+#include "sgs_regions.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2480,6 +2481,76 @@ int sgs_geodesic_path(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
     Q.stride = map_stride; Q.nx = p->nx; Q.ny = p->ny; Q.n_fields = n_fields; Q.kind = p->source; Q.n = n_queries; Q.max_len = max_len; Q.max_d2 = p->max_d2;
     for (int f = 0; f < SGS_GEO_PATH_MAX_FIELDS; ++f) Q.field_map[f] = f < n_fields ? field_map[f] : 0;
     hipLaunchKernelGGL(sgs::k_geo_path, dim3((unsigned)((n_queries + SGS_GEO_THREADS - 1) / SGS_GEO_THREADS)), dim3(SGS_GEO_THREADS), 0, st, Q);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_regions_label (csrc/sgs_regions.h) ------------------------------------------------------------------------------------------------
+static_assert(sizeof(sgs_regions_params) == 32, "sgs_regions_params is eight 4-byte fields");
+static_assert(sizeof(sgs_region_row) == sizeof(sgs::RegRow) && alignof(sgs_region_row) == 8, "sgs_region_row is the kernels' RegRow");
+static_assert(SGS_REGIONS_SRC_MASK8 == SGS_REG_SRC_MASK8 && SGS_REGIONS_SRC_D2 == SGS_REG_SRC_D2 && SGS_REGIONS_MAX_N == SGS_REG_MAX_N &&
+              SGS_REGIONS_MAX_MAPS == SGS_REG_MAX_MAPS, "the kernels' constants are the header's");
+
+extern "C" {
+
+int sgs_regions_tile(void) { return SGS_REG_TILE; }
+
+int64_t sgs_regions_work_words(int nx, int ny, int n_maps) {
+    if (nx < 1 || ny < 1 || nx > SGS_REG_MAX_N || ny > SGS_REG_MAX_N || n_maps < 1 || n_maps > SGS_REG_MAX_MAPS) return -1;
+    const int64_t cells = (int64_t)nx * ny, chunks = (cells + SGS_REG_CHUNK - 1) / SGS_REG_CHUNK;
+    return (int64_t)n_maps * 2 * (cells + chunks);                                   // parent, root, two words per chunk
+}
+
+int sgs_regions_label(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_stride, const sgs_regions_params* p,
+                      uint32_t* work, int32_t* labels, sgs_region_row* out_rows, int32_t max_regions,
+                      uint32_t* out_counts, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_regions_label"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(src, "src", p, "params", work, "work", labels, "labels", out_counts, "out_counts"));
+    if (max_regions < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: max_regions = %d", who, (int)max_regions);
+    if (max_regions > 0) SGS_TRY(a.non_null(out_rows, "out_rows"));
+    if (n_maps < 1 || n_maps > SGS_REG_MAX_MAPS) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_maps = %d (1 <= n_maps <= %d)", who, n_maps, SGS_REG_MAX_MAPS);
+    SGS_TRY(a.grid_within(p->nx, p->ny, SGS_REG_MAX_N));
+    if (p->source != SGS_REGIONS_SRC_MASK8 && p->source != SGS_REGIONS_SRC_D2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
+    if (p->connectivity != 4 && p->connectivity != 8) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown connectivity %d (4 or 8)", who, (int)p->connectivity);
+    if (p->lo > p->hi) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: lo = %u > hi = %u", who, (unsigned)p->lo, (unsigned)p->hi);
+    if (p->source == SGS_REGIONS_SRC_MASK8 && p->hi > 255u) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: hi = %u with a mask (hi <= 255)", who, (unsigned)p->hi);
+    if (p->flags != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
+    const int64_t cells = (int64_t)p->nx * p->ny;
+    SGS_TRY(a.frames_fit(map_stride, cells, "maps overlap (map_stride %lld elements, a map has %lld)"));
+    SGS_TRY(a.aligned(4, work, "work", labels, "labels", out_counts, "out_counts"));
+    if (p->source == SGS_REGIONS_SRC_D2) SGS_TRY(a.aligned(4, src, "src"));          // a mask is read byte by byte
+    SGS_TRY(a.aligned(8, out_rows, "out_rows"));
+    const int64_t work_words = sgs_regions_work_words(p->nx, p->ny, n_maps);
+    SGS_TRY(a.disjoint(labels, 4ull * (uint64_t)n_maps * (uint64_t)cells, "labels", work, 4ull * (uint64_t)work_words, "work"));
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    sgs::RegionsJob J;
+    J.src = src; J.stride = map_stride; J.nx = p->nx; J.ny = p->ny; J.n_maps = n_maps; J.kind = p->source; J.conn = p->connectivity;
+    J.lo = p->lo; J.hi = p->hi; J.cells = (unsigned)cells; J.max_regions = max_regions;
+    J.tiles_x = (p->nx + SGS_REG_TILE - 1) / SGS_REG_TILE; J.tiles_y = (p->ny + SGS_REG_TILE - 1) / SGS_REG_TILE;
+    J.n_chunks = (int)((cells + SGS_REG_CHUNK - 1) / SGS_REG_CHUNK);
+    J.parent = work; J.root = work + (int64_t)n_maps * cells; J.chunks = work + 2 * (int64_t)n_maps * cells;
+    J.labels = labels; J.rows = reinterpret_cast<sgs::RegRow*>(out_rows); J.counts = out_counts;
+    const dim3 threads(SGS_REG_THREADS);
+    const unsigned maps = (unsigned)n_maps, chunks = (unsigned)J.n_chunks;
+    if (max_regions > 0) {
+        const int64_t n_rows = (int64_t)n_maps * max_regions;
+        hipLaunchKernelGGL(sgs::k_reg_clear, dim3((unsigned)std::min<int64_t>((n_rows + SGS_REG_THREADS - 1) / SGS_REG_THREADS, 4096)), threads, 0, st, J.rows, (long long)n_rows);
+    }
+    hipLaunchKernelGGL(sgs::k_reg_local, dim3((unsigned)J.tiles_x, (unsigned)J.tiles_y, maps), threads, 0, st, J);
+    const int64_t border_cells = (int64_t)(J.tiles_y - 1) * p->nx + (int64_t)(J.tiles_x - 1) * p->ny;
+    if (border_cells > 0)
+        hipLaunchKernelGGL(sgs::k_reg_merge, dim3((unsigned)((border_cells + SGS_REG_THREADS - 1) / SGS_REG_THREADS), maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_flatten, dim3(chunks, maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_scan, dim3(maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_rank, dim3(chunks, maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_labels, dim3(chunks, maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_rows, dim3((unsigned)((cells + SGS_REG_ROW_REGION - 1) / SGS_REG_ROW_REGION), maps), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_reg_largest, dim3(maps), threads, 0, st, J);
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }

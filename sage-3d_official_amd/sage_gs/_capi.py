@@ -40,7 +40,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_resize_params_default", "sgs_resize", "sgs_object_table", "sgs_image_similarity",
            "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary",
            "sgs_clearance_map", "sgs_clearance_query",
-           "sgs_geodesic_tile", "sgs_geodesic_state_words", "sgs_geodesic_field", "sgs_geodesic_path")
+           "sgs_geodesic_tile", "sgs_geodesic_state_words", "sgs_geodesic_field", "sgs_geodesic_path",
+           "sgs_regions_tile", "sgs_regions_work_words", "sgs_regions_label")
 
 
 class SgsError(RuntimeError):
@@ -220,6 +221,31 @@ class SgsGeodesicParams(C.Structure):
 assert C.sizeof(SgsGeodesicParams) == 24
 
 
+REGIONS_SRC_MASK8, REGIONS_SRC_D2 = 0, 1     # include/sage_gs.h SGS_REGIONS_SRC_*
+REGIONS_MAX_N, REGIONS_MAX_MAPS = 4096, 65535
+REGIONS_NO_FIRST = 0xFFFFFFFF                # sgs_region_row.first of an empty row
+
+
+class SgsRegionsParams(C.Structure):
+    """include/sage_gs.h sgs_regions_params: the map's size, what its source is, the connectivity and the set lo <= v <= hi."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("source", C.c_int32), ("connectivity", C.c_int32), ("lo", C.c_uint32),
+                ("hi", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class SgsRegionRow(C.Structure):
+    """include/sage_gs.h sgs_region_row: row r of a map's region table describes label r + 1."""
+    _fields_ = [("area", C.c_uint32), ("x_min", C.c_int32), ("y_min", C.c_int32), ("x_end", C.c_int32), ("y_end", C.c_int32),
+                ("first", C.c_uint32), ("sum_x", C.c_uint64), ("sum_y", C.c_uint64)]
+
+
+# the same 40 bytes as a NumPy record: ten int32 words of Renderer.label_regions' rows
+REGION_ROW_DTYPE = __import__("numpy").dtype([("area", "<u4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_end", "<i4"), ("y_end", "<i4"), ("first", "<u4"),
+                                              ("sum_x", "<u8"), ("sum_y", "<u8")])
+REGION_ROW_WORDS = 10
+# the struct-size handshake: the library asserts the same figures when it is compiled (csrc/sgs_api.hip)
+assert C.sizeof(SgsRegionsParams) == 32 and REGION_ROW_DTYPE.itemsize == C.sizeof(SgsRegionRow) == 4 * REGION_ROW_WORDS
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -316,6 +342,9 @@ class Lib:
         lib.sgs_geodesic_state_words.argtypes = [i32, i32, i32]; lib.sgs_geodesic_state_words.restype = i64
         lib.sgs_geodesic_field.argtypes = [vp, vp, i32, i64, C.POINTER(SgsGeodesicParams), vp, i32, vp, i32, vp, vp, i32, vp, vp]
         lib.sgs_geodesic_path.argtypes = [vp, vp, i32, i64, C.POINTER(SgsGeodesicParams), vp, i32, vp, vp, i32, i32, vp, vp, vp]
+        lib.sgs_regions_tile.argtypes = []
+        lib.sgs_regions_work_words.argtypes = [i32, i32, i32]; lib.sgs_regions_work_words.restype = i64
+        lib.sgs_regions_label.argtypes = [vp, vp, i32, i64, C.POINTER(SgsRegionsParams), vp, vp, vp, C.c_int32, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

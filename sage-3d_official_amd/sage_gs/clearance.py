@@ -180,6 +180,19 @@ class ClearanceMap:
         from .geodesic import GeodesicField
         return GeodesicField.from_clearance(self, goals_xy=goals_xy)
 
+    def free_regions(self):
+        """The 8-connected regions of the cells an agent can stand on (d2 > the inflation limit): a sage_gs.regions.Regions of this
+        map, computed on the device at the first call and kept.  Two free cells have a path exactly when they share a label."""
+        if getattr(self, "_free_regions", None) is None:
+            from .regions import Regions
+            self._free_regions = Regions.of(self.d2, renderer=self._r, source="d2", lo=int(self.frame.max_d2) + 1)
+        return self._free_regions
+
+    def same_region(self, a_xy, b_xy) -> np.ndarray:
+        """bool [n]: whether positions a_xy[k] and b_xy[k] ([n, 2] or [n, 3], mapped to pixels as the checks map them, not clamped)
+        both lie on free cells of one region — whether a walk between them exists at all.  One gather on the device."""
+        return self.free_regions().same(self.cells_of(a_xy), self.cells_of(b_xy))
+
     def cells_of(self, xy) -> np.ndarray:
         """int64 [n, 2] = (i, j): the pixel of every position of xy, mapped and rounded as the queries map and round it (negation,
         flips, rint of a true division); not clamped — a position outside the map gives a cell outside 0 .. width - 1, 0 .. height - 1."""

@@ -1276,6 +1276,46 @@ class Renderer:
                                                     q.data_ptr(), n, max_len, cells.data_ptr(), info.data_ptr(), self._stream()), self._ctx)
         return cells, info.to(torch.int64) & 0xFFFFFFFF
 
+    # -- connected regions (include/sage_gs.h sgs_regions_label) -----------------------------------------------------------------------
+    def label_regions(self, src: torch.Tensor, *, source: Optional[str] = None, lo: int = 1, hi: Optional[int] = None, connectivity: int = 8,
+                      max_regions: int = 1024):
+        """The connected regions of the set lo <= v <= hi of grids on the device, a whole batch in one call: (labels, rows, counts).
+        src: a mask (uint8 or bool; hi defaults to 255, so lo = 1 is "non-zero") or a d2 map (int32 as clearance_map returns it; hi
+        defaults to 2^32 - 1, so lo = max_d2 + 1 is "where the agent can stand"), [ny,nx] or [B,ny,nx]; source ("mask" / "d2") is
+        inferred from the dtype.  labels int32 of src's shape: 0 outside the set, otherwise 1 + the number of regions whose least
+        raster index is smaller — scipy.ndimage.label's numbering, under connectivity 8 or 4.  rows int32 [max_regions,10] or
+        [B,max_regions,10] whose bytes are sgs_region_row (_capi.REGION_ROW_DTYPE): row r describes label r + 1 — area, tight box
+        (ends exclusive), the first raster index, the sums of x and y; a region whose label exceeds max_regions has no row, rows
+        past the number of regions are empty.  counts int32 [4] or [B,4]: regions found (the true number), cells in the set, the
+        largest area, the least label that has it.  max_regions = 0: rows is None.  The scratch is this method's.  Nothing is
+        copied to the host; asynchronous on the current stream.  All integer: a map's output does not depend on the batch."""
+        if source is None:
+            source = "d2" if getattr(src, "dtype", None) == torch.int32 else "mask"
+        if source not in ("mask", "d2"):
+            raise ValueError(f"unknown source {source!r}: 'mask' or 'd2'")
+        kind = _capi.REGIONS_SRC_MASK8 if source == "mask" else _capi.REGIONS_SRC_D2
+        maps, batched, b, ny, nx, stride = _maps_arg(src, self.device, torch.uint8 if source == "mask" else torch.int32, 1, "src")
+        top = 255 if source == "mask" else 0xFFFFFFFF
+        hi = top if hi is None else int(hi)
+        lo, max_regions = int(lo), int(max_regions)
+        if not 0 <= lo <= hi <= top:
+            raise ValueError(f"0 <= lo <= hi <= {top} for a {source} source")
+        if connectivity not in (4, 8):
+            raise ValueError("connectivity must be 4 or 8")
+        words = int(self._lib.sgs_regions_work_words(nx, ny, b))
+        if words < 0 or max_regions < 0:
+            raise ValueError(f"{b} maps of {nx} x {ny} cells, max_regions = {max_regions}: outside what sgs_regions_label takes")
+        labels = torch.empty((b, ny, nx), dtype=torch.int32, device=self.device)
+        rows = torch.empty((b, max_regions, _capi.REGION_ROW_WORDS), dtype=torch.int32, device=self.device) if max_regions else None
+        counts = torch.empty((b, 4), dtype=torch.int32, device=self.device)
+        work = torch.empty((words,), dtype=torch.int32, device=self.device)
+        params = _capi.SgsRegionsParams(nx, ny, kind, int(connectivity), lo, hi, 0, 0)
+        self._lib.check(self._lib.sgs_regions_label(self._ctx, maps.data_ptr(), b, stride, C.byref(params), work.data_ptr(), labels.data_ptr(),
+                                                    rows.data_ptr() if max_regions else None, max_regions, counts.data_ptr(), self._stream()), self._ctx)
+        if batched:
+            return labels, rows, counts
+        return labels[0], None if rows is None else rows[0], counts[0]
+
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
         self._lib.check(self._lib.sgs_mesh_set_record_capacity(self._ctx, int(n)), self._ctx)
