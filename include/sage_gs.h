@@ -867,6 +867,88 @@ int sgs_regions_label(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
                       uint32_t* work, int32_t* labels, sgs_region_row* out_rows, int32_t max_regions,
                       uint32_t* out_counts, void* hip_stream);
 
+/* ---- Item endpoints — the free cell beside an item ON THE SIDE THAT FACES a target.  What the reference's trajectory generator
+ * computes with get_nearest_free_pixel_on_side (a breadth-first search over Python sets, twice per candidate pair of items) before it
+ * plans between the two cells, and once per item in build_connectivity_map.  No new version: no existing struct changes.
+ *
+ *   Items     compressed sparse rows: item k is item_cells[item_offsets[k] .. item_offsets[k + 1]), raster indices y * nx + x,
+ *             duplicates allowed (they count in n and in the sums).  Every offset lies inside item_cells: the caller's contract.
+ *   Boundary  B: the distinct cells of the item with at least one 4-neighbour that is no cell of the item (outside the grid is none).
+ *   Field     d(c): the L1 distance from c to B — the level of the reference's search, which is 4-connected and walks through
+ *             obstacles.  Cells with d <= max_dist are examined.
+ *   Free      SGS_ENDPOINTS_SRC_MASK8: a byte of the uint8 [ny][nx] map is 0.  SGS_ENDPOINTS_SRC_D2: a word of the map
+ *             sgs_clearance_map wrote is > max_d2.
+ *   Side      with SGS_ENDPOINTS_QUERY_TOWARDS: (n x - Sx)(n tx - Sx) + (n y - Sy)(n ty - Sy) >= 0 in int64, n the item's entries
+ *             and S their sums — the sign of the reference's dot(c - mean, target - mean), exactly.
+ *   Answer    among the free cells on that side the least d; (x, y) the one of least raster index at that d; n_at_d how many there
+ *             are at that d (1: the reference's answer is forced to be this cell; otherwise the reference returns ONE of them, by the
+ *             iteration order of a hash table).  None is -1, -1, -1, 0: nothing within max_dist, a flagged item, item outside
+ *             0 .. n_items - 1, a target outside the grid, unknown query flags — checked on the device, no index derived from such a
+ *             query is used as an address.
+ *   Rows      out_items is one sgs_endpoints_item per item.  Flags: EMPTY (no entry, or offsets that decrease), BAD_CELL (an index
+ *             outside 0 .. nx * ny - 1), TOO_LONG (more than 2^19 entries; the slice is not read).  A flagged item has n and flags,
+ *             the empty box (x_min = y_min = INT32_MAX, x_end = y_end = 0), cx = cy = -1, and zeroes.  cx, cy: the sums over n
+ *             rounded half to even, the reference's instance_centroid_px.  boundary: |B|, valid when the work sufficed.
+ *   Counters  out_counts is uint64 [4]: [0] queries answered, [1] queries that answer none, [2] flagged items, [3] the bytes of work
+ *             this call needs.  When [3] > work_bytes the item rows (boundary 0) and the counters are written, every query answers
+ *             none, and the call still returns SGS_OK: call again with [3] bytes.  sgs_endpoints_work_bytes always suffices.
+ *   Kernels   sage-3d_official_amd/csrc/sgs_endpoints.h: a window per item of one byte per cell, a capped L1 distance transform from
+ *             wave ballots and two column sweeps, a reduction per query. */
+#define SGS_ENDPOINTS_SRC_MASK8 0
+#define SGS_ENDPOINTS_SRC_D2 1
+#define SGS_ENDPOINTS_MAX_N 4096
+#define SGS_ENDPOINTS_MAX_ITEMS 65535
+#define SGS_ENDPOINTS_MAX_DIST 63
+#define SGS_ENDPOINTS_MAX_ENTRIES (1u << 19)
+#define SGS_ENDPOINTS_MAX_QUERIES (1 << 22)
+#define SGS_ENDPOINTS_ITEM_EMPTY 1u
+#define SGS_ENDPOINTS_ITEM_BAD_CELL 2u
+#define SGS_ENDPOINTS_ITEM_TOO_LONG 4u
+#define SGS_ENDPOINTS_QUERY_TOWARDS 1u
+typedef struct sgs_endpoints_params {    /* 28 bytes */
+    int32_t  nx, ny;           /* cells; 1 <= nx, ny <= 4096 */
+    int32_t  source;           /* SGS_ENDPOINTS_SRC_* */
+    uint32_t max_d2;           /* SRC_D2: free iff d2 > max_d2; 0 with a mask */
+    int32_t  max_dist;         /* 0 .. 63; the reference's max_search_dist is 50 */
+    uint32_t flags;            /* 0 */
+    int32_t  reserved;         /* 0 */
+} sgs_endpoints_params;
+typedef struct sgs_endpoints_query {     /* 16 bytes */
+    int32_t  item;             /* 0 .. n_items - 1 */
+    int32_t  tx, ty;           /* the target cell, with SGS_ENDPOINTS_QUERY_TOWARDS */
+    uint32_t flags;            /* SGS_ENDPOINTS_QUERY_TOWARDS or 0 */
+} sgs_endpoints_query;
+typedef struct sgs_endpoints_item {      /* 56 bytes, 8-byte aligned */
+    uint32_t n;                /* entries of the list, duplicates included */
+    uint32_t flags;            /* SGS_ENDPOINTS_ITEM_* */
+    int32_t  x_min, y_min;     /* the tight box: x_min <= x < x_end, y_min <= y < y_end */
+    int32_t  x_end, y_end;
+    int32_t  cx, cy;           /* the centroid pixel */
+    uint32_t boundary;         /* |B| */
+    uint32_t reserved;         /* 0 */
+    uint64_t sum_x, sum_y;     /* of x and of y over the entries */
+} sgs_endpoints_item;
+typedef struct sgs_endpoints_answer {    /* 16 bytes */
+    int32_t  x, y;             /* the cell, or -1, -1 */
+    int32_t  d;                /* its L1 distance to B, or -1 */
+    int32_t  n_at_d;           /* candidates at that distance, or 0 */
+} sgs_endpoints_answer;
+/* The cells of one ballot word (the seams of the field's row pass), and the bytes of `work` that suffice for any n_items items on an
+ * nx x ny grid (-1 for arguments the call would refuse). */
+int sgs_endpoints_tile(void);
+int64_t sgs_endpoints_work_bytes(int nx, int ny, int n_items);
+/* All pointers are DEVICE buffers the caller owns; work is scratch whose contents before and after the call mean nothing.
+ * Stream-ordered and asynchronous: the call never synchronises and owns no scratch.  SGS_ERR_INVALID, before anything is enqueued or
+ * written, with a message that names the argument: null src, params, item_offsets, item_cells, work, out_items or out_counts; null
+ * queries or out_queries with n_queries > 0; n_items outside 1 .. 65535; n_queries outside 0 .. 2^22; nx or ny outside 1 .. 4096; an
+ * unknown source; max_dist outside 0 .. 63; max_d2 != 0 with a mask; flags or reserved != 0; work_bytes < 0; item_offsets,
+ * item_cells, queries, out_queries or a d2 src not 4-byte aligned; work, out_items or out_counts not 8-byte aligned; work overlapping
+ * out_items, out_queries or out_counts. */
+int sgs_endpoints(sgs_ctx* ctx, const void* src, const sgs_endpoints_params* params, const uint32_t* item_offsets,
+                  const int32_t* item_cells, int n_items, const sgs_endpoints_query* queries, int n_queries, void* work,
+                  int64_t work_bytes, sgs_endpoints_item* out_items, sgs_endpoints_answer* out_queries, uint64_t* out_counts,
+                  void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,7 @@
 #include "sgs_clearance.h"
 #include "sgs_geodesic.h"
 #include "sgs_regions.h"
+#include "sgs_endpoints.h"
 #include "sgs_own.h"
 
 namespace {
@@ -2551,6 +2552,78 @@ int sgs_regions_label(sgs_ctx* ctx, const void* src, int n_maps, int64_t map_str
     hipLaunchKernelGGL(sgs::k_reg_labels, dim3(chunks, maps), threads, 0, st, J);
     hipLaunchKernelGGL(sgs::k_reg_rows, dim3((unsigned)((cells + SGS_REG_ROW_REGION - 1) / SGS_REG_ROW_REGION), maps), threads, 0, st, J);
     hipLaunchKernelGGL(sgs::k_reg_largest, dim3(maps), threads, 0, st, J);
+    SGS_HIP(ctx, hipGetLastError());
+    return SGS_OK;
+}
+
+}  // extern "C"
+
+// ---- sgs_endpoints (csrc/sgs_endpoints.h) ----------------------------------------------------------------------------------------------------
+static_assert(sizeof(sgs_endpoints_params) == 28, "sgs_endpoints_params is seven 4-byte fields");
+static_assert(sizeof(sgs_endpoints_item) == sizeof(sgs::EpItem) && alignof(sgs_endpoints_item) == 8, "sgs_endpoints_item is the kernels' EpItem");
+static_assert(sizeof(sgs_endpoints_query) == sizeof(sgs::EpQuery) && sizeof(sgs_endpoints_answer) == sizeof(sgs::EpAnswer), "the kernels' query and answer are the header's");
+static_assert(SGS_ENDPOINTS_SRC_MASK8 == SGS_EP_SRC_MASK8 && SGS_ENDPOINTS_SRC_D2 == SGS_EP_SRC_D2 && SGS_ENDPOINTS_MAX_N == SGS_EP_MAX_N &&
+              SGS_ENDPOINTS_MAX_ITEMS == SGS_EP_MAX_ITEMS && SGS_ENDPOINTS_MAX_DIST == SGS_EP_MAX_DIST && SGS_ENDPOINTS_MAX_ENTRIES == SGS_EP_MAX_ENTRIES &&
+              SGS_ENDPOINTS_ITEM_EMPTY == SGS_EP_ITEM_EMPTY && SGS_ENDPOINTS_ITEM_BAD_CELL == SGS_EP_ITEM_BAD_CELL &&
+              SGS_ENDPOINTS_ITEM_TOO_LONG == SGS_EP_ITEM_TOO_LONG && SGS_ENDPOINTS_QUERY_TOWARDS == SGS_EP_QUERY_TOWARDS, "the kernels' constants are the header's");
+
+extern "C" {
+
+int sgs_endpoints_tile(void) { return SGS_EP_TILE; }
+
+int64_t sgs_endpoints_work_bytes(int nx, int ny, int n_items) {
+    if (nx < 1 || ny < 1 || nx > SGS_EP_MAX_N || ny > SGS_EP_MAX_N || n_items < 1 || n_items > SGS_EP_MAX_ITEMS) return -1;
+    return 8 * (int64_t)n_items + (((int64_t)n_items * nx * ny + 7) & ~(int64_t)7);   // the header, and every window the whole grid
+}
+
+int sgs_endpoints(sgs_ctx* ctx, const void* src, const sgs_endpoints_params* p, const uint32_t* item_offsets, const int32_t* item_cells,
+                  int n_items, const sgs_endpoints_query* queries, int n_queries, void* work, int64_t work_bytes,
+                  sgs_endpoints_item* out_items, sgs_endpoints_answer* out_queries, uint64_t* out_counts, void* hip_stream) {
+    if (!ctx) return SGS_ERR_INVALID;
+    const char* who = "sgs_endpoints"; const Args a = {ctx, who};
+    SGS_TRY(a.non_null(src, "src", p, "params", item_offsets, "item_offsets", item_cells, "item_cells", work, "work", out_items, "out_items",
+                       out_counts, "out_counts"));
+    if (n_queries < 0 || n_queries > SGS_ENDPOINTS_MAX_QUERIES) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_queries = %d (0 <= n_queries <= %d)", who, n_queries, SGS_ENDPOINTS_MAX_QUERIES);
+    if (n_queries > 0) SGS_TRY(a.non_null(queries, "queries", out_queries, "out_queries"));
+    if (n_items < 1 || n_items > SGS_EP_MAX_ITEMS) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: n_items = %d (1 <= n_items <= %d)", who, n_items, SGS_EP_MAX_ITEMS);
+    SGS_TRY(a.grid_within(p->nx, p->ny, SGS_EP_MAX_N));
+    if (p->source != SGS_ENDPOINTS_SRC_MASK8 && p->source != SGS_ENDPOINTS_SRC_D2) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown source %d", who, (int)p->source);
+    if (p->max_dist < 0 || p->max_dist > SGS_EP_MAX_DIST) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: max_dist = %d (0 <= max_dist <= %d)", who, (int)p->max_dist, SGS_EP_MAX_DIST);
+    if (p->source == SGS_ENDPOINTS_SRC_MASK8 && p->max_d2 != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: max_d2 = %u with a mask", who, (unsigned)p->max_d2);
+    if (p->flags != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: unknown flags 0x%x", who, (unsigned)p->flags);
+    if (p->reserved != 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: reserved = %d", who, (int)p->reserved);
+    if (work_bytes < 0) SGS_FAIL(ctx, SGS_ERR_INVALID, "%s: work_bytes = %lld", who, (long long)work_bytes);
+    SGS_TRY(a.aligned(4, item_offsets, "item_offsets", item_cells, "item_cells", queries, "queries", out_queries, "out_queries"));
+    if (p->source == SGS_ENDPOINTS_SRC_D2) SGS_TRY(a.aligned(4, src, "src"));        // a mask is read byte by byte
+    SGS_TRY(a.aligned(8, work, "work", out_items, "out_items", out_counts, "out_counts"));
+    SGS_TRY(a.disjoint(work, (uint64_t)work_bytes, "work", out_items, sizeof(sgs_endpoints_item) * (uint64_t)n_items, "out_items"));
+    SGS_TRY(a.disjoint(work, (uint64_t)work_bytes, "work", out_queries, sizeof(sgs_endpoints_answer) * (uint64_t)n_queries, "out_queries"));
+    SGS_TRY(a.disjoint(work, (uint64_t)work_bytes, "work", out_counts, 32, "out_counts"));
+    SGS_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int64_t header = 8 * (int64_t)n_items;
+    sgs::EpJob J;
+    J.src = src; J.offsets = item_offsets; J.cells = item_cells; J.queries = reinterpret_cast<const sgs::EpQuery*>(queries);
+    J.win_off = static_cast<unsigned long long*>(work); J.field = static_cast<unsigned char*>(work) + header;
+    J.items = reinterpret_cast<sgs::EpItem*>(out_items); J.answers = reinterpret_cast<sgs::EpAnswer*>(out_queries);
+    J.counts = reinterpret_cast<unsigned long long*>(out_counts);
+    J.work_bytes = (unsigned long long)work_bytes; J.has_header = work_bytes >= header;
+    J.nx = p->nx; J.ny = p->ny; J.n_items = n_items; J.n_queries = n_queries; J.kind = p->source; J.max_dist = p->max_dist; J.max_d2 = p->max_d2;
+    const dim3 threads(SGS_EP_THREADS);
+    const unsigned items = (unsigned)n_items;
+    // What a window can hold at most: the grid.  The kernels stride over what it does hold.
+    const auto blocks = [](int64_t units, int64_t per_block, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + per_block - 1) / per_block, cap)); };
+    const int64_t segs = (p->nx + SGS_EP_TILE - 1) / SGS_EP_TILE;
+    hipLaunchKernelGGL(sgs::k_ep_items, dim3(items), threads, 0, st, J);
+    hipLaunchKernelGGL(sgs::k_ep_scan, dim3(1), threads, 0, st, J);
+    if (work_bytes > header) {                                                       // otherwise no window fits and the field kernels would return at once
+        hipLaunchKernelGGL(sgs::k_ep_clear, dim3(blocks((work_bytes - header) / 8, SGS_EP_THREADS * 4, 4096)), threads, 0, st, J);
+        hipLaunchKernelGGL(sgs::k_ep_mark, dim3(blocks(SGS_EP_MAX_ENTRIES, SGS_EP_THREADS, 16), items), threads, 0, st, J);
+        hipLaunchKernelGGL(sgs::k_ep_boundary, dim3(blocks(segs * p->ny, SGS_EP_WAVES, 32), items), threads, 0, st, J);
+        hipLaunchKernelGGL(sgs::k_ep_rows, dim3(blocks(p->ny, SGS_EP_WAVES, 32), items), threads, 0, st, J);
+        hipLaunchKernelGGL(sgs::k_ep_cols, dim3(blocks(p->nx, SGS_EP_THREADS, 16), items), threads, 0, st, J);
+    }
+    if (n_queries > 0) hipLaunchKernelGGL(sgs::k_ep_query, dim3((unsigned)n_queries), threads, 0, st, J);
     SGS_HIP(ctx, hipGetLastError());
     return SGS_OK;
 }

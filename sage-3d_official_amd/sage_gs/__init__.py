@@ -25,14 +25,14 @@ from . import _capi  # noqa: F401,E402
 from ._capi import SgsError  # noqa: F401,E402
 
 __all__ = ["Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "TopdownGrid", "render", "default_renderer",
-           "SgsError", "scenes", "regions"]
+           "SgsError", "scenes", "regions", "trajectory"]
 
 
 def __getattr__(name):          # torch is imported only when the renderer is actually used
     if name in ("Camera", "RenderConfig", "Gaussians", "Renderer", "Scene", "Mesh", "TopdownGrid", "render", "default_renderer"):
         from . import renderer
         return getattr(renderer, name)
-    if name in ("scenes", "camera", "dist", "adapter", "ply", "mesh", "clearance", "geodesic", "regions"):
+    if name in ("scenes", "camera", "dist", "adapter", "ply", "mesh", "clearance", "geodesic", "regions", "trajectory"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -41,7 +41,8 @@ EXPORTS = ("sgs_version", "sgs_struct_sizes", "sgs_config_default", "sgs_create"
            "sgs_topdown_params_default", "sgs_topdown_map", "sgs_topdown_summary",
            "sgs_clearance_map", "sgs_clearance_query",
            "sgs_geodesic_tile", "sgs_geodesic_state_words", "sgs_geodesic_field", "sgs_geodesic_path",
-           "sgs_regions_tile", "sgs_regions_work_words", "sgs_regions_label")
+           "sgs_regions_tile", "sgs_regions_work_words", "sgs_regions_label",
+           "sgs_endpoints_tile", "sgs_endpoints_work_bytes", "sgs_endpoints")
 
 
 class SgsError(RuntimeError):
@@ -246,6 +247,26 @@ REGION_ROW_WORDS = 10
 assert C.sizeof(SgsRegionsParams) == 32 and REGION_ROW_DTYPE.itemsize == C.sizeof(SgsRegionRow) == 4 * REGION_ROW_WORDS
 
 
+ENDPOINTS_SRC_MASK8, ENDPOINTS_SRC_D2 = 0, 1  # include/sage_gs.h SGS_ENDPOINTS_*
+ENDPOINTS_MAX_N, ENDPOINTS_MAX_ITEMS, ENDPOINTS_MAX_DIST, ENDPOINTS_MAX_ENTRIES, ENDPOINTS_MAX_QUERIES = 4096, 65535, 63, 1 << 19, 1 << 22
+ENDPOINTS_ITEM_EMPTY, ENDPOINTS_ITEM_BAD_CELL, ENDPOINTS_ITEM_TOO_LONG = 1, 2, 4
+ENDPOINTS_QUERY_TOWARDS = 1
+
+
+class SgsEndpointsParams(C.Structure):
+    """include/sage_gs.h sgs_endpoints_params: the grid's size, what its source is, the free limit of a d2 map and the search distance."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("source", C.c_int32), ("max_d2", C.c_uint32), ("max_dist", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+# the three row types as NumPy records: sgs_endpoints_item (56 bytes), sgs_endpoints_query and sgs_endpoints_answer (16 bytes each)
+ENDPOINTS_ITEM_DTYPE = __import__("numpy").dtype([("n", "<u4"), ("flags", "<u4"), ("x_min", "<i4"), ("y_min", "<i4"), ("x_end", "<i4"), ("y_end", "<i4"),
+                                                  ("cx", "<i4"), ("cy", "<i4"), ("boundary", "<u4"), ("reserved", "<u4"), ("sum_x", "<u8"), ("sum_y", "<u8")])
+ENDPOINTS_QUERY_DTYPE = __import__("numpy").dtype([("item", "<i4"), ("tx", "<i4"), ("ty", "<i4"), ("flags", "<u4")])
+ENDPOINTS_ANSWER_DTYPE = __import__("numpy").dtype([("x", "<i4"), ("y", "<i4"), ("d", "<i4"), ("n_at_d", "<i4")])
+assert C.sizeof(SgsEndpointsParams) == 28 and ENDPOINTS_ITEM_DTYPE.itemsize == 56 and ENDPOINTS_QUERY_DTYPE.itemsize == ENDPOINTS_ANSWER_DTYPE.itemsize == 16
+
+
 class SgsStats(C.Structure):
     _fields_ = [("n_gaussians", C.c_int64), ("n_visible", C.c_int64), ("d_total", C.c_int64),
                 ("d_fetched", C.c_int64), ("n_pixels", C.c_int64), ("n_tiles", C.c_int32),
@@ -345,6 +366,9 @@ class Lib:
         lib.sgs_regions_tile.argtypes = []
         lib.sgs_regions_work_words.argtypes = [i32, i32, i32]; lib.sgs_regions_work_words.restype = i64
         lib.sgs_regions_label.argtypes = [vp, vp, i32, i64, C.POINTER(SgsRegionsParams), vp, vp, vp, C.c_int32, vp, vp]
+        lib.sgs_endpoints_tile.argtypes = []
+        lib.sgs_endpoints_work_bytes.argtypes = [i32, i32, i32]; lib.sgs_endpoints_work_bytes.restype = i64
+        lib.sgs_endpoints.argtypes = [vp, vp, C.POINTER(SgsEndpointsParams), vp, vp, i32, vp, i32, vp, i64, vp, vp, vp, vp]
 
     def __getattr__(self, name):
         return getattr(self._lib, name)

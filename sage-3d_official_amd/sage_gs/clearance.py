@@ -193,6 +193,12 @@ class ClearanceMap:
         both lie on free cells of one region — whether a walk between them exists at all.  One gather on the device."""
         return self.free_regions().same(self.cells_of(a_xy), self.cells_of(b_xy))
 
+    def nearest_free(self, item_set, towards=None, items=None, max_search_dist: int = 50) -> np.ndarray:
+        """For items of a sage_gs.trajectory.ItemSet the nearest cell an agent can stand on, on the side that faces a target: a record
+        array of (x, y, d, n_at_d), (-1, -1, -1, 0) for none — sage_gs.trajectory.nearest_free on this map's d2."""
+        from .trajectory import nearest_free
+        return nearest_free(item_set, self, towards, items, max_search_dist)
+
     def cells_of(self, xy) -> np.ndarray:
         """int64 [n, 2] = (i, j): the pixel of every position of xy, mapped and rounded as the queries map and round it (negation,
         flips, rint of a true division); not clamped — a position outside the map gives a cell outside 0 .. width - 1, 0 .. height - 1."""

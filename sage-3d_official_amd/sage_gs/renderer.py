@@ -271,6 +271,18 @@ def _maps_arg(src, device, dtype, per_cell, what):
     return maps, batched, b, ny, nx, _frame_stride(maps, ny * nx * per_cell)
 
 
+def _flat_i32(x, device, what):
+    """`x` — a tensor, or anything np.asarray takes — as a contiguous flat int32 tensor on `device` (uint32 values keep their bits)."""
+    if not isinstance(x, torch.Tensor):
+        a = np.asarray(x, np.int64).reshape(-1)
+        if a.size and (a.min() < -2 ** 31 or a.max() > 0xFFFFFFFF):
+            raise ValueError(f"{what} must fit 32 bits")
+        x = torch.from_numpy(a.astype(np.uint32).view(np.int32) if a.size and a.max() > 0x7FFFFFFF else a.astype(np.int32))
+    if x.dtype != torch.int32 or x.dim() != 1:
+        raise ValueError(f"{what} must be a flat int32 tensor")
+    return x.to(device).contiguous()
+
+
 def _rows_arg(x, device, dtype, width, what):
     """`x` — a tensor, or anything np.asarray takes — as a contiguous [n,width] tensor of `dtype` on `device`, n >= 1.  Host integers
     that do not fit `dtype` are refused (a tensor's values are not read)."""
@@ -1315,6 +1327,55 @@ class Renderer:
         if batched:
             return labels, rows, counts
         return labels[0], None if rows is None else rows[0], counts[0]
+
+    def endpoints(self, src: torch.Tensor, items, queries, *, source: Optional[str] = None, max_d2: int = 0, max_dist: int = 50):
+        """For every query the free cell nearest to an item's boundary on the side that faces a target (sgs_endpoints): (item_rows,
+        query_rows, counts).  src: one map on the device, a mask (uint8 or bool, free iff 0) or a d2 map (int32 as clearance_map
+        returns it, free iff d2 > max_d2); source ("mask" / "d2") is inferred from the dtype.  items: (offsets, cells), the CSR of the
+        items — int32 tensors on the device or anything np.asarray takes; offsets [n_items + 1], cells raster indices y * nx + x,
+        duplicates allowed.  queries: [n, 4] rows of (item, tx, ty, flags), flags bit 0: the target (tx, ty) is given.  item_rows
+        int32 [n_items, 14] whose bytes are sgs_endpoints_item (_capi.ENDPOINTS_ITEM_DTYPE), query_rows int32 [n, 4] = (x, y, d,
+        n_at_d) or (-1, -1, -1, 0), counts int64 [4]: answered, none, flagged items, bytes of scratch used.  The scratch is this
+        method's: a first guess from max_dist, and when the library reports that it needs more (counts[3], one read back), the call
+        is made again with that much.  All integer: an answer does not depend on the batch."""
+        if source is None:
+            source = "d2" if getattr(src, "dtype", None) == torch.int32 else "mask"
+        if source not in ("mask", "d2"):
+            raise ValueError(f"unknown source {source!r}: 'mask' or 'd2'")
+        kind = _capi.ENDPOINTS_SRC_MASK8 if source == "mask" else _capi.ENDPOINTS_SRC_D2
+        maps, batched, b, ny, nx, _ = _maps_arg(src, self.device, torch.uint8 if source == "mask" else torch.int32, 1, "src")
+        if batched:
+            raise ValueError("src must be one map [ny,nx]")
+        max_d2, max_dist = int(max_d2), int(max_dist)
+        if not 0 <= max_dist <= _capi.ENDPOINTS_MAX_DIST or not 0 <= max_d2 <= 0xFFFFFFFF or (source == "mask" and max_d2 != 0):
+            raise ValueError(f"0 <= max_dist <= {_capi.ENDPOINTS_MAX_DIST}; max_d2 is a d2 source's and fits 32 bits")
+        offsets, cells = items
+        offsets = _flat_i32(offsets, self.device, "item offsets")
+        cells = _flat_i32(cells, self.device, "item cells")
+        n_items = int(offsets.shape[0]) - 1
+        bound = int(self._lib.sgs_endpoints_work_bytes(nx, ny, n_items))
+        if bound < 0:
+            raise ValueError(f"{n_items} items on {nx} x {ny} cells: outside what sgs_endpoints takes")
+        q = _rows_arg(queries, self.device, torch.int32, 4, "queries") if (isinstance(queries, torch.Tensor) or len(queries)) else None
+        n_q = 0 if q is None else int(q.shape[0])
+        if n_q > _capi.ENDPOINTS_MAX_QUERIES:
+            raise ValueError(f"at most {_capi.ENDPOINTS_MAX_QUERIES} queries a call")
+        item_rows = torch.empty((n_items, 14), dtype=torch.int32, device=self.device)
+        query_rows = torch.empty((n_q, 4), dtype=torch.int32, device=self.device)
+        counts = torch.empty((4,), dtype=torch.int64, device=self.device)
+        params = _capi.SgsEndpointsParams(nx, ny, kind, max_d2, max_dist, 0, 0)
+        side = 2 * max_dist + 16                                                     # a window of a 16 x 16 item
+        want = min(bound, 8 * n_items + n_items * min(side, nx) * min(side, ny) + 8)
+        for _ in range(2):
+            work = torch.empty(((want + 7) // 8,), dtype=torch.int64, device=self.device)
+            self._lib.check(self._lib.sgs_endpoints(self._ctx, maps.data_ptr(), C.byref(params), offsets.data_ptr(), cells.data_ptr(), n_items,
+                                                    q.data_ptr() if n_q else None, n_q, work.data_ptr(), 8 * int(work.shape[0]), item_rows.data_ptr(),
+                                                    query_rows.data_ptr() if n_q else None, counts.data_ptr(), self._stream()), self._ctx)
+            need = int(counts[3].item())
+            if need <= 8 * int(work.shape[0]):
+                break
+            want = need
+        return item_rows, query_rows, counts
 
     def set_mesh_record_capacity(self, n: int):
         """Records (triangle, tile) the mesh path's buffer holds to start with (sgs_mesh_set_record_capacity); frames grow it as needed."""
