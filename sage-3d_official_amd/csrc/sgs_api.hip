@@ -61,6 +61,8 @@ struct sgs_scene {
     DevBuf<float4> geom, shq;
     DevBuf<float4> cbound;              // per chunk: bounding sphere of the means + largest scale (k_chunk_bounds)
     std::vector<unsigned> perm_host;    // Z-order: layout position -> original index (empty = identity)
+    DevBuf<unsigned> inv;               // its inverse on the device: original index -> layout position (empty = identity); a frame's splat
+                                        // records lie at layout positions and are found through it (sgs_kernels.h splat_at)
 };
 
 // The intermediates of ONE frame in flight.  Lane 0 serves ordinary frames on the caller's stream; pipelined
@@ -69,7 +71,7 @@ struct sgs_scene {
 // fill the chip better than back to back (measured +35 % frames/s with three lanes).
 struct Lane {
     // per-Gaussian scratch (ensure_splats)
-    DevBuf<Splat> splats;                        // one slot per Gaussian (slot == index)
+    DevBuf<Splat> splats;                        // one record per Gaussian, at its LAYOUT position (sgs_scene::inv)
     DevBuf<unsigned long long> vismask;          // per 64-Gaussian chunk: which slots are live this frame
     DevBuf<unsigned long long> bigmask;          //   ... and which of those went to the big-rect list
     DevBuf<unsigned> big_list;
@@ -705,7 +707,7 @@ int build_group(sgs_ctx* ctx, FrameGroup& G, const Group& g) {
     const int cp = SGS_TILE >> g.band.z;          // (the frames of a group share a resolution, a configuration and the fine-tile shift)
     const int gx = (g.cams->width + cp - 1) / cp, gy = (g.cams->height + cp - 1) / cp;
     memset(&G, 0, sizeof G);
-    G.geom = scene->geom.p; G.shq = scene->shq.p; G.cbound = scene->cbound.p; G.row_acc = ctx->row_acc.p;
+    G.geom = scene->geom.p; G.shq = scene->shq.p; G.cbound = scene->cbound.p; G.inv = scene->inv.p; G.row_acc = ctx->row_acc.p;
     for (int f = 0; f < g.nf; ++f) {
         Lane& A = ctx->lanes[g.lane0 + f];
         if ((rc = ensure_splats(ctx, A, scene->n)) != SGS_OK) return rc;
@@ -1010,7 +1012,8 @@ int layout_scene(sgs_ctx* ctx, sgs_scene* sc, const float* const* src, const sgs
     }
     if (n > 0) {
         // the probe (fine_shift_of): a pre-sample of up to 64 Ki Gaussians at even strides through the caller's order comes to the host (through
-        // the inverse of the Z-order permutation, in the sort's spare index buffer); 512 of them are drawn from it — systematically, with
+        // the inverse of the Z-order permutation, made in the sort's spare index buffer, which the scene then keeps: the composite finds a
+        // splat's record through it); 512 of them are drawn from it — systematically, with
         // probability 1/2 (1 / M0 + trace_i / sum of traces) each — and their covariances formed once
         const int M0 = (int)std::min<int64_t>(n, 65536), M = std::min(M0, 512);
         DevBuf<float4> own_probe;
@@ -1025,6 +1028,7 @@ int layout_scene(sgs_ctx* ctx, sgs_scene* sc, const float* const* src, const sgs
         hipLaunchKernelGGL(sgs::k_probe_gather, dim3((unsigned)((M0 + 255) / 256)), dim3(256), 0, 0, (long long)n, M0, d_inv, sc->geom.p, d_probe);
         SGS_HIP(ctx, hipMemcpy(rows.data(), d_probe, rows.size() * sizeof(float4), hipMemcpyDeviceToHost));
         own_probe.reset();
+        if (d_inv) sc->inv = std::move(own_idx[d_inv == idx[0] ? 0 : 1]);      // (the copy above has waited for k_invert_perm; one owner: the scene)
         {
             std::vector<double> tr((size_t)M0);
             double T = 0.0;
@@ -1489,13 +1493,19 @@ int read_chunk_skipped(sgs_ctx* ctx, const Lane& L, int64_t n_chunks, void* host
 }
 
 // device records (sgs_common.h: 64 B, conic pre-scaled for the composite, opacity also as an exponent offset) -> x,y,conic a,b | c,opacity,r,g | b,depth,rect01,rect23
-int read_splats(sgs_ctx* ctx, const Lane& L, void* host_dst, int64_t n, int64_t elem) {
-    const int64_t cnt = n / elem;
-    std::vector<Splat> tmp((size_t)std::max<int64_t>(1, cnt));
-    SGS_HIP(ctx, hipMemcpy(tmp.data(), L.splats.p, (size_t)cnt * sizeof(Splat), hipMemcpyDeviceToHost));
+// The device holds a record at its Gaussian's LAYOUT position; the caller gets it at the ORIGINAL index (perm: layout position -> original
+// index, nullptr = identity; the padding of the last chunk lies behind both orders).
+int read_splats(sgs_ctx* ctx, const FrameRec& r, const Lane& L, void* host_dst, int64_t n, int64_t elem) {
+    const int64_t cnt = n / elem, n_slots = (r.n + 63) / 64 * 64;
+    const unsigned* perm = r.scene && !r.scene->perm_host.empty() ? r.scene->perm_host.data() : nullptr;
+    const int64_t n_read = perm ? n_slots : cnt;           // (a short read of a permuted scene may want any of the records)
+    std::vector<Splat> tmp((size_t)std::max<int64_t>(1, n_read));
+    SGS_HIP(ctx, hipMemcpy(tmp.data(), L.splats.p, (size_t)n_read * sizeof(Splat), hipMemcpyDeviceToHost));
     const double l2e = 1.4426950408889634;
-    for (int64_t i = 0; i < cnt; ++i) {
-        const Splat& sp = tmp[(size_t)i];
+    for (int64_t p = 0; p < n_read; ++p) {
+        const int64_t i = perm && p < r.n ? (int64_t)perm[(size_t)p] : p;
+        if (i >= cnt) continue;
+        const Splat& sp = tmp[(size_t)p];
         float* o = (float*)((char*)host_dst + i * elem);
         o[0] = sp.x; o[1] = sp.y;
         // (the record holds the roots of the completed square A (dx + k dy)^2 + C' dy^2 in the slots A, B, C: a = sqrt(A),
@@ -1509,8 +1519,8 @@ int read_splats(sgs_ctx* ctx, const Lane& L, void* host_dst, int64_t n, int64_t 
     return SGS_OK;
 }
 
-// A splat lives at its Gaussian's index; the per-chunk visibility masks say which are live.  Dead slots are blanked (slot ids ->
-// 0xFFFFFFFF, splats -> 0) so stale data cannot pass for live.
+// The caller sees a splat at its Gaussian's index (read_splats); the per-chunk visibility masks, by layout position, say which are live.
+// Dead slots are blanked (slot ids -> 0xFFFFFFFF, splats -> 0) so stale data cannot pass for live.
 int blank_dead_slots(sgs_ctx* ctx, const FrameRec& r, const Lane& L, bool slot_ids, void* host_dst, int64_t n, int64_t elem) {
     const int64_t n_chunks = (r.n + 63) / 64, n_slots = n_chunks * 64;
     std::vector<unsigned long long> vm((size_t)std::max<int64_t>(1, n_chunks));
@@ -1572,7 +1582,7 @@ int64_t sgs_debug_read(sgs_ctx* ctx, int what, void* host_dst, int64_t bytes) {
     if (what == SGS_BUF_SCENE_GEOM) rc = read_scene_geom(ctx, sc, n_slots, host_dst, n);
     if (what == SGS_BUF_SCENE_SH) rc = read_scene_sh(ctx, sc, n_slots, host_dst, n);
     if (what == SGS_BUF_CHUNK_SKIPPED) rc = read_chunk_skipped(ctx, L, n_chunks, host_dst, n);
-    if (what == SGS_BUF_SPLATS) rc = read_splats(ctx, L, host_dst, n, elem);
+    if (what == SGS_BUF_SPLATS) rc = read_splats(ctx, r, L, host_dst, n, elem);
     if (rc == SGS_OK && elem) rc = blank_dead_slots(ctx, r, L, what == SGS_BUF_SLOT_IDS, host_dst, n, elem);
     return rc != SGS_OK ? rc : have;
 }

@@ -143,13 +143,17 @@ struct FrameSlot {
 };
 struct FrameGroup {
     const float4* geom; const float4* shq; const float4* cbound;      // the scene (shared by the group's frames)
+    const unsigned* inv;                                               // original index -> layout position (nullptr: the scene is in the caller's order)
     unsigned long long* row_acc;                                       // per-row record counters of the context
     FrameSlot s[SGS_MAX_GROUP];
 };
+static_assert(sizeof(FrameGroup) <= 4096, "FrameGroup is passed by value: it must stay inside the 4-KiB kernarg segment");
 
-// One projected Gaussian ("splat"): 64 B, 64-B aligned — exactly one HBM access sector, written once per frame by
-// k_preprocess (at the Gaussian's ORIGINAL index: with the scene in Z-order that is a scatter, and a 48-B record
-// straddling sectors made every such write a read-modify-write) and gathered by k_tile_render.  Everything the composite
+// One projected Gaussian ("splat"): 64 B, 64-B aligned — exactly one HBM access sector (a 48-B record straddling sectors made
+// every write a read-modify-write), written once per frame by k_preprocess at the Gaussian's LAYOUT position — a chunk's visible
+// lanes write one contiguous run of at most 4 KiB; at the original index, with the scene in Z-order, the same store was a scatter
+// of 64 sectors over the whole buffer — and gathered by k_tile_render, which names a splat by its ORIGINAL index (the tile records,
+// the depth ties) and finds its record through the scene's inverse permutation (splat_at, sgs_kernels.h).  Everything the composite
 // needs per (splat, tile) that does not depend on the tile is computed here once, per splat:
 //   word 0..3   x, y, a, a k          q2(d) = A dx^2 + B dx dy + C dy^2 = -power * log2(e)  (A = conic_a log2(e)/2, B = conic_b log2(e), ...)
 //                                     as the completed square A (dx + k dy)^2 + C' dy^2 (k = B / 2A, C' = C - B^2 / 4A), stored by its

@@ -814,8 +814,8 @@ __device__ __forceinline__ void preprocess_chunk(const FrameParams& P, const flo
         }
     }
 
-    // No compaction: a splat lives at its Gaussian's ORIGINAL index (slot), and the wave's ballot is the
-    // chunk's visibility mask.  Ties on depth can then break on the slot number itself.
+    // No compaction: a splat is NAMED by its Gaussian's ORIGINAL index (slot) — so ties on depth break on the slot number
+    // itself — its record lives at the layout position, and the wave's ballot is the chunk's visibility mask.
     const unsigned long long vmask = __ballot(vis);
     // A splat whose rect covers hundreds of tiles (a near-camera Gaussian) would keep ONE wave of the
     // binning kernels busy for its whole expansion; those few go to a global list instead and are
@@ -859,7 +859,9 @@ __device__ __forceinline__ void preprocess_chunk(const FrameParams& P, const flo
         }
         const float depth = (float)tz;
         // the record of the composite (sgs_common.h): constants folded per splat, not per (splat, tile) or per pixel
-        float4* sp = reinterpret_cast<float4*>(splats + slot);
+        // (stored at the LAYOUT position: the chunk's visible lanes write one contiguous run; readers that name a splat by its
+        //  original index find the record through splat_at)
+        float4* sp = reinterpret_cast<float4*>(splats + pos);
         // q2 = -power * log2(e) = A dx^2 + B dx dy + C dy^2 with the fp32 conic (ca, cb, cc) — the form S6 defines — is stored as
         // the completed square  A (dx + k dy)^2 + C' dy^2,  k = B / 2A,  C' = C - B^2 / 4A = det / A,  derived in fp64 FROM the
         // fp32 conic: two non-negative terms instead of three that cancel.  A needle (sigma_minor ~ 0.55 px from the dilation,
@@ -1706,12 +1708,17 @@ __device__ __forceinline__ void radix_sort_bits(unsigned* a_k, unsigned* a_v, un
     }
 }
 
+// Where the record of the splat named `slot` (a Gaussian's ORIGINAL index) lies in the frame's splat buffer: at the Gaussian's layout
+// position (preprocess_chunk), i.e. through the inverse of the scene's Z-order permutation; inv == nullptr (wave-uniform): the scene is in
+// the caller's order.  EVERY reader of a record by index goes through here.
+__device__ __forceinline__ unsigned splat_at(const unsigned* __restrict__ inv, unsigned slot) { return inv ? inv[slot] : slot; }
+
 // Sorts (k,v)[0..n) by (depth bits, slot); b_k/b_v are ping-pong space of the same size.  A splat's
 // slot IS its Gaussian index, so ties on depth break on v itself.  Keys lie in [sub, sub + 2^nbits).
 // All threads of the workgroup must call it.  (Used for depth buckets too long for the LDS rank sort.)
 __device__ __forceinline__ void sort_segment(unsigned* a_k, unsigned* a_v, unsigned* b_k, unsigned* b_v,
                                              unsigned n, unsigned sub, unsigned nbits, SortShared& sh,
-                                             const Splat* __restrict__ splats, long long n_gauss,
+                                             const Splat* __restrict__ splats, const unsigned* __restrict__ inv, long long n_gauss,
                                              FrameStatus* st) {
     const unsigned tid = threadIdx.x;
     if (tid == 0) sh.flag = 0u;
@@ -1742,7 +1749,7 @@ __device__ __forceinline__ void sort_segment(unsigned* a_k, unsigned* a_v, unsig
         __syncthreads();
         const unsigned idbits = n_gauss > 1 ? 64u - (unsigned)__clzll((long long)(n_gauss - 1)) : 1u;
         radix_sort_bits(a_k, a_v, b_k, b_v, n, 0u, idbits, sh);
-        for (unsigned i = tid; i < n; i += 256) a_k[i] = splats[a_v[i]].key;
+        for (unsigned i = tid; i < n; i += 256) a_k[i] = splats[splat_at(inv, a_v[i])].key;
         __syncthreads();
         radix_sort_bits(a_k, a_v, b_k, b_v, n, sub, nbits, sh);
         if (tid == 0) atomicAdd(&st->n_resort_tiles, 1u);
@@ -2104,7 +2111,7 @@ template <bool AUX, bool STATS, bool TF>
 #ifndef SGS_RENDER_WGS
 #define SGS_RENDER_WGS 5
 #endif
-__device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned bx) {
+__device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned* __restrict__ inv, const unsigned bx) {
     static_assert(TF || !AUX, "the coverage output needs the final transmittance");
     const FrameParams& P = S.P;
     const uint4* __restrict__ tile_order = S.tile_order;
@@ -2571,7 +2578,7 @@ __device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned b
                     const unsigned i = r0 + (unsigned)tid + 256u * (unsigned)u;
                     hv[u] = i < wcnt;
                     kq[u] = hv[u] ? s_q[lo - win_lo + i] : ~0ull;
-                    const float4* const sp = reinterpret_cast<const float4*>(splats + (hv[u] ? (unsigned)kq[u] : 0u));
+                    const float4* const sp = reinterpret_cast<const float4*>(splats + splat_at(inv, hv[u] ? (unsigned)kq[u] : 0u));
                     qA[u] = sp[0]; qc[u] = *reinterpret_cast<const float*>(sp + 1);
                     qh[u] = reinterpret_cast<const float2*>(sp + 2)[1]; qm[u] = *reinterpret_cast<const float*>(sp + 3);
                 }
@@ -2619,7 +2626,8 @@ __device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned b
             // UNCONDITIONAL loads (lanes without a record read slot 0 and never use it): inside `if (have)` the
             // compiler has to merge the loaded registers with their defaults at the end of the branch, i.e. wait for
             // the gather right here — instead of behind the ranking below, which is what hides its latency
-            const float4* const sp = reinterpret_cast<const float4*>(splats + (have ? (unsigned)mine : 0u));
+            // (the record's position is looked up first, unconditionally too: the lookup and the gather both hide behind the ranking)
+            const float4* const sp = reinterpret_cast<const float4*>(splats + splat_at(inv, have ? (unsigned)mine : 0u));
             const float4 nA = sp[0], nB = sp[1], nC = sp[2];
             const float nD = *reinterpret_cast<const float*>(sp + 3);           // qmax
             // Rank of my record inside the group.  The resident queue is bucket-contiguous (MSD partition) and the
@@ -2733,7 +2741,7 @@ __device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned b
                 b_k[i] = (unsigned)(x >> 32); b_v[i] = (unsigned)x;
             }
             __syncthreads();
-            sort_segment(b_k, b_v, a_k, a_v, cnt, sub, nbits, sh, splats, P.n, st);
+            sort_segment(b_k, b_v, a_k, a_v, cnt, sub, nbits, sh, splats, inv, P.n, st);
             gv = b_v;
             if (tid == 0) atomicAdd(&st->class_count[3], 1u);
             if (full_sort) {
@@ -2759,7 +2767,7 @@ __device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned b
                 unsigned qbits = 0;
                 if (tid == 0) SGS_STAGE_DUMMY()       // (the arena is shared with the sort scratch: rewritten per batch)
                 if (have) {
-                    const float4* sp = reinterpret_cast<const float4*>(splats + gv[gb + (unsigned)tid]);
+                    const float4* sp = reinterpret_cast<const float4*>(splats + splat_at(inv, gv[gb + (unsigned)tid]));
                     const float4 nA = sp[0], nB = sp[1], nC = sp[2];
                     const float qmax = *reinterpret_cast<const float*>(sp + 3), hx = nC.z, hy = nC.w;
                     const float rx = nA.x - tile_fx, ry = nA.y - tile_fy;          // centre relative to the tile
@@ -2847,7 +2855,7 @@ __device__ __forceinline__ void render_tile(const FrameSlot& S, const unsigned b
 
 template <bool AUX, bool STATS, bool TF>
 __global__ __launch_bounds__(256, AUX ? 4 : SGS_RENDER_WGS) void k_tile_render(const FrameGroup G) {
-    render_tile<AUX, STATS, TF>(G.s[blockIdx.y], blockIdx.x);
+    render_tile<AUX, STATS, TF>(G.s[blockIdx.y], G.inv, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
